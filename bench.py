@@ -23,13 +23,22 @@ over the ranks (dist.shard_jobs); each rank reduces its shard to one Fp12
 Miller product, the 576-byte partials are all-gathered over RCCL and ONE
 final exponentiation runs on their product, then the per-block verdicts are
 all-gathered.  --weak: every rank verifies its own segment.
-A second measurement times the gossip batch (BASELINE configs[1], "C2":
-64 aggregate sets x 128 pubkeys, batchable, one job) for the p50 latency.
+
+A plain run does only what the headline figure needs: set-up, warm-up, the K
+timed steps, the result line.  --full adds every other measurement to the
+line, each a run of its own after the timed steps: the lone batch
+(one_in_flight), the gossip batch (BASELINE configs[1], "C2": 64 aggregate
+sets x 128 pubkeys, batchable, one job) and the other C1/C2/C3/C5 latencies,
+the host-resident, epoch-slice, mixed-size, shard-projection, weak-scaling and
+reserved-device legs, the roofline (its microbenchmarks) and the CPU baseline.
+--dump-outputs DIR writes what the last timed step returned to its caller
+(the per-block verdicts) as DIR/job_results.npy, float32.
 
 Synthetic data: keys sk_i = SHA256("bgv-sk"||LE64(seed)||LE32(i)) mod r and
-signatures are generated on the device (bgv_gen_keys / bgv_gen_sign).
+signatures are generated on the device (bgv_gen_keys / bgv_gen_sign); the
+inputs depend on the arguments alone, so two runs verify the same batch.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--blocks B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--blocks B] [--full] [--dump-outputs DIR]
 """
 from __future__ import annotations
 
@@ -583,11 +592,17 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--blocks", type=int, default=1024, help="blocks in the segment (1024 = 32 epochs)")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-c2", action="store_true", help="skip the C1/C2/C3/C5, host-resident and shard legs (profiling runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every other measurement (lone batch, C1/C2/C3/C5 latencies, "
+                         "host-resident / epoch / mixed / shard / weak-scaling / reserved-device legs, roofline, CPU baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (the per-block verdicts) as DIR/job_results.npy (float32)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-c2", action="store_true",
+                    help="--full: skip the C1/C2/C3/C5, host-resident and shard legs (profiling runs)")
     ap.add_argument("--weak", action="store_true",
                     help="N > 1: every rank verifies its own segment (default: ONE segment split across the ranks, BASELINE configs[3])")
-    ap.add_argument("--no-weak-leg", action="store_true", help="N > 1: skip the extra weak-scaling measurement")
+    ap.add_argument("--no-weak-leg", action="store_true", help="--full, N > 1: skip the extra weak-scaling measurement")
     ap.add_argument("--inflight", type=int, default=0,
                     help="batches in flight per GPU: contexts on the GPU, one worker thread each (dist.run_in_flight); "
                          "0 = auto (3, or 4 for batches under 32,000 sets per GPU)")
@@ -669,6 +684,7 @@ def main():
     ex = ThreadPoolExecutor(max_workers=args.inflight)
     stage_sum = np.zeros(native.N_STAGES)
     t_sub, lat = {}, []
+    last_out = {}  # what the latest finished step returned to its caller (--dump-outputs)
 
     # the inputs are written once above and only read by the steps: one
     # synchronisation here instead of a wait for torch's stream on every call
@@ -687,13 +703,16 @@ def main():
         c = ds[k % len(ds)]
         if world == 1:
             ok = bool((res[0] == 1).all())
+            last_out["job_results"] = res[0]
         else:
             valid, local_jr = combine_sharded(c, res, dist, device=coll_dev)
             if shard:  # every rank ends with the whole segment's per-block verdicts
                 full = gather_job_results(local_jr, shards, seg["n_jobs"], dist, device=coll_dev)
                 ok = valid and bool((full == 1).all())
+                last_out["job_results"] = full
             else:
                 ok = valid and bool((local_jr == 1).all())
+                last_out["job_results"] = local_jr
         lat.append((time.perf_counter() - t_sub.pop(k)) * 1e3)
         stage_sum[:] += np.array(list(c.last_stats.stage_ms))
         return ok
@@ -724,8 +743,17 @@ def main():
     ms_per_step = elapsed / args.steps * 1e3
     value = total_sets * args.steps / elapsed
 
+    if args.dump_outputs and rank == 0:
+        # the arrays the caller of the last timed step received: the per-block
+        # verdicts (1 valid, 0 invalid, -code rejected; 4 KB for the segment)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, v in last_out.items():
+            v = v.cpu().numpy() if hasattr(v, "cpu") else np.asarray(v)
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), v.astype(np.float32))
+
     timed_layout = d.last_stats.layout()  # the variant the timed batches ran with (bgv_stats), before the extra legs
-    if not stage_sum.any():  # untimed shard steps: one step of the same shard on a timed context, after the timed region
+    # untimed shard steps: with --full, one step of the same shard on a timed context, after the timed region
+    if args.full and not stage_sum.any():
         dt = native.Device(gpu, timing=1)
         dt.gen_keys(0, N_VALIDATORS, SEED)
         dt.partial(darr, on_device=True)
@@ -735,13 +763,13 @@ def main():
 
     legs = {}
     iso_stage_ms = None
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         # the same batch with ONE in flight (the r01-r05 step): its latency and
         # the kernels' durations without other batches beside them
         legs["one_in_flight"], iso_stage_ms = one_in_flight(d, darr, torch)
-    if shard and not args.no_weak_leg:
+    if args.full and shard and not args.no_weak_leg:
         legs["weak_scaling"] = weak_leg(ds, torch, dev, dist, coll_dev, rank, world, args)
-    if rank == 0 and world == 1 and not args.no_c2:
+    if args.full and rank == 0 and world == 1 and not args.no_c2:
         legs.update(small_configs(d, torch, dev, arrays))
         host = dict(arrays)
         host["sigs"] = sigs.cpu().numpy()
@@ -762,7 +790,7 @@ def main():
     # is the stage with the largest time (stages overlap on three streams)
     roof = None
     counts = fpmul_counts()
-    if rank == 0:
+    if args.full and rank == 0:
         mad_ms = d.bench_mad(256 * 256 * 8, 4096)
         mad_rate = 256 * 256 * 8 * 4096 * 8 / (mad_ms * 1e-3)  # lane-ops/s
         peak_fpmul = mad_rate / 288.0 / 1e9
@@ -837,7 +865,7 @@ def main():
     # a queue's scratch allocation failed there (HSA_STATUS_ERROR_OUT_OF_RESOURCES
     # with the other contexts' queues holding theirs), so a failure is recorded
     # in the leg instead of ending the run
-    if rank == 0 and world == 1 and not args.no_c2:
+    if args.full and rank == 0 and world == 1 and not args.no_c2:
         for c in ds[1:]:
             c.close()
         try:
@@ -846,7 +874,7 @@ def main():
             legs["reserved_device"] = {"error": f"{type(e).__name__}: {e}"[:400]}
 
     if rank == 0:
-        cpu = None if (args.no_cpu or world > 1) else cpu_baseline()
+        cpu = cpu_baseline() if (args.full and not args.no_cpu and world == 1) else None
         par = (f"one segment sharded by job over {world} GPUs (shard_jobs), RCCL all-gather of Miller partials + per-job verdicts"
                if shard else f"one segment per GPU x{world}, RCCL all-gather of Miller partials")
         par += f"; {args.inflight} batches in flight per GPU (contexts, dist.run_in_flight)"
@@ -857,6 +885,7 @@ def main():
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": args.full,
             "ms_per_step": round(ms_per_step, 3),
             "higher_is_better": True,
             "scaling": "weak" if args.weak else "strong",

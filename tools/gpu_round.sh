@@ -9,6 +9,7 @@ rc=$?
 tail -5 gpurun_out/gputest.log
 if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then echo "pytest exit $rc: stopping"; exit $rc; fi
 [ -n "$NO_BENCH" ] && exit $rc
+BENCH_ARGS="--full ${BENCH_ARGS:-}"  # the whole line: every leg, roofline, CPU baseline
 timeout -k 10 ${BENCH_TIMEOUT:-600} python -u bench.py ${BENCH_ARGS:-} > gpurun_out/bench.json 2> gpurun_out/bench.log
 brc=$?
 tail -3 gpurun_out/bench.log

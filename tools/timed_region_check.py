@@ -2,7 +2,7 @@
 
     python3 tools/timed_region_check.py TRACE_kernel_trace.csv BENCH.json [--inflight 3 --steps 20 --warmup 1]
 
-The trace is `rocprofv3 --kernel-trace` of `bench.py --no-c2 --no-cpu --steps K`
+The trace is `rocprofv3 --kernel-trace` of `bench.py --full --no-c2 --no-cpu --steps K`
 (one C4 batch per step, D in flight).  Per kernel the dispatches come in bench
 order: D context-priming batches, W warm-up batches, the K timed batches, then
 the one_in_flight leg (1 + 5 lone batches).  For each stage's main kernel the
@@ -34,7 +34,7 @@ def main():
         name = r["Kernel_Name"].split("(")[0].replace("bgv::", "").strip()
         d[name].append((int(r["Start_Timestamp"]), int(r["End_Timestamp"])))
     first = args.inflight + args.warmup
-    print(f"rocprofv3 --kernel-trace of `bench.py --no-c2 --no-cpu --steps {args.steps}` ({args.inflight} batches in flight);")
+    print(f"rocprofv3 --kernel-trace of `bench.py --full --no-c2 --no-cpu --steps {args.steps}` ({args.inflight} batches in flight);")
     print(f"dispatch order per kernel: {args.inflight} context-priming + {args.warmup} warm-up batches, the {args.steps} timed "
           "batches, then one_in_flight (1 + 5).")
     for k, stage in KERNELS:

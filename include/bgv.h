@@ -238,6 +238,85 @@ int bgv_verify(bgv_ctx* ctx, const bgv_batch* batch, int32_t* job_result, int32_
  * (bgv_verify, bgv_partial, bgv_partial_finish); counters are left zero. */
 int bgv_last_stats(bgv_ctx* ctx, bgv_stats* stats);
 
+/* ---- same-message batches --------------------------------------------------
+ * IBlsVerifier.verifySignatureSetsSameMessage (upstream Lodestar): gossip
+ * attestations (chain/validation/attestation.ts:271) are single-pubkey sets,
+ * and all members of a committee that vote for the same head sign the same
+ * signing root.  For sets that share a message
+ *   prod_i e(pk_i, H(m))^{r_i} = e(sum_i r_i pk_i, H(m)),
+ * so a group of n sets needs n signature decodes and subgroup checks, one
+ * weighted G1 sum over table rows, one weighted G2 sum, ONE hash and TWO
+ * Miller pairs.  Additive to ABI 4: no existing entry point changes.
+ *
+ * Sets are grouped by message: group g owns sets [group_offsets[g],
+ * group_offsets[g+1]) and msgs holds one root per GROUP.  Every set has
+ * exactly one key: pk_indices[i] is a table row, or with bit 31 set a row of
+ * raw_pks, as in bgv_batch.  Host batches are staged and checked like
+ * bgv_batch (offsets monotone and spanning [0, n_sets], scalars non-zero);
+ * an empty group, or n_groups > n_sets, is BGV_E_INVALID_ARG.  On-device
+ * batches are trusted to satisfy the contract.  n_sets == 0 succeeds with no
+ * output.
+ *
+ * The result is per set, because callers act per attestation:
+ *  - A set is rejected before aggregation, with set_valid = 0 and its
+ *    bgv_set_code, and left out of its group's sums when its signature does
+ *    not decode or fails the subgroup check (codes as bgv_verify), is the
+ *    identity (BGV_SET_VERIFY_FAIL), when its index is out of range
+ *    (BGV_SET_INDEX_RANGE) or its key is the identity
+ *    (BGV_SET_PK_IS_INFINITY).  One malformed signature does not force its
+ *    neighbours into the retry.
+ *  - Groups are cut into segments of at most 64 sets.  Per segment over the
+ *    surviving sets P = sum r_i pk_i and S = sum r_i sigma_i; one whole-batch
+ *    check prod ML(P, H(m_g)) ML(-G1, S) with one final exponentiation.  On
+ *    success every surviving set is valid.
+ *  - If it fails: one final exponentiation per segment, then every surviving
+ *    set of a failing segment is decided on its own, e(pk_i, H(m_g))
+ *    e(-G1, sigma_i) == 1, as a one-set job of the ordinary pipeline, inside
+ *    the same call.  Such a set has set_valid = 0 and set_code 0 when it fails.
+ *  - A segment whose P is the identity (e.g. a key beside its negation with
+ *    equal scalars) is no error: its pair is skipped and its sets go to the
+ *    per-set retry.
+ * The call runs on the context's streams and counts as a batch in flight like
+ * bgv_verify.                                                                */
+typedef struct bgv_sm_batch {
+  uint32_t n_sets;               /* single-pubkey sets */
+  uint32_t n_groups;             /* distinct messages */
+  const uint32_t* group_offsets; /* [n_groups + 1] */
+  const uint32_t* pk_indices;    /* [n_sets]; bit 31 selects raw_pks */
+  const uint8_t* raw_pks;        /* [n_raw][96], may be NULL */
+  uint32_t n_raw;
+  const uint8_t* msgs;           /* [n_groups][32] */
+  const uint8_t* sigs;           /* [n_sets][192] */
+  const uint32_t* sig_len;       /* [n_sets] */
+  const uint64_t* scalars;       /* [n_sets] non-zero, or NULL = drawn on the device as bgv_verify does */
+  uint32_t on_device;
+} bgv_sm_batch;
+
+/* counters that show which path ran */
+typedef struct bgv_sm_stats {
+  uint32_t n_sets, n_groups, n_segments;
+  uint32_t hashes;         /* hash_to_G2 evaluations in the first pass */
+  uint32_t pairs;          /* Miller pairs in the first pass */
+  uint32_t groups_retried; /* groups with a segment that went to the per-set retry */
+  uint32_t sets_retried;   /* sets decided on their own */
+  float total_ms;          /* host clock around the call */
+} bgv_sm_stats;
+
+/* set_valid[n_sets] (host memory) 1 / 0 per set; set_code[n_sets] (host
+ * memory, may be NULL) bgv_set_code of a rejected set, else 0; stats may be
+ * NULL. */
+int bgv_verify_same_message(bgv_ctx* ctx, const bgv_sm_batch* batch, uint8_t* set_valid, int32_t* set_code,
+                            bgv_sm_stats* stats);
+/* The host-side contract check of bgv_verify_same_message on its own (no
+ * device, no context): BGV_OK or BGV_E_INVALID_ARG with bgv_last_error().
+ * Offsets and scalars of an on-device batch are not read. */
+int bgv_sm_check(const bgv_sm_batch* batch);
+/* test-only: bgv_verify_same_message plus, per GROUP, P_g (96 B affine), S_g
+ * (192 B affine) and H(m_g) (192 B affine) in the byte layout of bgv_debug,
+ * all-zero for the identity.  Any output pointer may be NULL. */
+int bgv_debug_same_message(bgv_ctx* ctx, const bgv_sm_batch* batch, uint8_t* set_valid, int32_t* set_code,
+                           bgv_sm_stats* stats, uint8_t* p_group96, uint8_t* s_group192, uint8_t* h_group192);
+
 /* Multi-GPU partials: run the batch up to, but excluding, the
  * final exponentiation and return this shard's Miller product (576 B, 12
  * Fp coefficients of w^0..w^5, c0||c1 each, 48-byte big-endian) with the

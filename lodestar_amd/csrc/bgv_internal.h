@@ -156,4 +156,58 @@ void launch_bench_fpmul(hipStream_t st, fp_t* io, uint32_t lanes, uint32_t iters
 void launch_gen_scalars(hipStream_t st, const uint32_t key[8], const uint32_t nonce[3], uint64_t* out, uint32_t n);
 void launch_bench_mad(hipStream_t st, uint64_t* io, uint32_t lanes, uint32_t iters);
 
+// ---- same-message batches (bgv_verify_same_message, bgv_same_msg.hip) -------
+// Single-pubkey sets grouped by message; every group is cut into segments of
+// at most SM_SEG sets (msm_g1.h).  A segment is a job of the G2 bucket MSM
+// over the real sets and one set = one job of the virtual batch that runs the
+// Miller loops, folds and final exponentiations (bgv_api.hip).
+enum : int32_t {
+  C_SEG_DEAD = 10,   // no set of the segment survived: nothing to pair, nothing to retry
+  C_SEG_RETRY = 11,  // sum r_i pk_i is the identity: the sets are decided on their own
+};
+struct sm_view {
+  uint32_t n_sets, n_segs, n_groups, n_raw, table_n;
+  const uint32_t* seg_off;    // [n_segs + 1]
+  const uint32_t* seg_group;  // [n_segs]
+  const uint32_t* pk_idx;     // [n_sets]
+  const g1a* raw_pks;
+  const g1a* table;
+  const uint64_t* scalars;
+  const int32_t* sig_code;    // k_sig outcome of every set
+  const uint32_t* sig_inf;
+  uint32_t* skip;             // [n_sets] 1: the set is left out of its segment's sums
+  int32_t* set_code;          // [n_sets] bgv_set_code of a rejected set
+  g1j* win;                   // [n_segs * 16] window sums
+  g1a* p_seg;                 // [n_segs] sum r_i pk_i, affine (the virtual batch's rpk_aff)
+  int32_t* seg_code;          // [n_segs] C_OK, C_SEG_DEAD or C_SEG_RETRY
+  const g2a* h_group;         // [n_groups] H(m_g)
+  g2a* h_seg;                 // [n_segs] the virtual batch's h_aff
+  int32_t* pk_code_v;         // [n_segs] the virtual batch's pk_code
+  int32_t* job_code_v;        // [n_segs] the virtual batch's job_code
+  const g2a* s_seg;           // [n_segs] sum r_i sigma_i (the per-job MSM over the real sets)
+  const uint32_t* s_inf;
+};
+// per-set retry of failing segments: set list[k] becomes set k = job k of an ordinary batch
+struct sm_retry {
+  uint32_t n;
+  const uint32_t* list;        // [n] set index
+  const uint32_t* list_group;  // [n] its group
+  const uint32_t* pk_idx;
+  const uint8_t* msgs;         // [n_groups][32]
+  const uint8_t* sigs;
+  const uint32_t* sig_len;
+  const uint64_t* scalars;
+  uint32_t* o_iota;            // [n + 1] job and pubkey offsets
+  uint32_t* o_idx;
+  uint8_t* o_msgs;
+  uint8_t* o_sigs;
+  uint32_t* o_len;
+  uint64_t* o_scalars;
+};
+void launch_sm_classify(hipStream_t st, const sm_view& v);
+void launch_sm_g1_sum(hipStream_t st, const sm_view& v);
+void launch_sm_apply(hipStream_t st, const sm_view& v);
+void launch_sm_group_sums(hipStream_t st, const sm_view& v, const uint32_t* group_seg, g1a* p_group, g2a* s_group);
+void launch_sm_retry_gather(hipStream_t st, const sm_retry& r);
+
 }  // namespace bgv

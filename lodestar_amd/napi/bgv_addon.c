@@ -20,6 +20,8 @@
  *                                                bgv_combine_final: ONE final exponentiation of the shards
  *   partialFinish(ctx) -> Promise<result>        bgv_partial_finish: localise the last partial()'s shard
  *                                                after a failed combined check
+ *   verifySameMessage(ctx, smBatch) -> Promise<smResult>, verifySameMessageSync(ctx, smBatch) -> smResult
+ *                                                bgv_verify_same_message (see "same-message batches" below)
  *
  * batch = {jobOffsets: Uint32Array, pkOffsets: Uint32Array, pkIndices:
  * Uint32Array, msgs: Uint8Array, sigs: Uint8Array (192 B per set), sigLen:
@@ -533,6 +535,207 @@ static napi_value VerifySync(napi_env env, napi_callback_info info) {
   return r;
 }
 
+/* ------------------------------------------------------- same-message batches
+ * verifySameMessage(ctx, batch) -> Promise<result>, verifySameMessageSync(ctx, batch) -> result
+ * (bgv_verify_same_message; IBlsVerifier.verifySignatureSetsSameMessage).
+ * batch = {groupOffsets: Uint32Array, pkIndices: Uint32Array (one per set), msgs: Uint8Array (32 B per GROUP),
+ * sigs: Uint8Array (192 B per set), sigLen: Uint32Array, rawPks?: Uint8Array}.
+ * result = {valid: Uint8Array (1 / 0 per set), codes: Int32Array (bgv_set_code of a rejected set), segments,
+ * hashes, pairs, groupsRetried, setsRetried, deviceMs, workerStartMs, workerEndMs}.  Ownership as for verify:
+ * the offsets are copied at call time and every length is checked against the copy. */
+enum { S_GRP, S_PKI, S_MSG, S_SIG, S_LEN, S_RAW, S_FIELDS };
+static const char* SM_FIELD[S_FIELDS] = {"groupOffsets", "pkIndices", "msgs", "sigs", "sigLen", "rawPks"};
+static const napi_typedarray_type SM_FIELD_T[S_FIELDS] = {napi_uint32_array, napi_uint32_array, napi_uint8_array,
+                                                          napi_uint8_array,  napi_uint32_array, napi_uint8_array};
+
+typedef struct {
+  addon_ctx* c;
+  bgv_sm_batch b;
+  uint32_t* group_off;
+  uint8_t* valid;
+  int32_t* codes;
+  bgv_sm_stats stats;
+  double t_start_ms, t_end_ms;
+  int status;
+  char err[512];
+  napi_ref refs[S_FIELDS];
+  napi_ref ctx_ref;
+  napi_async_work work;
+  napi_deferred deferred;
+} sm_job;
+
+static void sm_free(napi_env env, sm_job* j) {
+  for (int k = 0; k < S_FIELDS; k++)
+    if (j->refs[k]) napi_delete_reference(env, j->refs[k]);
+  if (j->ctx_ref) napi_delete_reference(env, j->ctx_ref);
+  free(j->group_off);
+  free(j->valid);
+  free(j->codes);
+}
+
+static int sm_read_batch(napi_env env, napi_value obj, sm_job* j, int pin) {
+  void* p[S_FIELDS] = {0};
+  size_t n[S_FIELDS] = {0};
+  napi_value v[S_FIELDS];
+  for (int k = 0; k < S_FIELDS; k++) {
+    bool has = false;
+    napi_has_named_property(env, obj, SM_FIELD[k], &has);
+    if (!has) {
+      if (k == S_RAW) continue;
+      napi_throw_type_error(env, NULL, "batch field missing");
+      return -1;
+    }
+    napi_get_named_property(env, obj, SM_FIELD[k], &v[k]);
+    if (typed(env, v[k], SM_FIELD_T[k], &p[k], &n[k])) {
+      napi_throw_type_error(env, NULL, "batch field has the wrong typed-array type");
+      return -1;
+    }
+  }
+  if (n[S_GRP] < 1) {
+    napi_throw_range_error(env, NULL, "groupOffsets needs at least one entry");
+    return -1;
+  }
+  memset(&j->b, 0, sizeof j->b);
+  j->b.n_groups = (uint32_t)(n[S_GRP] - 1);
+  j->group_off = (uint32_t*)malloc(4 * n[S_GRP]);
+  if (!j->group_off) {
+    napi_throw_error(env, NULL, "out of memory");
+    return -1;
+  }
+  memcpy(j->group_off, p[S_GRP], 4 * n[S_GRP]);
+  const uint32_t n_sets = j->group_off[j->b.n_groups];
+  j->b.n_sets = n_sets;
+  if (n[S_MSG] < 32ull * j->b.n_groups || n[S_SIG] < 192ull * n_sets || n[S_LEN] < n_sets || n[S_PKI] < n_sets) {
+    napi_throw_range_error(env, NULL, "msgs / sigs / sigLen / pkIndices shorter than the group or set count");
+    return -1;
+  }
+  j->valid = (uint8_t*)calloc(n_sets ? n_sets : 1, 1);
+  j->codes = (int32_t*)calloc(n_sets ? n_sets : 1, 4);
+  if (!j->valid || !j->codes) {
+    napi_throw_error(env, NULL, "out of memory");
+    return -1;
+  }
+  if (pin)
+    for (int k = 0; k < S_FIELDS; k++)
+      if (p[k] && k != S_GRP) napi_create_reference(env, v[k], 1, &j->refs[k]);
+  j->b.group_offsets = j->group_off;
+  j->b.pk_indices = (const uint32_t*)p[S_PKI];
+  j->b.msgs = (const uint8_t*)p[S_MSG];
+  j->b.sigs = (const uint8_t*)p[S_SIG];
+  j->b.sig_len = (const uint32_t*)p[S_LEN];
+  j->b.raw_pks = (const uint8_t*)p[S_RAW];
+  j->b.n_raw = (uint32_t)(n[S_RAW] / 96);
+  j->b.scalars = NULL; /* drawn inside the library */
+  j->b.on_device = 0;
+  return 0;
+}
+
+static void sm_run(sm_job* j) {
+  pthread_mutex_lock(&j->c->mu);
+  j->t_start_ms = now_ms();
+  if (j->c->closed) {
+    j->status = BGV_E_INVALID_ARG;
+    snprintf(j->err, sizeof j->err, "QUEUE_ERROR_QUEUE_ABORTED");
+  } else {
+    j->status = bgv_verify_same_message(j->c->ctx, &j->b, j->valid, j->codes, &j->stats);
+    if (j->status != BGV_OK) snprintf(j->err, sizeof j->err, "bgv error %d: %s", j->status, bgv_last_error());
+  }
+  j->t_end_ms = now_ms();
+  pthread_mutex_unlock(&j->c->mu);
+}
+
+static napi_value sm_result(napi_env env, const sm_job* j) {
+  napi_value o, v, ab;
+  void* dst = NULL;
+  if (napi_create_object(env, &o) != napi_ok) return NULL;
+  if (napi_create_arraybuffer(env, j->b.n_sets, &dst, &ab) != napi_ok) return NULL;
+  if (j->b.n_sets) memcpy(dst, j->valid, j->b.n_sets);
+  napi_create_typedarray(env, napi_uint8_array, j->b.n_sets, ab, 0, &v);
+  napi_set_named_property(env, o, "valid", v);
+  v = new_int32_array(env, j->codes, j->b.n_sets);
+  if (!v) return NULL;
+  napi_set_named_property(env, o, "codes", v);
+  const struct { const char* name; uint32_t val; } u[] = {
+      {"segments", j->stats.n_segments}, {"hashes", j->stats.hashes}, {"pairs", j->stats.pairs},
+      {"groupsRetried", j->stats.groups_retried}, {"setsRetried", j->stats.sets_retried}};
+  for (size_t k = 0; k < sizeof u / sizeof u[0]; k++) {
+    napi_create_uint32(env, u[k].val, &v);
+    napi_set_named_property(env, o, u[k].name, v);
+  }
+  napi_create_double(env, (double)j->stats.total_ms, &v);
+  napi_set_named_property(env, o, "deviceMs", v);
+  napi_create_double(env, j->t_start_ms, &v);
+  napi_set_named_property(env, o, "workerStartMs", v);
+  napi_create_double(env, j->t_end_ms, &v);
+  napi_set_named_property(env, o, "workerEndMs", v);
+  return o;
+}
+
+static void sm_exec(napi_env env, void* data) { /* libuv worker thread */
+  (void)env;
+  sm_run((sm_job*)data);
+}
+
+static void sm_done(napi_env env, napi_status st, void* data) { /* main thread */
+  sm_job* j = (sm_job*)data;
+  if (st != napi_ok && j->status == BGV_OK) {
+    j->status = BGV_E_INVALID_ARG;
+    snprintf(j->err, sizeof j->err, "async work cancelled");
+  }
+  if (j->status != BGV_OK) {
+    napi_value msg, err;
+    napi_create_string_utf8(env, j->err, NAPI_AUTO_LENGTH, &msg);
+    napi_create_error(env, NULL, msg, &err);
+    napi_reject_deferred(env, j->deferred, err);
+  } else {
+    napi_resolve_deferred(env, j->deferred, sm_result(env, j));
+  }
+  napi_delete_async_work(env, j->work);
+  sm_free(env, j);
+  free(j);
+}
+
+static napi_value VerifySameMessage(napi_env env, napi_callback_info info) {
+  size_t argc = 2;
+  napi_value a[2];
+  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, a, NULL, NULL));
+  addon_ctx* c = get_ctx(env, a[0]);
+  if (!c) return NULL;
+  sm_job* j = (sm_job*)calloc(1, sizeof *j);
+  j->c = c;
+  if (sm_read_batch(env, a[1], j, 1)) {
+    sm_free(env, j);
+    free(j);
+    return NULL;
+  }
+  napi_create_reference(env, a[0], 1, &j->ctx_ref); /* the context outlives its queued work */
+  napi_value promise, name;
+  NAPI_CALL(env, napi_create_promise(env, &j->deferred, &promise));
+  NAPI_CALL(env, napi_create_string_utf8(env, "bgv_verify_same_message", NAPI_AUTO_LENGTH, &name));
+  NAPI_CALL(env, napi_create_async_work(env, NULL, name, sm_exec, sm_done, j, &j->work));
+  NAPI_CALL(env, napi_queue_async_work(env, j->work));
+  return promise;
+}
+
+static napi_value VerifySameMessageSync(napi_env env, napi_callback_info info) {
+  size_t argc = 2;
+  napi_value a[2];
+  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, a, NULL, NULL));
+  addon_ctx* c = get_ctx(env, a[0]);
+  if (!c) return NULL;
+  sm_job j;
+  memset(&j, 0, sizeof j);
+  j.c = c;
+  napi_value r = NULL;
+  if (!sm_read_batch(env, a[1], &j, 0)) {
+    sm_run(&j);
+    if (j.status != BGV_OK) napi_throw_error(env, NULL, j.err);
+    else r = sm_result(env, &j);
+  }
+  sm_free(env, &j);
+  return r;
+}
+
 static napi_value Init(napi_env env, napi_value exports) {
   napi_property_descriptor d[] = {
       {"abiVersion", NULL, AbiVersion, NULL, NULL, NULL, napi_enumerable, NULL},
@@ -548,6 +751,8 @@ static napi_value Init(napi_env env, napi_value exports) {
       {"partial", NULL, Partial, NULL, NULL, NULL, napi_enumerable, NULL},
       {"partialFinish", NULL, PartialFinish, NULL, NULL, NULL, napi_enumerable, NULL},
       {"combineFinal", NULL, CombineFinal, NULL, NULL, NULL, napi_enumerable, NULL},
+      {"verifySameMessage", NULL, VerifySameMessage, NULL, NULL, NULL, napi_enumerable, NULL},
+      {"verifySameMessageSync", NULL, VerifySameMessageSync, NULL, NULL, NULL, napi_enumerable, NULL},
   };
   if (napi_define_properties(env, exports, sizeof d / sizeof d[0], d) != napi_ok) return NULL;
   return exports;

@@ -187,6 +187,71 @@ function encodeJobs(jobs) {
   return {jobOffsets, pkOffsets, pkIndices, msgs, sigs, sigLen, rawPks};
 }
 
+// the caller-side checks of one verifySignatureSetsSameMessage call, as checkSets makes them
+function checkSameMessage(sets, message) {
+  if (!message || message.length !== 32) throw Error("signingRoot must be 32 bytes");
+  for (const s of sets) {
+    if (!s || !s.publicKey) throw Error("EMPTY_AGGREGATE_ARRAY");
+    if (s.publicKey.raw && s.publicKey.raw.length !== 96) throw Error("raw pubkeys must be 96-byte uncompressed");
+  }
+}
+
+// calls [{sets, message}] -> the groups of ONE device call: one group per
+// call, calls whose messages are byte-equal share a group (first appearance
+// order).  where[k] = [start, end) of call k in the flattened sets.
+function mergeSameMessage(calls) {
+  const byMsg = new Map();
+  const order = [];
+  calls.forEach((c, k) => {
+    const key = Buffer.from(c.message).toString("hex");
+    if (!byMsg.has(key)) { byMsg.set(key, {message: c.message, calls: []}); order.push(key); }
+    byMsg.get(key).calls.push(k);
+  });
+  const groups = [];
+  const where = new Array(calls.length);
+  let pos = 0;
+  for (const key of order) {
+    const g = byMsg.get(key);
+    const sets = [];
+    for (const k of g.calls) {
+      where[k] = [pos, pos + calls[k].sets.length];
+      pos += calls[k].sets.length;
+      for (const s of calls[k].sets) sets.push(s);
+    }
+    groups.push({message: g.message, sets});
+  }
+  return {groups, where};
+}
+
+// groups [{message, sets: [{publicKey, signature}]}] -> the arrays of include/bgv.h bgv_sm_batch
+function encodeSameMessage(groups) {
+  let n = 0, nRaw = 0;
+  for (const g of groups) {
+    if (g.sets.length === 0) throw Error("Empty signature set");
+    n += g.sets.length;
+    for (const s of g.sets) if (s.publicKey.raw) nRaw++;
+  }
+  const groupOffsets = new Uint32Array(groups.length + 1);
+  const pkIndices = new Uint32Array(Math.max(n, 1));
+  const rawPks = new Uint8Array(Math.max(nRaw, 1) * 96);
+  const msgs = new Uint8Array(Math.max(groups.length, 1) * 32);
+  const sigs = new Uint8Array(Math.max(n, 1) * 192);
+  const sigLen = new Uint32Array(Math.max(n, 1));
+  let i = 0, r = 0;
+  groups.forEach((g, k) => {
+    msgs.set(g.message, 32 * k);
+    for (const s of g.sets) {
+      const pk = s.publicKey;
+      if (pk.raw) { pkIndices[i] = (RAW_BIT | r) >>> 0; rawPks.set(pk.raw, 96 * r++); } else pkIndices[i] = pk.index >>> 0;
+      sigLen[i] = s.signature.length;
+      if (s.signature.length === 96 || s.signature.length === 192) sigs.set(s.signature, 192 * i);
+      i++;
+    }
+    groupOffsets[k + 1] = i;
+  });
+  return {groupOffsets, pkIndices, msgs, sigs, sigLen, rawPks};
+}
+
 // device work of a job in Montgomery Fp products (lodestar_amd/dist.py
 // job_work, from tools/fpmul_counts.json): per set 13,790, per pubkey
 // reference 11 (one G1 mixed addition of the gather)
@@ -245,6 +310,9 @@ function newMetrics() {
     lodestar_bls_worker_thread_time_per_sigset_seconds: hist(),
     // verifyOnMainThread calls (mainThreadDurationInThreadPool, multithread/index.ts:156-167)
     lodestar_bls_thread_pool_main_thread_time_seconds: hist(),
+    // verifySignatureSetsSameMessage: sets sent to the device, and groups that went to the per-set retry
+    lodestar_bls_thread_pool_same_message_sig_sets_started_total: 0,
+    lodestar_bls_thread_pool_same_message_retries_total: 0,
   };
 }
 
@@ -328,6 +396,13 @@ class BlsGpuVerifier {
     this.metrics = newMetrics();
     this.runJob = this.runJob.bind(this);
     this.runBufferedJobs = this.runBufferedJobs.bind(this);
+    // verifySignatureSetsSameMessage: a queue and a buffer of their own
+    this.smJobs = [];
+    this.smBuffered = null;
+    this.smRunning = false;
+    this.smDeviceCalls = 0; // merged device calls issued (test hook)
+    this.runSameMessage = this.runSameMessage.bind(this);
+    this.flushSameMessage = this.flushSameMessage.bind(this);
   }
 
   // syncPubkeys / addPubkey (pubkeyCache.ts:56-77): 48-byte compressed keys, every replica
@@ -360,7 +435,74 @@ class BlsGpuVerifier {
   // not (gating on idle devices would stop the network processor,
   // network/processor/index.ts:406, for every 5-40 ms device batch)
   canAcceptWork() {
-    return !this.closed && this.jobs.length < MAX_JOBS_CAN_ACCEPT_WORK && this.queuedSets < this.maxSetsPerDeviceBatch;
+    const smJobs = this.smJobs.length + (this.smBuffered ? this.smBuffered.jobs.length : 0);
+    let smSets = this.smBuffered ? this.smBuffered.sigCount : 0;
+    for (const j of this.smJobs) smSets += j.sets.length;
+    return !this.closed && this.jobs.length + smJobs < MAX_JOBS_CAN_ACCEPT_WORK && this.queuedSets + smSets < this.maxSetsPerDeviceBatch;
+  }
+
+  // IBlsVerifier.verifySignatureSetsSameMessage (upstream Lodestar; the call
+  // site is gossip attestation validation, chain/validation/attestation.ts:271):
+  // sets = [{publicKey: {index} | {raw}, signature}] that all sign `message`;
+  // resolves one boolean per set.  Batchable calls wait in a buffer of their
+  // own under the pool's rule (100 ms, or more than 32 signatures waiting);
+  // whatever is queued goes out as ONE merged device call
+  // (bgv_verify_same_message) on one bulk context, one group per call, calls
+  // with byte-equal messages sharing a group.
+  async verifySignatureSetsSameMessage(sets, message, opts = {}) {
+    if (this.closed) throw new QueueError();
+    if (sets.length === 0) return [];
+    checkSameMessage(sets, message);
+    return new Promise((resolve, reject) => {
+      const job = {resolve, reject, sets, message, addedTimeMs: Date.now()};
+      if (opts.batchable) {
+        if (!this.smBuffered) this.smBuffered = {jobs: [], sigCount: 0, timeout: setTimeout(this.flushSameMessage, MAX_BUFFER_WAIT_MS)};
+        this.smBuffered.jobs.push(job);
+        this.smBuffered.sigCount += sets.length;
+        if (this.smBuffered.sigCount > MAX_BUFFERED_SIGS) {
+          clearTimeout(this.smBuffered.timeout);
+          this.flushSameMessage();
+        }
+      } else {
+        this.smJobs.push(job);
+        setTimeout(this.runSameMessage, 0);
+      }
+    });
+  }
+
+  flushSameMessage() {
+    if (this.smBuffered) {
+      this.smJobs.push(...this.smBuffered.jobs);
+      this.smBuffered = null;
+      setTimeout(this.runSameMessage, 0);
+    }
+  }
+
+  async runSameMessage() {
+    if (this.closed || this.smRunning || this.smJobs.length === 0) return;
+    this.smRunning = true;
+    const jobs = [];
+    let n = 0;
+    while (this.smJobs.length > 0 && (jobs.length === 0 || n + this.smJobs[0].sets.length <= this.maxSetsPerDeviceBatch)) {
+      const j = this.smJobs.shift();
+      jobs.push(j);
+      n += j.sets.length;
+    }
+    const m = this.metrics;
+    try {
+      const {groups, where} = mergeSameMessage(jobs);
+      const {best} = this.idleContexts();
+      this.smDeviceCalls++;
+      m.lodestar_bls_thread_pool_same_message_sig_sets_started_total += n;
+      const res = await addon.verifySameMessage(this.ctxs[best >= 0 ? best : 0], encodeSameMessage(groups));
+      m.lodestar_bls_thread_pool_same_message_retries_total += res.groupsRetried;
+      m.lodestar_bls_thread_pool_time_seconds_sum += (res.workerEndMs - res.workerStartMs) / 1000;
+      jobs.forEach((job, k) => job.resolve(Array.from(res.valid.subarray(where[k][0], where[k][1]), (v) => v === 1)));
+    } catch (e) {
+      for (const job of jobs) job.reject(e);
+    }
+    this.smRunning = false;
+    if (this.smJobs.length > 0) setTimeout(this.runSameMessage, 0);
   }
 
   async verifySignatureSets(sets, opts = {}) {
@@ -624,6 +766,13 @@ class BlsGpuVerifier {
     for (const job of this.jobs) job.reject(new QueueError());
     this.jobs = [];
     this.queuedSets = 0;
+    if (this.smBuffered) {
+      clearTimeout(this.smBuffered.timeout);
+      for (const job of this.smBuffered.jobs) job.reject(new QueueError());
+      this.smBuffered = null;
+    }
+    for (const job of this.smJobs) job.reject(new QueueError());
+    this.smJobs = [];
     for (const c of this.allContexts()) addon.close(c); // each waits for its batch in flight (the context mutex)
   }
 }
@@ -660,6 +809,15 @@ class BlsGpuSingleThreadVerifier {
     return o.value;
   }
 
+  // verifySignatureSetsSameMessage on the calling thread: one device call, one group
+  async verifySignatureSetsSameMessage(sets, message) {
+    if (this.closed) throw new QueueError();
+    if (sets.length === 0) return [];
+    checkSameMessage(sets, message);
+    const res = addon.verifySameMessageSync(this.ctx, encodeSameMessage([{message, sets}]));
+    return Array.from(res.valid, (v) => v === 1);
+  }
+
   async close() {
     if (this.closed) return;
     this.closed = true;
@@ -673,5 +831,6 @@ class BlsGpuSingleThreadVerifier {
 
 module.exports = {
   addon, BlsGpuVerifier, BlsGpuSingleThreadVerifier, QueueError, sourceHash, checkBuildId, chunkifyMaximizeChunkSize, encodeJobs, checkSets, shardJobs, jobWork,
+  encodeSameMessage, mergeSameMessage, checkSameMessage,
   MAX_BUFFERED_SIGS, MAX_BUFFER_WAIT_MS, MAX_JOBS_CAN_ACCEPT_WORK, SHARD_MIN_SETS, PRIORITY_CUS, RESERVED_CAP, CONTEXTS_PER_DEVICE,
 };

@@ -51,6 +51,7 @@ EXPORTS = [
     "bgv_pubkeys_set", "bgv_pubkeys_count", "bgv_pubkeys_get", "bgv_pubkeys_validate", "bgv_verify", "bgv_last_stats",
     "bgv_partial", "bgv_partial_finish", "bgv_combine_final", "bgv_debug_stages", "bgv_gen_keys", "bgv_gen_sign", "bgv_bench_fpmul",
     "bgv_bench_mad", "bgv_debug_fp_ops", "bgv_debug_g2_decode",
+    "bgv_verify_same_message", "bgv_sm_check", "bgv_debug_same_message",
 ]
 FP_OPS_N = 13
 
@@ -114,6 +115,33 @@ class BgvStats(ctypes.Structure):
     def layout(self) -> dict:
         """the pipeline variant the last batch ran with (prepare() in bgv_api.hip)"""
         return {k: int(getattr(self, k)) for k in self.LAYOUT}
+
+
+class BgvSmBatch(ctypes.Structure):
+    """bgv_sm_batch (include/bgv.h): single-pubkey sets grouped by message."""
+    _fields_ = [
+        ("n_sets", ctypes.c_uint32),
+        ("n_groups", ctypes.c_uint32),
+        ("group_offsets", ctypes.c_void_p),
+        ("pk_indices", ctypes.c_void_p),
+        ("raw_pks", ctypes.c_void_p),
+        ("n_raw", ctypes.c_uint32),
+        ("msgs", ctypes.c_void_p),
+        ("sigs", ctypes.c_void_p),
+        ("sig_len", ctypes.c_void_p),
+        ("scalars", ctypes.c_void_p),
+        ("on_device", ctypes.c_uint32),
+    ]
+
+
+class BgvSmStats(ctypes.Structure):
+    """bgv_sm_stats (include/bgv.h): counters that show which path ran."""
+    _fields_ = [(k, ctypes.c_uint32) for k in
+                ("n_sets", "n_groups", "n_segments", "hashes", "pairs", "groups_retried", "sets_retried")] + [
+        ("total_ms", ctypes.c_float)]
+
+    def as_dict(self) -> dict:
+        return {k: (float(getattr(self, k)) if k == "total_ms" else int(getattr(self, k))) for k, _ in self._fields_}
 
 
 class BgvCfg(ctypes.Structure):
@@ -236,6 +264,9 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
             "bgv_bench_mad": ([P, u32, u32, ctypes.POINTER(ctypes.c_float)], ctypes.c_int),
             "bgv_debug_fp_ops": ([P, P, u32, P], ctypes.c_int),
             "bgv_debug_g2_decode": ([P, P, P, u32, P, P], ctypes.c_int),
+            "bgv_verify_same_message": ([P, ctypes.POINTER(BgvSmBatch), P, P, ctypes.POINTER(BgvSmStats)], ctypes.c_int),
+            "bgv_sm_check": ([ctypes.POINTER(BgvSmBatch)], ctypes.c_int),
+            "bgv_debug_same_message": ([P, ctypes.POINTER(BgvSmBatch), P, P, ctypes.POINTER(BgvSmStats), P, P, P], ctypes.c_int),
         }
         for name, (args, res) in sig.items():
             fn = getattr(lib, name)
@@ -377,6 +408,52 @@ class Device:
         self._check(self.lib.bgv_verify(self.h, ctypes.byref(b), jr.ctypes.data,
                                         sc.ctypes.data if sc is not None else None, ctypes.byref(self.last_stats)))
         return jr[: b.n_jobs], (sc[: b.n_sets] if sc is not None else None)
+
+    @staticmethod
+    def make_sm_batch(arrays: dict, on_device: bool = False, sync_inputs: bool = True) -> BgvSmBatch:
+        """arrays as verifier.encode_same_message returns them"""
+        b = BgvSmBatch()
+        b.n_sets = int(arrays["n_sets"])
+        b.n_groups = int(arrays["n_groups"])
+        b.group_offsets = _ptr(arrays["group_offsets"])
+        b.pk_indices = _ptr(arrays["pk_indices"])
+        b.raw_pks = _ptr(arrays.get("raw_pks"))
+        b.n_raw = int(arrays.get("n_raw", 0))
+        b.msgs = _ptr(arrays["msgs"])
+        b.sigs = _ptr(arrays["sigs"])
+        b.sig_len = _ptr(arrays["sig_len"])
+        b.scalars = _ptr(arrays.get("scalars"))
+        b.on_device = 1 if on_device else 0
+        if on_device and sync_inputs:
+            _sync_producers(arrays)
+        return b
+
+    def verify_same_message(self, arrays: dict, on_device: bool = False, sync_inputs: bool = True):
+        """bgv_verify_same_message: (set_valid bool[n_sets], set_code int32[n_sets]);
+        the counters of the call are left in last_sm_stats"""
+        b = self.make_sm_batch(arrays, on_device, sync_inputs)
+        ok = np.zeros(max(b.n_sets, 1), dtype=np.uint8)
+        sc = np.zeros(max(b.n_sets, 1), dtype=np.int32)
+        self.last_sm_stats = BgvSmStats()
+        self._check(self.lib.bgv_verify_same_message(self.h, ctypes.byref(b), ok.ctypes.data, sc.ctypes.data,
+                                                     ctypes.byref(self.last_sm_stats)))
+        return ok[: b.n_sets].astype(bool), sc[: b.n_sets]
+
+    def debug_same_message(self, arrays: dict, on_device: bool = False) -> dict:
+        """bgv_debug_same_message (test only): the verdicts plus P_g, S_g and H(m_g) per group"""
+        b = self.make_sm_batch(arrays, on_device)
+        n, G = b.n_sets, b.n_groups
+        ok = np.zeros(max(n, 1), dtype=np.uint8)
+        sc = np.zeros(max(n, 1), dtype=np.int32)
+        pg = np.zeros((max(G, 1), 96), np.uint8)
+        sg = np.zeros((max(G, 1), 192), np.uint8)
+        hg = np.zeros((max(G, 1), 192), np.uint8)
+        self.last_sm_stats = BgvSmStats()
+        self._check(self.lib.bgv_debug_same_message(self.h, ctypes.byref(b), ok.ctypes.data, sc.ctypes.data,
+                                                    ctypes.byref(self.last_sm_stats), pg.ctypes.data, sg.ctypes.data,
+                                                    hg.ctypes.data))
+        return {"set_valid": ok[:n].astype(bool), "set_code": sc[:n], "p_group": pg[:G], "s_group": sg[:G],
+                "h_group": hg[:G], "stats": self.last_sm_stats.as_dict()}
 
     def partial(self, arrays: dict, on_device: bool = False, sync_inputs: bool = True):
         """bgv_partial: (miller576 bytes, set codes, provisional job results

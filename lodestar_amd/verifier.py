@@ -283,6 +283,210 @@ def check_sets(sets: list[ISignatureSet]) -> None:
             raise BlsError("signingRoot must be 32 bytes")
 
 
+# ------------------------------------------------- same-message batches
+def check_same_message(sets, message: bytes) -> None:
+    """Caller-side checks of one verifySignatureSetsSameMessage call, as
+    check_sets makes them: every set is (PublicKey, signature) with one key,
+    a raw key is a 96-byte uncompressed point, the signing root is 32 bytes."""
+    if len(message) != 32:
+        raise BlsError("signingRoot must be 32 bytes")
+    for pk, _sig in sets:
+        if pk is None:
+            raise BlsError("EMPTY_AGGREGATE_ARRAY")
+        if pk.index is None and len(pk.raw) != 96:
+            _decompress_raw48(pk.raw)
+        if pk.index is not None and not (0 <= pk.index < 0x80000000):
+            raise BlsError(f"pubkey index {pk.index} out of range")
+
+
+def encode_same_message(groups, scalars: np.ndarray | None = None) -> dict:
+    """Flatten groups [(message, [(PublicKey, signature), ...]), ...] into the
+    arrays of bgv_sm_batch (include/bgv.h): one message per group, one key and
+    one signature per set.  An empty group is refused (the library would)."""
+    n = sum(len(g[1]) for g in groups)
+    G = len(groups)
+    off = [0]
+    idx: list[int] = []
+    raw: list[bytes] = []
+    raw_pos: dict[bytes, int] = {}
+    msgs = np.zeros((max(G, 1), 32), dtype=np.uint8)
+    sigs = np.zeros((max(n, 1), 192), dtype=np.uint8)
+    sig_len = np.zeros(max(n, 1), dtype=np.uint32)
+    i = 0
+    for g, (message, sets) in enumerate(groups):
+        if len(sets) == 0:
+            raise BlsError("Empty signature set", 10)
+        if len(message) != 32:
+            raise BlsError("signingRoot must be 32 bytes")
+        msgs[g] = np.frombuffer(bytes(message), dtype=np.uint8)
+        for pk, sig in sets:
+            if pk.index is not None:
+                idx.append(pk.index)
+            else:
+                r = pk.raw if len(pk.raw) == 96 else _decompress_raw48(pk.raw)
+                if r not in raw_pos:
+                    raw_pos[r] = len(raw)
+                    raw.append(r)
+                idx.append(0x80000000 | raw_pos[r])
+            sl = len(sig)
+            sig_len[i] = sl
+            if sl in (96, 192):
+                sigs[i, :sl] = np.frombuffer(bytes(sig), dtype=np.uint8)
+            i += 1
+        off.append(i)
+    return {
+        "n_sets": n,
+        "n_groups": G,
+        "group_offsets": np.array(off, dtype=np.uint32),
+        "pk_indices": np.array(idx if idx else [0], dtype=np.uint32),
+        "raw_pks": np.frombuffer(b"".join(raw), dtype=np.uint8).copy() if raw else None,
+        "n_raw": len(raw),
+        "msgs": msgs,
+        "sigs": sigs,
+        "sig_len": sig_len,
+        "scalars": scalars,
+    }
+
+
+def merge_same_message(calls):
+    """Merge calls [(sets, message), ...] into the groups of ONE device call:
+    one group per call, and calls whose messages are byte-equal share a group
+    (in order of first appearance).  Returns (groups, where) with where[k] the
+    slice of the flattened sets that belongs to call k."""
+    order: list[bytes] = []
+    members: dict[bytes, list[int]] = {}
+    for k, (_sets, message) in enumerate(calls):
+        m = bytes(message)
+        if m not in members:
+            members[m] = []
+            order.append(m)
+        members[m].append(k)
+    groups = []
+    where: list = [None] * len(calls)
+    pos = 0
+    for m in order:
+        sets = []
+        for k in members[m]:
+            where[k] = slice(pos, pos + len(calls[k][0]))
+            pos += len(calls[k][0])
+            sets.extend(calls[k][0])
+        groups.append((m, sets))
+    return groups, where
+
+
+def run_same_message_calls(device, calls, scalars_for=None, metrics: dict | None = None) -> list:
+    """One device call (Device.verify_same_message) for the merged calls;
+    returns list[bool] per call."""
+    groups, where = merge_same_message(calls)
+    n = sum(len(g[1]) for g in groups)
+    arrays = encode_same_message(groups, scalars_for(n) if scalars_for else None)
+    ok, _codes = device.verify_same_message(arrays)
+    if metrics is not None:
+        st = getattr(device, "last_sm_stats", None)
+        metrics["same_message_sets_started"] = metrics.get("same_message_sets_started", 0) + n
+        metrics["same_message_retries"] = metrics.get("same_message_retries", 0) + (int(st.groups_retried) if st is not None else 0)
+    ok = [bool(x) for x in ok]
+    return [ok[w] for w in where]
+
+
+@dataclass
+class _SmJob:
+    sets: list
+    message: bytes
+    future: asyncio.Future
+    added: float
+
+
+class SameMessageQueue:
+    """The queue of verifySignatureSetsSameMessage calls: batchable calls are
+    buffered under the pool's rule (MAX_BUFFER_WAIT_MS, or more than
+    MAX_BUFFERED_SIGS signatures waiting, multithread/index.ts:48-57) in a
+    queue of their own; whatever is queued when the device side is free goes
+    out as ONE merged device call (merge_same_message).  run_merged(calls) ->
+    list[list[bool]] runs on `executor` (None: the loop's default)."""
+
+    def __init__(self, run_merged, executor=None, max_sets: int = MAX_SETS_PER_DEVICE_BATCH):
+        self._run_merged = run_merged
+        self._executor = executor
+        self._max_sets = max_sets
+        self._jobs: list[_SmJob] = []
+        self._buffered: list[_SmJob] = []
+        self._buffered_sigs = 0
+        self._handle = None
+        self._running = False
+        self._closed = False
+        self.device_calls = 0
+
+    def pending_jobs(self) -> int:
+        return len(self._jobs) + len(self._buffered)
+
+    def pending_sets(self) -> int:
+        return sum(len(j.sets) for j in self._jobs + self._buffered)
+
+    async def submit(self, sets, message: bytes, batchable: bool) -> list:
+        if self._closed:
+            raise QueueError(QueueErrorCode.QUEUE_ABORTED)
+        loop = asyncio.get_running_loop()
+        job = _SmJob(list(sets), bytes(message), loop.create_future(), time.monotonic())
+        if batchable:
+            if not self._buffered:
+                self._handle = loop.call_later(MAX_BUFFER_WAIT_MS / 1000, self._flush)
+            self._buffered.append(job)
+            self._buffered_sigs += len(job.sets)
+            if self._buffered_sigs > MAX_BUFFERED_SIGS:
+                self._handle.cancel()
+                self._flush()
+        else:
+            self._jobs.append(job)
+            loop.call_soon(self._schedule)
+        return await job.future
+
+    def _flush(self):
+        self._jobs.extend(self._buffered)
+        self._buffered = []
+        self._buffered_sigs = 0
+        self._handle = None
+        asyncio.get_running_loop().call_soon(self._schedule)
+
+    def _schedule(self):
+        if self._closed or self._running or not self._jobs:
+            return
+        take, n = [], 0
+        while self._jobs and (n == 0 or n + len(self._jobs[0].sets) <= self._max_sets):
+            j = self._jobs.pop(0)
+            take.append(j)
+            n += len(j.sets)
+        self._running = True
+        asyncio.ensure_future(self._run(take))
+
+    async def _run(self, jobs: list):
+        loop = asyncio.get_running_loop()
+        try:
+            self.device_calls += 1
+            res = await loop.run_in_executor(self._executor, self._run_merged, [(j.sets, j.message) for j in jobs])
+            for j, r in zip(jobs, res):
+                if not j.future.done():
+                    j.future.set_result(r)
+        except Exception as e:  # noqa: BLE001 -- a device error rejects the merged calls
+            for j in jobs:
+                if not j.future.done():
+                    j.future.set_exception(e)
+        finally:
+            self._running = False
+            loop.call_soon(self._schedule)
+
+    def abort(self):
+        self._closed = True
+        if self._handle is not None:
+            self._handle.cancel()
+            self._handle = None
+        for j in self._jobs + self._buffered:
+            if not j.future.done():
+                j.future.set_exception(QueueError(QueueErrorCode.QUEUE_ABORTED))
+        self._jobs.clear()
+        self._buffered.clear()
+
+
 # ----------------------------------------------------------------- verifier
 @dataclass
 class _Job:
@@ -356,6 +560,7 @@ class BlsGpuVerifier:
         self._busy = 0
         self._exec = ThreadPoolExecutor(max_workers=len(self.devices) + 1)  # + the main-thread path
         self._dev_locks = [threading.Lock() for _ in self.devices]
+        self._sm = SameMessageQueue(self._run_same_message, self._exec, max_sets_per_device_batch)
 
     # -- IBlsVerifier ---------------------------------------------------
     def can_accept_work(self) -> bool:
@@ -365,8 +570,24 @@ class BlsGpuVerifier:
         sets, whether or not a batch is in flight (a GPU wants large batches;
         gating on idle devices would stall the network processor for every
         batch, network/processor/index.ts:406)."""
-        return (not self._closed and len(self._jobs) < MAX_JOBS_CAN_ACCEPT_WORK
-                and sum(len(j.sets) for j in self._jobs) < self._max_batch)
+        return (not self._closed and len(self._jobs) + self._sm.pending_jobs() < MAX_JOBS_CAN_ACCEPT_WORK
+                and sum(len(j.sets) for j in self._jobs) + self._sm.pending_sets() < self._max_batch)
+
+    async def verify_signature_sets_same_message(self, sets, message: bytes, opts: VerifySignatureOpts | None = None) -> list:
+        """IBlsVerifier.verifySignatureSetsSameMessage (upstream Lodestar; the
+        call site is gossip attestation validation, chain/validation/
+        attestation.ts:271): `sets` is a list of (PublicKey, signature) that
+        all sign `message`; one boolean per set.  Batchable calls wait in a
+        buffer of their own and are merged into one device call
+        (bgv_verify_same_message) on one bulk context, one group per call."""
+        opts = opts or VerifySignatureOpts()
+        sets = list(sets)
+        if not sets:
+            return []
+        check_same_message(sets, message)
+        if self._closed:
+            raise QueueError(QueueErrorCode.QUEUE_ABORTED)
+        return await self._sm.submit(sets, message, opts.batchable)
 
     async def verify_signature_sets(self, sets: list[ISignatureSet], opts: VerifySignatureOpts | None = None) -> bool:
         opts = opts or VerifySignatureOpts()
@@ -399,6 +620,7 @@ class BlsGpuVerifier:
                 j.future.set_exception(QueueError(QueueErrorCode.QUEUE_ABORTED))
         self._jobs.clear()
         self._buffered.clear()
+        self._sm.abort()
         self._exec.shutdown(wait=True)
         for d in self._contexts():
             d.close()
@@ -566,6 +788,16 @@ class BlsGpuVerifier:
             self.metrics["main_thread_calls"] += 1
         return self._verdict(int(jr[0]))
 
+    def _run_same_message(self, calls) -> list:
+        """the merged same-message calls on one bulk context (no sharding)"""
+        idle = [k for k, f in enumerate(self._idle) if f]
+        d = idle[0] if idle else 0
+        with self._dev_locks[d]:
+            t0 = time.perf_counter()
+            out = run_same_message_calls(self.devices[d], calls, self._scalars if self._rng is not None else None, self.metrics)
+            self.metrics["device_time_s"] = self.metrics.get("device_time_s", 0.0) + time.perf_counter() - t0
+        return out
+
     def _run_device_batch(self, jobs: list[list[ISignatureSet]], devs: list[int] | None = None) -> list:
         """Verify a list of jobs on the devices `devs` (default: all); returns
         per job True / False / BlsError.  One device: bgv_verify.  Several: the
@@ -697,6 +929,16 @@ class BlsGpuSingleThreadVerifier:
         self.metrics["main_thread_calls"] += 1
         return r
 
+    async def verify_signature_sets_same_message(self, sets, message: bytes, opts: VerifySignatureOpts | None = None) -> list:
+        """verifySignatureSetsSameMessage in the calling thread: one device call, one group"""
+        if self._closed:
+            raise QueueError(QueueErrorCode.QUEUE_ABORTED)
+        sets = list(sets)
+        if not sets:
+            return []
+        check_same_message(sets, message)
+        return run_same_message_calls(self.device, [(sets, message)], None, self.metrics)[0]
+
     def can_accept_work(self) -> bool:
         return True
 
@@ -768,4 +1010,6 @@ def _new_metrics() -> dict:
         "batch_sigs_success": 0,
         "device_time_s": 0.0,
         "job_wait_time_s": [],
+        "same_message_sets_started": 0,
+        "same_message_retries": 0,
     }

@@ -317,6 +317,73 @@ int bgv_sm_check(const bgv_sm_batch* batch);
 int bgv_debug_same_message(bgv_ctx* ctx, const bgv_sm_batch* batch, uint8_t* set_valid, int32_t* set_code,
                            bgv_sm_stats* stats, uint8_t* p_group96, uint8_t* s_group192, uint8_t* h_group192);
 
+/* ---- same-message batches of aggregate sets --------------------------------
+ * The same identity holds when a set's key is an aggregate:
+ *   prod_i e(PK_i, H(m))^{r_i} = e(sum_i r_i PK_i, H(m)),  PK_i = sum_j pk_ij.
+ * Gossip beacon_aggregate_and_proof objects (chain/validation/
+ * aggregateAndProof.ts:164-179: about 16 aggregates per committee and slot
+ * sign one AttestationData root) and the attestations of a block
+ * (state-transition signatureSets/indexedAttestation.ts:40-47: several
+ * aggregates of one committee and data) are such sets.  A group pays its
+ * per-set key aggregation, which bgv_verify pays too, plus one hash and two
+ * Miller pairs per segment.  Additive to ABI 4.
+ *
+ * Set i owns keys pk_indices[pk_offsets[i] .. pk_offsets[i+1]) (table rows,
+ * or rows of raw_pks with bit 31 set), as in bgv_batch; everything else is
+ * bgv_sm_batch.  Host batches are staged and checked on the pinned copy:
+ * pk_offsets monotone and spanning [0, total], group offsets as for
+ * bgv_sm_batch, scalars non-zero; a set without keys fails the call with
+ * BGV_E_EMPTY_SET, as bgv_verify does.  On-device batches are trusted;
+ * offsets that run backwards there still cause no out-of-bounds access.
+ *
+ * Semantics are bgv_verify_same_message's (per-set verdicts, rejection before
+ * aggregation, 64-set segments, whole-batch check, per-segment final
+ * exponentiation, per-set retry inside the call, an identity P of a segment
+ * goes to the retry), with the key codes of an aggregate:
+ *  - any index past the table (or past n_raw): BGV_SET_INDEX_RANGE;
+ *  - PK_i is the identity (all rows the identity, or a key beside its
+ *    negation): BGV_SET_PK_IS_INFINITY;
+ *  - identity rows inside a finite aggregate add nothing;
+ *  - signature codes take precedence over key codes; an identity signature
+ *    reports BGV_SET_VERIFY_FAIL.
+ * A batch whose pk_offsets is 0, 1, 2, ... gives the verdicts, codes and group
+ * sums of bgv_verify_same_message on the same arrays.  The retry verifies a
+ * set against its aggregated key PK_i, as a one-set job of the ordinary
+ * pipeline with PK_i as a raw key.
+ * When it pays: the call is a longer chain of kernels
+ * than bgv_verify's latency mode, so one slot's ~1,000 aggregates are faster
+ * as one-set jobs of bgv_verify; a batch that fills the device (tens of
+ * thousands of sets) is several times faster here.                            */
+typedef struct bgv_sma_batch {
+  uint32_t n_sets;               /* aggregate sets */
+  uint32_t n_groups;             /* distinct messages */
+  const uint32_t* group_offsets; /* [n_groups + 1] */
+  const uint32_t* pk_offsets;    /* [n_sets + 1] */
+  const uint32_t* pk_indices;    /* [pk_offsets[n_sets]]; bit 31 selects raw_pks */
+  const uint8_t* raw_pks;        /* [n_raw][96], may be NULL */
+  uint32_t n_raw;
+  const uint8_t* msgs;           /* [n_groups][32] */
+  const uint8_t* sigs;           /* [n_sets][192] */
+  const uint32_t* sig_len;       /* [n_sets] */
+  const uint64_t* scalars;       /* [n_sets] non-zero, or NULL = drawn on the device */
+  uint32_t on_device;
+} bgv_sma_batch;
+
+/* Outputs as bgv_verify_same_message; bgv_sm_stats is reused (callers count the
+ * aggregated keys from pk_offsets). */
+int bgv_verify_same_message_agg(bgv_ctx* ctx, const bgv_sma_batch* batch, uint8_t* set_valid, int32_t* set_code,
+                                bgv_sm_stats* stats);
+/* The host-side contract check on its own (no device, no context): BGV_OK,
+ * BGV_E_INVALID_ARG or BGV_E_EMPTY_SET with bgv_last_error().  Offsets and
+ * scalars of an on-device batch are not read. */
+int bgv_sma_check(const bgv_sma_batch* batch);
+/* test-only: bgv_verify_same_message_agg plus, per SET, PK_i before weighting
+ * (96 B affine, all-zero when the set's key was rejected) and the per-group
+ * outputs of bgv_debug_same_message.  Any output pointer may be NULL. */
+int bgv_debug_same_message_agg(bgv_ctx* ctx, const bgv_sma_batch* batch, uint8_t* set_valid, int32_t* set_code,
+                               bgv_sm_stats* stats, uint8_t* pk_set96, uint8_t* p_group96, uint8_t* s_group192,
+                               uint8_t* h_group192);
+
 /* Multi-GPU partials: run the batch up to, but excluding, the
  * final exponentiation and return this shard's Miller product (576 B, 12
  * Fp coefficients of w^0..w^5, c0||c1 each, 48-byte big-endian) with the

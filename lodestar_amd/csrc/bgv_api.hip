@@ -134,6 +134,10 @@ struct bgv_ctx {
   dbuf<g2a> sm_hg, sm_sg;
   dbuf<g1a> sm_pg;
   dbuf<uint8_t> sm_retry;
+  // bgv_verify_same_message_agg
+  dbuf<g1j> sma_pk;           // per set: PK_i, Jacobian
+  dbuf<int32_t> sma_pk_code;  // per set: its key code
+  dbuf<g1a> sma_aff;          // PK_i affine: the retry's sets, or every set for the debug entry
   // microbench scratch
   dbuf<fp_t> mb_fp;
   dbuf<uint64_t> mb_u64;
@@ -316,6 +320,7 @@ int bgv_close(bgv_ctx* c) {
   c->set_job.release(); c->s_inf.release(); c->item_off.release(); c->item_job.release(); c->s_aff.release();
   c->sm_skip.release(); c->sm_list.release(); c->sm_zero.release(); c->sm_seg_code.release(); c->sm_win.release();
   c->sm_hg.release(); c->sm_sg.release(); c->sm_pg.release(); c->sm_retry.release();
+  c->sma_pk.release(); c->sma_pk_code.release(); c->sma_aff.release();
   c->mb_fp.release(); c->mb_u64.release();
   (void)hipStreamDestroy(c->st);
   (void)hipStreamDestroy(c->st_hash);
@@ -1258,6 +1263,329 @@ int bgv_verify_same_message(bgv_ctx* c, const bgv_sm_batch* b, uint8_t* set_vali
 int bgv_debug_same_message(bgv_ctx* c, const bgv_sm_batch* b, uint8_t* set_valid, int32_t* set_code, bgv_sm_stats* stats,
                            uint8_t* p_group96, uint8_t* s_group192, uint8_t* h_group192) {
   return sm_run(c, b, set_valid, set_code, stats, p_group96, s_group192, h_group192);
+}
+
+// ---- same-message batches of aggregate sets ----------------------------------
+// bgv_verify_same_message_agg: sm_run with a set's key an aggregate.  Layout:
+//   st_pk   : chunk set-up -> gather (k_pk_chunk) -> per-set fold (k_sma_set_sum)
+//             beside the signature decode, then [classify] the weighted sum
+//             over the folded keys (k_sma_g1_digit / k_sm_g1_fold)
+//   st      : sig decode + subgroup -> [set sums] classify -> G2 sums ->
+//             [pk, hash] apply -> the (-G1, S_seg) pairs -> [set pairs] folds
+//             and final exponentiations of the virtual batch, as in sm_run
+//   st_hash : one hash per group, then [apply] the (P_seg, H(m)) pairs beside
+//             the (-G1, S_seg) ones
+// The retry takes the surviving sets of failing segments with PK_i as a raw key.
+
+static int sma_check_args(const bgv_sma_batch* b) {
+  if (!b) return fail(BGV_E_INVALID_ARG, "batch is NULL");
+  if (b->n_sets == 0 && b->n_groups == 0) return BGV_OK;
+  if (b->n_groups > b->n_sets) return fail(BGV_E_INVALID_ARG, "n_groups %u > n_sets %u (a group is never empty)", b->n_groups, b->n_sets);
+  if (b->n_groups == 0) return fail(BGV_E_INVALID_ARG, "n_sets %u without a group", b->n_sets);
+  if (!b->group_offsets || !b->pk_offsets || !b->pk_indices || !b->msgs || !b->sigs || !b->sig_len)
+    return fail(BGV_E_INVALID_ARG, "missing batch array");
+  if (b->n_raw && !b->raw_pks) return fail(BGV_E_INVALID_ARG, "n_raw > 0 but raw_pks is NULL");
+  return BGV_OK;
+}
+
+// `go`: the copy of the group offsets the segments are cut from
+static int sma_check_groups(const bgv_sma_batch* b, const uint32_t* go) {
+  const uint32_t n = b->n_sets, G = b->n_groups;
+  if (go[0] != 0 || go[G] != n) return fail(BGV_E_INVALID_ARG, "group_offsets must span [0, n_sets]");
+  for (uint32_t g = 0; g < G; g++) {
+    if (go[g + 1] < go[g]) return fail(BGV_E_INVALID_ARG, "group_offsets not monotone");
+    if (go[g + 1] == go[g]) return fail(BGV_E_INVALID_ARG, "group %u is empty", g);
+  }
+  return BGV_OK;
+}
+
+// `po`: the copy of the key offsets the device will see; total: the length of pk_indices that is staged
+static int sma_check_keys(const bgv_sma_batch* b, const uint32_t* po, uint32_t total) {
+  const uint32_t n = b->n_sets;
+  if (po[0] != 0 || po[n] != total) return fail(BGV_E_INVALID_ARG, "pk_offsets must span [0, total]");
+  for (uint32_t i = 0; i < n; i++)
+    if (po[i + 1] < po[i]) return fail(BGV_E_INVALID_ARG, "pk_offsets not monotone");
+  for (uint32_t i = 0; i < n; i++)
+    if (po[i + 1] == po[i]) return fail(BGV_E_EMPTY_SET, "EMPTY_AGGREGATE_ARRAY (set %u)", i);
+  return BGV_OK;
+}
+
+int bgv_sma_check(const bgv_sma_batch* b) {
+  if (int r = sma_check_args(b)) return r;
+  if (b->on_device || b->n_sets == 0) return BGV_OK;
+  if (int r = sma_check_groups(b, b->group_offsets)) return r;
+  if (int r = sma_check_keys(b, b->pk_offsets, b->pk_offsets[b->n_sets])) return r;
+  if (b->scalars)
+    for (uint32_t i = 0; i < b->n_sets; i++)
+      if (!b->scalars[i]) return fail(BGV_E_INVALID_ARG, "scalars[%u] is zero", i);
+  return BGV_OK;
+}
+
+static int sma_run(bgv_ctx* c, const bgv_sma_batch* b, uint8_t* set_valid, int32_t* set_code, bgv_sm_stats* stats,
+                   uint8_t* pk_set96, uint8_t* p_group96, uint8_t* s_group192, uint8_t* h_group192) {
+  if (!c) return fail(BGV_E_INVALID_ARG, "null ctx");
+  if (int r = sma_check_args(b)) return r;
+  if (stats) memset(stats, 0, sizeof *stats);
+  const uint32_t n = b->n_sets, G = b->n_groups;
+  if (n == 0) return BGV_OK;
+  if (!set_valid) return fail(BGV_E_INVALID_ARG, "set_valid is NULL");
+  c->partial_pending = false;
+  HIPCHK(hipSetDevice(c->device));
+  active_guard ag(c->device);
+  const auto t0 = std::chrono::steady_clock::now();
+  // the group offsets and the key total come to the host first: the segments
+  // and the gather's grid bound are cut from these copies
+  std::vector<uint32_t> go((size_t)G + 1);
+  uint32_t total = 0;
+  if (b->on_device) {
+    HIPCHK(hipMemcpyAsync(go.data(), b->group_offsets, go.size() * 4, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(hipMemcpyAsync(&total, b->pk_offsets + n, 4, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(hipStreamSynchronize(c->st));
+  } else {
+    memcpy(go.data(), b->group_offsets, go.size() * 4);
+    total = b->pk_offsets[n];  // sizes the pk_indices copy; re-checked on the pinned copy
+  }
+  if (int r = sma_check_groups(b, go.data())) return r;
+  const bool host = !b->on_device;
+
+  // staging: the segment tables always, the batch arrays of a host batch
+  const uint32_t *d_seg_off = nullptr, *d_seg_group = nullptr, *d_group_seg = nullptr, *d_iota = nullptr;
+  const uint32_t *d_po = b->pk_offsets, *d_idx = b->pk_indices, *d_len = b->sig_len;
+  const uint8_t *d_msgs = b->msgs, *d_sigs = b->sigs, *d_raw = b->raw_pks;
+  const uint64_t* d_scalars = b->scalars;
+  std::vector<uint32_t> seg_off, seg_group, group_seg((size_t)G + 1);
+  seg_off.reserve(n / SM_SEG + G + 1);
+  for (uint32_t g = 0; g < G; g++) {
+    group_seg[g] = (uint32_t)seg_off.size();
+    for (uint32_t i = go[g]; i < go[g + 1]; i += SM_SEG) { seg_off.push_back(i); seg_group.push_back(g); }
+  }
+  const uint32_t S = (uint32_t)seg_off.size();
+  group_seg[G] = S;
+  seg_off.push_back(n);
+  std::vector<uint32_t> iota((size_t)S + 1);
+  for (uint32_t s = 0; s <= S; s++) iota[s] = s;
+  stage_seg segs[11] = {
+      {seg_off.data(), ((size_t)S + 1) * 4, (const void**)&d_seg_off, 0},
+      {seg_group.data(), (size_t)S * 4, (const void**)&d_seg_group, 0},
+      {group_seg.data(), ((size_t)G + 1) * 4, (const void**)&d_group_seg, 0},
+      {iota.data(), ((size_t)S + 1) * 4, (const void**)&d_iota, 0},
+      {b->pk_offsets, ((size_t)n + 1) * 4, (const void**)&d_po, 0},
+      {b->pk_indices, (size_t)total * 4, (const void**)&d_idx, 0},
+      {b->msgs, (size_t)G * 32, (const void**)&d_msgs, 0},
+      {b->raw_pks, (size_t)b->n_raw * 96, (const void**)&d_raw, 0},
+      {b->scalars, b->scalars ? (size_t)n * 8 : 0, (const void**)&d_scalars, 0},
+      {b->sigs, (size_t)n * 192, (const void**)&d_sigs, 0},
+      {b->sig_len, (size_t)n * 4, (const void**)&d_len, 0},
+  };
+  size_t bytes = 0;
+  if (int r = stage_pack(c, segs, host ? 11 : 4, bytes)) return r;
+  if (host) {  // the contract, on the pinned copy the device will see
+    const uint32_t* po = (const uint32_t*)(c->pin_in + segs[4].off);
+    if (int r = sma_check_keys(b, po, total)) return r;
+    if (b->scalars) {
+      const uint64_t* sc = (const uint64_t*)(c->pin_in + segs[8].off);
+      for (uint32_t i = 0; i < n; i++)
+        if (!sc[i]) return fail(BGV_E_INVALID_ARG, "scalars[%u] is zero", i);
+    }
+  }
+  if (int r = stage_issue(c, bytes)) return r;
+  if (!b->scalars) {
+    uint32_t kn[11];
+    random_bytes(kn, sizeof kn);
+    if (int r = ensure_or_release_lines(c, c->scalars, n)) return r;
+    launch_gen_scalars(c->st, kn, kn + 8, c->scalars.p, n);
+    HIPCHK(hipGetLastError());
+    d_scalars = c->scalars.p;
+  }
+  if (int r = ensure_or_release_lines(c, c->raw_conv, b->n_raw ? b->n_raw : 1)) return r;
+  launch_raw_pks(c->st, d_raw, c->raw_conv.p, b->n_raw);
+
+  // view A: the real sets, one job per segment (gather, signature decode, G2 sums)
+  dev_batch dA;
+  memset(&dA, 0, sizeof dA);
+  dA.n_sets = n; dA.n_jobs = S; dA.n_raw = b->n_raw; dA.table_n = c->table_n; dA.table = c->table;
+  dA.span_log2 = 6; dA.job_lanes = 36; dA.pairs_per_item = 1; dA.msm = 4; dA.clear_lanes = 9;
+  dA.chunk_bound = total / PK_CHUNK + n;  // as prepare() sets it: sum ceil(k_i / 32) <= total / 32 + n
+  dA.defer_from = n;
+  dA.job_off = d_seg_off; dA.pk_off = d_po; dA.pk_idx = d_idx; dA.raw_pks = c->raw_conv.p;
+  dA.sigs = d_sigs; dA.sig_len = d_len; dA.scalars = d_scalars;
+  dev_work w;
+  if (int r = work_alloc(c, dA, w)) return r;
+  int r = 0;
+  if ((r = c->sm_skip.ensure(n)) || (r = c->sm_zero.ensure(n)) || (r = c->sm_seg_code.ensure(S)) ||
+      (r = c->sm_win.ensure((size_t)S * 16)) || (r = c->sm_hg.ensure(G)) || (r = c->q_part.ensure(2 * (size_t)G)) ||
+      (r = c->sma_pk.ensure(n)) || (r = c->sma_pk_code.ensure(n)))
+    return r;
+  HIPCHK(hipMemsetAsync(c->sm_zero.p, 0, (size_t)n * 4, c->st));
+  sm_view v;
+  memset(&v, 0, sizeof v);
+  v.n_sets = n; v.n_segs = S; v.n_groups = G; v.n_raw = b->n_raw; v.table_n = c->table_n;
+  v.seg_off = d_seg_off; v.seg_group = d_seg_group; v.pk_idx = d_idx; v.raw_pks = c->raw_conv.p; v.table = c->table;
+  v.scalars = d_scalars; v.sig_code = w.sig_code; v.sig_inf = w.sig_inf; v.skip = c->sm_skip.p; v.set_code = w.set_code;
+  v.win = c->sm_win.p; v.p_seg = w.rpk_aff; v.seg_code = c->sm_seg_code.p; v.h_group = c->sm_hg.p; v.h_seg = w.h_aff;
+  v.pk_code_v = w.pk_code; v.job_code_v = w.job_code; v.s_seg = w.s_aff; v.s_inf = w.s_inf;
+  v.pk_set = c->sma_pk.p; v.pk_set_code = c->sma_pk_code.p;
+
+  HIPCHK(hipEventRecord(c->ev_fork, c->st));
+  HIPCHK(hipStreamWaitEvent(c->st_hash, c->ev_fork, 0));
+  HIPCHK(hipStreamWaitEvent(c->st_pk, c->ev_fork, 0));
+  {  // one hash per group on the hash stream (latency-mode kernels: two lanes per map)
+    dev_batch dH;
+    memset(&dH, 0, sizeof dH);
+    dH.n_sets = G; dH.n_jobs = G; dH.split = 1; dH.msgs = d_msgs;
+    dH.clear_lanes = G < 9000 ? 9u : (G < 16500 ? 3u : 1u);
+    dev_work wH;
+    memset(&wH, 0, sizeof wH);
+    wH.q_part = c->q_part.p;
+    wH.h_aff = c->sm_hg.p;
+    launch_stage(c->st_hash, ST_HASH, dH, wH);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(c->ev_dep[ST_HASH], c->st_hash));
+  }
+  {  // the keys of every set on the pubkey stream, beside the signature decode
+    dev_batch dP = dA;
+    dP.miller_coop = 36;  // launch_prep: the chunk set-up only, no Miller work items
+    launch_prep(c->st_pk, dP, w);
+    launch_stage(c->st_pk, ST_PK, dP, w);
+    launch_sma_set_sum(c->st_pk, dP, w, c->sma_pk.p, c->sma_pk_code.p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(c->ev_dep[ST_PK], c->st_pk));
+  }
+  launch_stage(c->st, ST_SIG, dA, w);
+  HIPCHK(hipStreamWaitEvent(c->st, c->ev_dep[ST_PK], 0));
+  launch_sma_classify(c->st, v);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(c->ev_sigdec, c->st));
+  HIPCHK(hipStreamWaitEvent(c->st_pk, c->ev_sigdec, 0));
+  launch_sma_g1_sum(c->st_pk, v);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(c->ev_dep[ST_PK_SCALE], c->st_pk));
+  {
+    // the per-job MSM sums what `skip` leaves in and rejects nothing (sm_run)
+    dev_work wz = w;
+    wz.sig_code = c->sm_zero.p;
+    wz.pk_code = c->sm_zero.p;
+    wz.sig_inf = c->sm_skip.p;
+    launch_stage(c->st, ST_SIG_SCALE, dA, wz);
+    launch_stage(c->st, ST_S_TREE, dA, wz);
+    HIPCHK(hipGetLastError());
+  }
+  HIPCHK(hipStreamWaitEvent(c->st, c->ev_dep[ST_PK_SCALE], 0));
+  HIPCHK(hipStreamWaitEvent(c->st, c->ev_dep[ST_HASH], 0));
+  launch_sm_apply(c->st, v);
+  // view B: the virtual batch, segment s = set s = job s
+  dev_batch dB;
+  memset(&dB, 0, sizeof dB);
+  dB.n_sets = S; dB.n_jobs = S; dB.pairs_per_item = 1; dB.job_lanes = 36;
+  dB.miller_coop = S < 2000 ? 36u : (S < 6000 ? 18u : 6u);
+  dB.job_off = d_iota;
+  // the (P_seg, H(m)) pairs on the hash stream beside the (-G1, S_seg) pairs, as
+  // run_stages places them: a few thousand lanes each, one after the other they
+  // would both be on the critical path
+  HIPCHK(hipEventRecord(c->ev_prep, c->st));
+  HIPCHK(hipStreamWaitEvent(c->st_hash, c->ev_prep, 0));
+  launch_stage(c->st_hash, ST_MILLER, dB, w);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(c->ev_dep[ST_MILLER], c->st_hash));
+  launch_stage(c->st, ST_MILLER_JOBS, dB, w);
+  HIPCHK(hipStreamWaitEvent(c->st, c->ev_dep[ST_MILLER], 0));
+  for (int s = ST_F_TREE; s <= ST_JOB_FINAL; s++) launch_stage(c->st, s, dB, w);
+  HIPCHK(hipGetLastError());
+
+  // first-pass results
+  const size_t o_jr = 256, o_sc = o_jr + (((size_t)S * 4 + 255) & ~size_t(255)), o_sk = o_sc + (((size_t)n * 4 + 255) & ~size_t(255));
+  if ((r = pinned_reserve(c->pin_out, c->pin_out_cap, o_sk + (size_t)n * 4))) return r;
+  HIPCHK(hipMemcpyAsync(c->pin_out, w.flags, 4, hipMemcpyDeviceToHost, c->st));
+  HIPCHK(hipMemcpyAsync(c->pin_out + o_jr, w.job_result, (size_t)S * 4, hipMemcpyDeviceToHost, c->st));
+  HIPCHK(hipMemcpyAsync(c->pin_out + o_sc, w.set_code, (size_t)n * 4, hipMemcpyDeviceToHost, c->st));
+  HIPCHK(hipMemcpyAsync(c->pin_out + o_sk, c->sm_skip.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->st));
+  if (pk_set96 || p_group96 || s_group192 || h_group192) {
+    const size_t o_set = (size_t)G * 480;
+    if ((r = c->sm_pg.ensure(G)) || (r = c->sm_sg.ensure(G)) || (r = c->sma_aff.ensure(n)) ||
+        (r = c->dbg_out.ensure(o_set + (size_t)n * 96)))
+      return r;
+    launch_sm_group_sums(c->st, v, d_group_seg, c->sm_pg.p, c->sm_sg.p);
+    launch_sma_pk_aff(c->st, c->sma_pk.p, c->sma_aff.p, n);
+    uint8_t* o = c->dbg_out.p;
+    launch_export_g1a(c->st, c->sm_pg.p, o, G);
+    launch_export_g2a(c->st, c->sm_sg.p, o + (size_t)G * 96, G);
+    launch_export_g2a(c->st, c->sm_hg.p, o + (size_t)G * 288, G);
+    launch_export_g1a(c->st, c->sma_aff.p, o + o_set, n);
+    HIPCHK(hipGetLastError());
+    if (p_group96) HIPCHK(hipMemcpyAsync(p_group96, o, (size_t)G * 96, hipMemcpyDeviceToHost, c->st));
+    if (s_group192) HIPCHK(hipMemcpyAsync(s_group192, o + (size_t)G * 96, (size_t)G * 192, hipMemcpyDeviceToHost, c->st));
+    if (h_group192) HIPCHK(hipMemcpyAsync(h_group192, o + (size_t)G * 288, (size_t)G * 192, hipMemcpyDeviceToHost, c->st));
+    if (pk_set96) HIPCHK(hipMemcpyAsync(pk_set96, o + o_set, (size_t)n * 96, hipMemcpyDeviceToHost, c->st));
+  }
+  HIPCHK(hipStreamSynchronize(c->st));
+  c->staged_pending = false;
+  const int32_t* jr = (const int32_t*)(c->pin_out + o_jr);
+  const int32_t* sc = (const int32_t*)(c->pin_out + o_sc);
+  const uint32_t* sk = (const uint32_t*)(c->pin_out + o_sk);
+  std::vector<uint32_t> list, list_group;
+  uint32_t pairs = 0, groups_retried = 0, last_group = 0xffffffffu;
+  for (uint32_t s = 0; s < S; s++) {
+    const bool ok = jr[s] == 1, retry = jr[s] == 0 || jr[s] == -C_SEG_RETRY;
+    if (jr[s] >= 0) pairs += 2;
+    if (retry && seg_group[s] != last_group) { groups_retried++; last_group = seg_group[s]; }
+    for (uint32_t i = seg_off[s]; i < seg_off[s + 1]; i++) {
+      set_valid[i] = (!sk[i] && ok) ? 1 : 0;
+      if (set_code) set_code[i] = sc[i];
+      if (retry && !sk[i]) { list.push_back(i); list_group.push_back(seg_group[s]); }
+    }
+  }
+  const uint32_t nr = (uint32_t)list.size();
+  if (nr) {
+    // the rare path: the surviving sets of the failing segments, each on its
+    // own against its aggregated key, which enters as row k of a raw-key table
+    const size_t a = 256;
+    auto up = [&](size_t x) { return (x + a - 1) & ~(a - 1); };
+    const size_t o_iota = 0, o_idx = up(((size_t)nr + 1) * 4), o_len = o_idx + up((size_t)nr * 4), o_scal = o_len + up((size_t)nr * 4),
+                 o_msg = o_scal + up((size_t)nr * 8), o_sig = o_msg + up((size_t)nr * 32), o_pk = o_sig + up((size_t)nr * 192),
+                 total_r = o_pk + up((size_t)nr * 96);
+    if ((r = c->sm_retry.ensure(total_r)) || (r = c->sm_list.ensure(2 * (size_t)nr)) || (r = c->sma_aff.ensure(nr))) return r;
+    HIPCHK(hipMemcpyAsync(c->sm_list.p, list.data(), (size_t)nr * 4, hipMemcpyHostToDevice, c->st));
+    HIPCHK(hipMemcpyAsync(c->sm_list.p + nr, list_group.data(), (size_t)nr * 4, hipMemcpyHostToDevice, c->st));
+    uint8_t* base = c->sm_retry.p;
+    sm_retry q;
+    q.n = nr; q.list = c->sm_list.p; q.list_group = c->sm_list.p + nr;
+    q.pk_idx = nullptr; q.msgs = d_msgs; q.sigs = d_sigs; q.sig_len = d_len; q.scalars = d_scalars;
+    q.o_iota = (uint32_t*)(base + o_iota); q.o_idx = (uint32_t*)(base + o_idx); q.o_len = (uint32_t*)(base + o_len);
+    q.o_scalars = (uint64_t*)(base + o_scal); q.o_msgs = base + o_msg; q.o_sigs = base + o_sig;
+    launch_sma_retry_gather(c->st, q, c->sma_pk.p, c->sma_aff.p);
+    launch_export_g1a(c->st, c->sma_aff.p, base + o_pk, nr);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(c->st));  // prepare() starts the hash maps on another stream
+    bgv_batch bb;
+    memset(&bb, 0, sizeof bb);
+    bb.n_sets = nr; bb.n_jobs = nr; bb.job_offsets = q.o_iota; bb.pk_offsets = q.o_iota; bb.pk_indices = q.o_idx;
+    bb.raw_pks = base + o_pk; bb.n_raw = nr; bb.msgs = q.o_msgs; bb.sigs = q.o_sigs; bb.sig_len = q.o_len;
+    bb.scalars = q.o_scalars; bb.on_device = 1;
+    dev_batch d2;
+    if ((r = prepare(c, &bb, d2, true))) return r;
+    dev_work w2;
+    if ((r = work_alloc(c, d2, w2))) return r;
+    if ((r = run_stages(c, d2, w2, 0, ST_COUNT))) return r;
+    std::vector<int32_t> jr2(nr);
+    if ((r = finish_results(c, d2, w2, jr2.data(), nullptr, nullptr))) return r;
+    for (uint32_t k = 0; k < nr; k++) set_valid[list[k]] = jr2[k] == 1 ? 1 : 0;
+  }
+  if (stats) {
+    stats->n_sets = n; stats->n_groups = G; stats->n_segments = S;
+    stats->hashes = G; stats->pairs = pairs;
+    stats->groups_retried = groups_retried; stats->sets_retried = nr;
+    stats->total_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  }
+  return BGV_OK;
+}
+
+int bgv_verify_same_message_agg(bgv_ctx* c, const bgv_sma_batch* b, uint8_t* set_valid, int32_t* set_code, bgv_sm_stats* stats) {
+  return sma_run(c, b, set_valid, set_code, stats, nullptr, nullptr, nullptr, nullptr);
+}
+
+int bgv_debug_same_message_agg(bgv_ctx* c, const bgv_sma_batch* b, uint8_t* set_valid, int32_t* set_code, bgv_sm_stats* stats,
+                               uint8_t* pk_set96, uint8_t* p_group96, uint8_t* s_group192, uint8_t* h_group192) {
+  return sma_run(c, b, set_valid, set_code, stats, pk_set96, p_group96, s_group192, h_group192);
 }
 
 // ---- multi-GPU partials ---------------------------------------------------

@@ -186,6 +186,9 @@ struct sm_view {
   int32_t* job_code_v;        // [n_segs] the virtual batch's job_code
   const g2a* s_seg;           // [n_segs] sum r_i sigma_i (the per-job MSM over the real sets)
   const uint32_t* s_inf;
+  // aggregate sets (bgv_verify_same_message_agg; NULL otherwise)
+  const g1j* pk_set;           // [n_sets] PK_i = sum_j pk_ij, Jacobian; the identity for a rejected key
+  const int32_t* pk_set_code;  // [n_sets] key code of k_sma_set_sum
 };
 // per-set retry of failing segments: set list[k] becomes set k = job k of an ordinary batch
 struct sm_retry {
@@ -209,5 +212,13 @@ void launch_sm_g1_sum(hipStream_t st, const sm_view& v);
 void launch_sm_apply(hipStream_t st, const sm_view& v);
 void launch_sm_group_sums(hipStream_t st, const sm_view& v, const uint32_t* group_seg, g1a* p_group, g2a* s_group);
 void launch_sm_retry_gather(hipStream_t st, const sm_retry& r);
+// aggregate sets: the per-set fold of the gather's chunk sums (b, w: the real
+// sets as a dev_batch view, after launch_prep and launch_pk_gather), then the
+// stages above over pk_set instead of table rows
+void launch_sma_set_sum(hipStream_t st, const dev_batch& b, const dev_work& w, g1j* pk_set, int32_t* pk_set_code);
+void launch_sma_classify(hipStream_t st, const sm_view& v);
+void launch_sma_g1_sum(hipStream_t st, const sm_view& v);
+void launch_sma_pk_aff(hipStream_t st, const g1j* pk_set, g1a* out, uint32_t n);
+void launch_sma_retry_gather(hipStream_t st, const sm_retry& r, const g1j* pk_set, g1a* o_pk);
 
 }  // namespace bgv

@@ -172,6 +172,109 @@ __global__ void BGV_SM_LB k_sm_retry_gather(sm_retry r) {
   for (uint32_t k = 0; k < 192; k++) r.o_sigs[192u * t + k] = r.sigs[192u * i + k];
 }
 
+// ---- aggregate sets (bgv_verify_same_message_agg) ---------------------------
+// A set's key is PK_i = sum_j pk_{i,j}.  The balanced gather of the ordinary
+// pipeline (k_chunk_count / k_scan / k_chunk_set / k_pk_chunk) leaves one
+// partial sum per PK_CHUNK keys; the kernels below fold them per set and run
+// the weighted sum over the folded keys.
+
+// lane = set: the fold of k_pk without its scalar multiplication and without
+// its inversion.  PK_i stays Jacobian; the key code is k_pk's: the range marker
+// (0, 1, 1) of a chunk (or offsets that run backwards) is C_INDEX_RANGE, the
+// identity C_PK_IS_INFINITY.  A rejected set's PK_i is stored as the identity.
+__global__ void BGV_SM_LB k_sma_set_sum(dev_batch b, dev_work w, g1j* pk_set, int32_t* pk_set_code) {
+  const uint32_t i = sm_gtid();
+  if (i >= b.n_sets) return;
+  g1j acc;
+  jac_set_inf(acc);
+  const uint32_t c0 = w.chunk_off[i], c1 = w.chunk_off[i + 1];
+  bool range_err = c1 > b.chunk_bound || b.pk_off[i + 1] < b.pk_off[i];
+  for (uint32_t c = c0; c < c1 && !range_err; c++) {
+    const g1j p = w.pk_part[c];
+    if (!jac_is_inf(p) && fp_is_zero(p.x)) range_err = true;
+    else jac_add(acc, acc, p);
+  }
+  int32_t code = C_OK;
+  if (range_err) code = C_INDEX_RANGE;
+  else if (jac_is_inf(acc)) code = C_PK_IS_INFINITY;
+  if (code != C_OK) jac_set_inf(acc);
+  pk_set[i] = acc;
+  pk_set_code[i] = code;
+}
+
+// k_sm_classify for aggregate keys: signature code first, then the key code of
+// k_sma_set_sum, then the identity signature
+__global__ void BGV_SM_LB k_sma_classify(sm_view v) {
+  const uint32_t i = sm_gtid();
+  if (i >= v.n_sets) return;
+  int32_t code = v.sig_code[i];
+  if (code == C_OK) code = v.pk_set_code[i];
+  if (code == C_OK && v.sig_inf[i]) code = C_VERIFY_FAIL;
+  v.set_code[i] = code;
+  v.skip[i] = code != C_OK ? 1u : 0u;
+}
+
+// k_sm_g1_digit over the per-set keys: the addend is PK_i in Jacobian form,
+// read from pk_set, and the bucket addition the full one (msm_g1.h
+// msm_g1_bucket_add_jac).  Scaling and the 16-lane fold are k_sm_g1_digit's;
+// k_sm_g1_fold finishes the segment.
+__global__ void BGV_SM_LB k_sma_g1_digit(sm_view v) {
+  const uint32_t t = sm_gtid();
+  const uint32_t s = t >> 8, win = (t >> 4) & 15u, d = t & 15u;
+  if (s >= v.n_segs) return;  // whole waves: 256 lanes per segment
+  const uint32_t beg = v.seg_off[s], end = v.seg_off[s + 1];
+  g1j acc;
+  jac_set_inf(acc);
+  uint32_t i = beg;
+  for (;;) {
+    while (i < end) {
+      if (d != 0 && !v.skip[i] && msm_g1_digit(v.scalars[i], win) == d) break;
+      i++;
+    }
+    if (!__any(i < end)) break;
+    if (i < end) {
+      const g1j pk = v.pk_set[i];  // finite: k_sma_classify skipped the others
+      msm_g1_bucket_add_jac(acc, pk);
+      i++;
+    }
+  }
+  msm_g1_scale_digit(acc, d);
+  for (uint32_t st = 8; st >= 1; st >>= 1) {
+    g1j o;
+    shfl_down16(o, acc, st);
+    if (d < st) jac_add(acc, acc, o);
+  }
+  if (d == 0) v.win[16u * s + win] = acc;
+}
+
+// PK_i as an affine point (all-zero for a rejected key): bgv_debug_same_message_agg
+__global__ void BGV_SM_LB k_sma_pk_aff(const g1j* pk_set, g1a* out, uint32_t n) {
+  const uint32_t i = sm_gtid();
+  if (i >= n) return;
+  g1a a;
+  jac_to_aff(a, pk_set[i]);
+  out[i] = a;
+}
+
+// the per-set retry's batch, as k_sm_retry_gather builds it, with the set's
+// aggregated key as row t of a raw-key table: o_pk[t] = PK_i affine, and the
+// job's single index is 0x80000000 | t
+__global__ void BGV_SM_LB k_sma_retry_gather(sm_retry r, const g1j* pk_set, g1a* o_pk) {
+  const uint32_t t = sm_gtid();
+  if (t > r.n) return;
+  r.o_iota[t] = t;
+  if (t == r.n) return;
+  const uint32_t i = r.list[t], g = r.list_group[t];
+  g1a a;
+  jac_to_aff(a, pk_set[i]);
+  o_pk[t] = a;
+  r.o_idx[t] = 0x80000000u | t;
+  r.o_len[t] = r.sig_len[i];
+  r.o_scalars[t] = r.scalars[i];
+  for (uint32_t k = 0; k < 32; k++) r.o_msgs[32u * t + k] = r.msgs[32u * g + k];
+  for (uint32_t k = 0; k < 192; k++) r.o_sigs[192u * t + k] = r.sigs[192u * i + k];
+}
+
 static inline dim3 sm_grid(uint32_t n) { return dim3((n + 63u) / 64u); }
 
 void launch_sm_classify(hipStream_t st, const sm_view& v) {
@@ -194,6 +297,28 @@ void launch_sm_group_sums(hipStream_t st, const sm_view& v, const uint32_t* grou
 
 void launch_sm_retry_gather(hipStream_t st, const sm_retry& r) {
   hipLaunchKernelGGL(k_sm_retry_gather, sm_grid(r.n + 1u), dim3(64), 0, st, r);
+}
+
+void launch_sma_set_sum(hipStream_t st, const dev_batch& b, const dev_work& w, g1j* pk_set, int32_t* pk_set_code) {
+  if (b.n_sets) hipLaunchKernelGGL(k_sma_set_sum, sm_grid(b.n_sets), dim3(64), 0, st, b, w, pk_set, pk_set_code);
+}
+
+void launch_sma_classify(hipStream_t st, const sm_view& v) {
+  if (v.n_sets) hipLaunchKernelGGL(k_sma_classify, sm_grid(v.n_sets), dim3(64), 0, st, v);
+}
+
+void launch_sma_g1_sum(hipStream_t st, const sm_view& v) {
+  if (!v.n_segs) return;
+  hipLaunchKernelGGL(k_sma_g1_digit, dim3(v.n_segs * 4u), dim3(64), 0, st, v);
+  hipLaunchKernelGGL(k_sm_g1_fold, sm_grid(v.n_segs * 16u), dim3(64), 0, st, v);
+}
+
+void launch_sma_pk_aff(hipStream_t st, const g1j* pk_set, g1a* out, uint32_t n) {
+  if (n) hipLaunchKernelGGL(k_sma_pk_aff, sm_grid(n), dim3(64), 0, st, pk_set, out, n);
+}
+
+void launch_sma_retry_gather(hipStream_t st, const sm_retry& r, const g1j* pk_set, g1a* o_pk) {
+  hipLaunchKernelGGL(k_sma_retry_gather, sm_grid(r.n + 1u), dim3(64), 0, st, r, pk_set, o_pk);
 }
 
 }  // namespace bgv

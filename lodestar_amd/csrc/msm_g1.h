@@ -81,4 +81,46 @@ BGV_HD bool msm_g1_segment(g1a& out, const g1a* rows, const uint64_t* scalars, c
   return jac_to_aff(out, total);
 }
 
+// ---- aggregate sets (bgv_verify_same_message_agg) ---------------------------
+// A set's key is PK_i = sum_j pk_{i,j}, left in Jacobian form by the per-set
+// fold of the gather's chunk sums (k_sma_set_sum): no inversion per set.  The
+// bucket addition is then add-2007-bl (16 Fp products); curve.h jac_add takes
+// the exceptional cases by cross-multiplying, so two representations of one
+// point double and a point beside its negation empties the bucket.
+
+// bucket += pk (pk is not the identity)
+BGV_HD void msm_g1_bucket_add_jac(g1j& bucket, const g1j& pk) { jac_add(bucket, bucket, pk); }
+
+// bucket (win, d) of pks[0, n): entries flagged in `skip` (may be NULL) and
+// identity entries add nothing
+BGV_HD void msm_g1_bucket_jac(g1j& acc, const g1j* pks, const uint64_t* scalars, const uint32_t* skip, uint32_t n,
+                              uint32_t win, uint32_t d) {
+  jac_set_inf(acc);
+  if (d == 0) return;
+  for (uint32_t i = 0; i < n; i++) {
+    if ((skip && skip[i]) || msm_g1_digit(scalars[i], win) != d) continue;
+    if (jac_is_inf(pks[i])) continue;
+    msm_g1_bucket_add_jac(acc, pks[i]);
+  }
+}
+
+// msm_g1_segment over Jacobian entries
+BGV_HD bool msm_g1_segment_jac(g1a& out, const g1j* pks, const uint64_t* scalars, const uint32_t* skip, uint32_t n) {
+  g1j total;
+  jac_set_inf(total);
+  for (uint32_t win = 0; win < MSM_G1_WINDOWS; win++) {
+    g1j sw;
+    jac_set_inf(sw);
+    for (uint32_t d = 1; d < 16; d++) {
+      g1j b;
+      msm_g1_bucket_jac(b, pks, scalars, skip, n, win, d);
+      msm_g1_scale_digit(b, d);
+      jac_add(sw, sw, b);
+    }
+    msm_g1_shift(sw, win);
+    jac_add(total, total, sw);
+  }
+  return jac_to_aff(out, total);
+}
+
 }  // namespace bgv

@@ -22,6 +22,8 @@
  *                                                after a failed combined check
  *   verifySameMessage(ctx, smBatch) -> Promise<smResult>, verifySameMessageSync(ctx, smBatch) -> smResult
  *                                                bgv_verify_same_message (see "same-message batches" below)
+ *   verifySameMessageAgg(ctx, smaBatch) -> Promise<smResult>, verifySameMessageAggSync(ctx, smaBatch) -> smResult
+ *                                                bgv_verify_same_message_agg: the sets' keys are aggregates
  *
  * batch = {jobOffsets: Uint32Array, pkOffsets: Uint32Array, pkIndices:
  * Uint32Array, msgs: Uint8Array, sigs: Uint8Array (192 B per set), sigLen:
@@ -542,15 +544,21 @@ static napi_value VerifySync(napi_env env, napi_callback_info info) {
  * sigs: Uint8Array (192 B per set), sigLen: Uint32Array, rawPks?: Uint8Array}.
  * result = {valid: Uint8Array (1 / 0 per set), codes: Int32Array (bgv_set_code of a rejected set), segments,
  * hashes, pairs, groupsRetried, setsRetried, deviceMs, workerStartMs, workerEndMs}.  Ownership as for verify:
- * the offsets are copied at call time and every length is checked against the copy. */
-enum { S_GRP, S_PKI, S_MSG, S_SIG, S_LEN, S_RAW, S_FIELDS };
-static const char* SM_FIELD[S_FIELDS] = {"groupOffsets", "pkIndices", "msgs", "sigs", "sigLen", "rawPks"};
-static const napi_typedarray_type SM_FIELD_T[S_FIELDS] = {napi_uint32_array, napi_uint32_array, napi_uint8_array,
-                                                          napi_uint8_array,  napi_uint32_array, napi_uint8_array};
+ * the offsets are copied at call time and every length is checked against the copy.
+ *
+ * verifySameMessageAgg / verifySameMessageAggSync (bgv_verify_same_message_agg): the same, with
+ * pkOffsets: Uint32Array (n_sets + 1 entries, copied too) and pkIndices holding pkOffsets[n_sets] keys. */
+enum { S_GRP, S_PKI, S_MSG, S_SIG, S_LEN, S_RAW, S_PKO, S_FIELDS };
+static const char* SM_FIELD[S_FIELDS] = {"groupOffsets", "pkIndices", "msgs", "sigs", "sigLen", "rawPks", "pkOffsets"};
+static const napi_typedarray_type SM_FIELD_T[S_FIELDS] = {napi_uint32_array, napi_uint32_array, napi_uint8_array, napi_uint8_array,
+                                                          napi_uint32_array, napi_uint8_array,  napi_uint32_array};
 
 typedef struct {
   addon_ctx* c;
   bgv_sm_batch b;
+  int agg;          /* the sets' keys are aggregates: `ba` is the batch, `b` keeps the counts */
+  bgv_sma_batch ba;
+  uint32_t* pk_off;
   uint32_t* group_off;
   uint8_t* valid;
   int32_t* codes;
@@ -569,6 +577,7 @@ static void sm_free(napi_env env, sm_job* j) {
     if (j->refs[k]) napi_delete_reference(env, j->refs[k]);
   if (j->ctx_ref) napi_delete_reference(env, j->ctx_ref);
   free(j->group_off);
+  free(j->pk_off);
   free(j->valid);
   free(j->codes);
 }
@@ -579,6 +588,7 @@ static int sm_read_batch(napi_env env, napi_value obj, sm_job* j, int pin) {
   napi_value v[S_FIELDS];
   for (int k = 0; k < S_FIELDS; k++) {
     bool has = false;
+    if (k == S_PKO && !j->agg) continue;
     napi_has_named_property(env, obj, SM_FIELD[k], &has);
     if (!has) {
       if (k == S_RAW) continue;
@@ -605,8 +615,22 @@ static int sm_read_batch(napi_env env, napi_value obj, sm_job* j, int pin) {
   memcpy(j->group_off, p[S_GRP], 4 * n[S_GRP]);
   const uint32_t n_sets = j->group_off[j->b.n_groups];
   j->b.n_sets = n_sets;
-  if (n[S_MSG] < 32ull * j->b.n_groups || n[S_SIG] < 192ull * n_sets || n[S_LEN] < n_sets || n[S_PKI] < n_sets) {
-    napi_throw_range_error(env, NULL, "msgs / sigs / sigLen / pkIndices shorter than the group or set count");
+  size_t n_keys = n_sets;
+  if (j->agg) {
+    if (n[S_PKO] < (size_t)n_sets + 1) {
+      napi_throw_range_error(env, NULL, "pkOffsets shorter than the set count + 1");
+      return -1;
+    }
+    j->pk_off = (uint32_t*)malloc(4 * ((size_t)n_sets + 1));
+    if (!j->pk_off) {
+      napi_throw_error(env, NULL, "out of memory");
+      return -1;
+    }
+    memcpy(j->pk_off, p[S_PKO], 4 * ((size_t)n_sets + 1));
+    n_keys = j->pk_off[n_sets];
+  }
+  if (n[S_MSG] < 32ull * j->b.n_groups || n[S_SIG] < 192ull * n_sets || n[S_LEN] < n_sets || n[S_PKI] < n_keys) {
+    napi_throw_range_error(env, NULL, "msgs / sigs / sigLen / pkIndices shorter than the group, set or key count");
     return -1;
   }
   j->valid = (uint8_t*)calloc(n_sets ? n_sets : 1, 1);
@@ -617,7 +641,7 @@ static int sm_read_batch(napi_env env, napi_value obj, sm_job* j, int pin) {
   }
   if (pin)
     for (int k = 0; k < S_FIELDS; k++)
-      if (p[k] && k != S_GRP) napi_create_reference(env, v[k], 1, &j->refs[k]);
+      if (p[k] && k != S_GRP && k != S_PKO) napi_create_reference(env, v[k], 1, &j->refs[k]);
   j->b.group_offsets = j->group_off;
   j->b.pk_indices = (const uint32_t*)p[S_PKI];
   j->b.msgs = (const uint8_t*)p[S_MSG];
@@ -627,6 +651,19 @@ static int sm_read_batch(napi_env env, napi_value obj, sm_job* j, int pin) {
   j->b.n_raw = (uint32_t)(n[S_RAW] / 96);
   j->b.scalars = NULL; /* drawn inside the library */
   j->b.on_device = 0;
+  if (j->agg) {
+    memset(&j->ba, 0, sizeof j->ba);
+    j->ba.n_sets = n_sets;
+    j->ba.n_groups = j->b.n_groups;
+    j->ba.group_offsets = j->group_off;
+    j->ba.pk_offsets = j->pk_off;
+    j->ba.pk_indices = j->b.pk_indices;
+    j->ba.raw_pks = j->b.raw_pks;
+    j->ba.n_raw = j->b.n_raw;
+    j->ba.msgs = j->b.msgs;
+    j->ba.sigs = j->b.sigs;
+    j->ba.sig_len = j->b.sig_len;
+  }
   return 0;
 }
 
@@ -637,7 +674,8 @@ static void sm_run(sm_job* j) {
     j->status = BGV_E_INVALID_ARG;
     snprintf(j->err, sizeof j->err, "QUEUE_ERROR_QUEUE_ABORTED");
   } else {
-    j->status = bgv_verify_same_message(j->c->ctx, &j->b, j->valid, j->codes, &j->stats);
+    j->status = j->agg ? bgv_verify_same_message_agg(j->c->ctx, &j->ba, j->valid, j->codes, &j->stats)
+                       : bgv_verify_same_message(j->c->ctx, &j->b, j->valid, j->codes, &j->stats);
     if (j->status != BGV_OK) snprintf(j->err, sizeof j->err, "bgv error %d: %s", j->status, bgv_last_error());
   }
   j->t_end_ms = now_ms();
@@ -695,7 +733,7 @@ static void sm_done(napi_env env, napi_status st, void* data) { /* main thread *
   free(j);
 }
 
-static napi_value VerifySameMessage(napi_env env, napi_callback_info info) {
+static napi_value sm_async(napi_env env, napi_callback_info info, int agg) {
   size_t argc = 2;
   napi_value a[2];
   NAPI_CALL(env, napi_get_cb_info(env, info, &argc, a, NULL, NULL));
@@ -703,6 +741,7 @@ static napi_value VerifySameMessage(napi_env env, napi_callback_info info) {
   if (!c) return NULL;
   sm_job* j = (sm_job*)calloc(1, sizeof *j);
   j->c = c;
+  j->agg = agg;
   if (sm_read_batch(env, a[1], j, 1)) {
     sm_free(env, j);
     free(j);
@@ -711,13 +750,14 @@ static napi_value VerifySameMessage(napi_env env, napi_callback_info info) {
   napi_create_reference(env, a[0], 1, &j->ctx_ref); /* the context outlives its queued work */
   napi_value promise, name;
   NAPI_CALL(env, napi_create_promise(env, &j->deferred, &promise));
-  NAPI_CALL(env, napi_create_string_utf8(env, "bgv_verify_same_message", NAPI_AUTO_LENGTH, &name));
+  NAPI_CALL(env, napi_create_string_utf8(env, agg ? "bgv_verify_same_message_agg" : "bgv_verify_same_message", NAPI_AUTO_LENGTH,
+                                         &name));
   NAPI_CALL(env, napi_create_async_work(env, NULL, name, sm_exec, sm_done, j, &j->work));
   NAPI_CALL(env, napi_queue_async_work(env, j->work));
   return promise;
 }
 
-static napi_value VerifySameMessageSync(napi_env env, napi_callback_info info) {
+static napi_value sm_sync(napi_env env, napi_callback_info info, int agg) {
   size_t argc = 2;
   napi_value a[2];
   NAPI_CALL(env, napi_get_cb_info(env, info, &argc, a, NULL, NULL));
@@ -726,6 +766,7 @@ static napi_value VerifySameMessageSync(napi_env env, napi_callback_info info) {
   sm_job j;
   memset(&j, 0, sizeof j);
   j.c = c;
+  j.agg = agg;
   napi_value r = NULL;
   if (!sm_read_batch(env, a[1], &j, 0)) {
     sm_run(&j);
@@ -735,6 +776,11 @@ static napi_value VerifySameMessageSync(napi_env env, napi_callback_info info) {
   sm_free(env, &j);
   return r;
 }
+
+static napi_value VerifySameMessage(napi_env env, napi_callback_info info) { return sm_async(env, info, 0); }
+static napi_value VerifySameMessageSync(napi_env env, napi_callback_info info) { return sm_sync(env, info, 0); }
+static napi_value VerifySameMessageAgg(napi_env env, napi_callback_info info) { return sm_async(env, info, 1); }
+static napi_value VerifySameMessageAggSync(napi_env env, napi_callback_info info) { return sm_sync(env, info, 1); }
 
 static napi_value Init(napi_env env, napi_value exports) {
   napi_property_descriptor d[] = {
@@ -753,6 +799,8 @@ static napi_value Init(napi_env env, napi_value exports) {
       {"combineFinal", NULL, CombineFinal, NULL, NULL, NULL, napi_enumerable, NULL},
       {"verifySameMessage", NULL, VerifySameMessage, NULL, NULL, NULL, napi_enumerable, NULL},
       {"verifySameMessageSync", NULL, VerifySameMessageSync, NULL, NULL, NULL, napi_enumerable, NULL},
+      {"verifySameMessageAgg", NULL, VerifySameMessageAgg, NULL, NULL, NULL, napi_enumerable, NULL},
+      {"verifySameMessageAggSync", NULL, VerifySameMessageAggSync, NULL, NULL, NULL, napi_enumerable, NULL},
   };
   if (napi_define_properties(env, exports, sizeof d / sizeof d[0], d) != napi_ok) return NULL;
   return exports;

@@ -252,6 +252,55 @@ function encodeSameMessage(groups) {
   return {groupOffsets, pkIndices, msgs, sigs, sigLen, rawPks};
 }
 
+// the caller-side checks of one verifyAggregateSetsSameMessage call: every set is
+// {publicKeys: [{index} | {raw} | validator index, ...], signature} with at least one key
+function checkAggregateSameMessage(sets, message) {
+  if (!message || message.length !== 32) throw Error("signingRoot must be 32 bytes");
+  for (const s of sets) {
+    if (!s || !s.publicKeys || s.publicKeys.length === 0) throw Error("EMPTY_AGGREGATE_ARRAY");
+    for (const pk of s.publicKeys) {
+      if (pk === null || pk === undefined) throw Error("EMPTY_AGGREGATE_ARRAY");
+      if (typeof pk !== "number" && pk.raw && pk.raw.length !== 96) throw Error("raw pubkeys must be 96-byte uncompressed");
+    }
+  }
+}
+
+// groups [{message, sets: [{publicKeys, signature}]}] -> the arrays of include/bgv.h bgv_sma_batch
+function encodeSameMessageAgg(groups) {
+  let n = 0, nKeys = 0, nRaw = 0;
+  for (const g of groups) {
+    if (g.sets.length === 0) throw Error("Empty signature set");
+    n += g.sets.length;
+    for (const s of g.sets) {
+      if (s.publicKeys.length === 0) throw Error("EMPTY_AGGREGATE_ARRAY");
+      nKeys += s.publicKeys.length;
+      for (const pk of s.publicKeys) if (typeof pk !== "number" && pk.raw) nRaw++;
+    }
+  }
+  const groupOffsets = new Uint32Array(groups.length + 1);
+  const pkOffsets = new Uint32Array(n + 1);
+  const pkIndices = new Uint32Array(Math.max(nKeys, 1));
+  const rawPks = new Uint8Array(Math.max(nRaw, 1) * 96);
+  const msgs = new Uint8Array(Math.max(groups.length, 1) * 32);
+  const sigs = new Uint8Array(Math.max(n, 1) * 192);
+  const sigLen = new Uint32Array(Math.max(n, 1));
+  let i = 0, k = 0, r = 0;
+  groups.forEach((g, gi) => {
+    msgs.set(g.message, 32 * gi);
+    for (const s of g.sets) {
+      for (const pk of s.publicKeys) {
+        if (typeof pk === "number") pkIndices[k++] = pk >>> 0;
+        else if (pk.raw) { pkIndices[k++] = (RAW_BIT | r) >>> 0; rawPks.set(pk.raw, 96 * r++); } else pkIndices[k++] = pk.index >>> 0;
+      }
+      sigLen[i] = s.signature.length;
+      if (s.signature.length === 96 || s.signature.length === 192) sigs.set(s.signature, 192 * i);
+      pkOffsets[++i] = k;
+    }
+    groupOffsets[gi + 1] = i;
+  });
+  return {groupOffsets, pkOffsets, pkIndices, msgs, sigs, sigLen, rawPks};
+}
+
 // device work of a job in Montgomery Fp products (lodestar_amd/dist.py
 // job_work, from tools/fpmul_counts.json): per set 13,790, per pubkey
 // reference 11 (one G1 mixed addition of the gather)
@@ -313,6 +362,9 @@ function newMetrics() {
     // verifySignatureSetsSameMessage: sets sent to the device, and groups that went to the per-set retry
     lodestar_bls_thread_pool_same_message_sig_sets_started_total: 0,
     lodestar_bls_thread_pool_same_message_retries_total: 0,
+    // verifyAggregateSetsSameMessage: the same two counters for aggregate sets
+    lodestar_bls_thread_pool_same_message_agg_sig_sets_started_total: 0,
+    lodestar_bls_thread_pool_same_message_agg_retries_total: 0,
   };
 }
 
@@ -403,6 +455,13 @@ class BlsGpuVerifier {
     this.smDeviceCalls = 0; // merged device calls issued (test hook)
     this.runSameMessage = this.runSameMessage.bind(this);
     this.flushSameMessage = this.flushSameMessage.bind(this);
+    // verifyAggregateSetsSameMessage: again a queue and a buffer of their own
+    this.smaJobs = [];
+    this.smaBuffered = null;
+    this.smaRunning = false;
+    this.smaDeviceCalls = 0; // merged device calls issued (test hook)
+    this.runSameMessageAgg = this.runSameMessageAgg.bind(this);
+    this.flushSameMessageAgg = this.flushSameMessageAgg.bind(this);
   }
 
   // syncPubkeys / addPubkey (pubkeyCache.ts:56-77): 48-byte compressed keys, every replica
@@ -435,9 +494,11 @@ class BlsGpuVerifier {
   // not (gating on idle devices would stop the network processor,
   // network/processor/index.ts:406, for every 5-40 ms device batch)
   canAcceptWork() {
-    const smJobs = this.smJobs.length + (this.smBuffered ? this.smBuffered.jobs.length : 0);
-    let smSets = this.smBuffered ? this.smBuffered.sigCount : 0;
+    const smJobs = this.smJobs.length + (this.smBuffered ? this.smBuffered.jobs.length : 0) +
+      this.smaJobs.length + (this.smaBuffered ? this.smaBuffered.jobs.length : 0);
+    let smSets = (this.smBuffered ? this.smBuffered.sigCount : 0) + (this.smaBuffered ? this.smaBuffered.sigCount : 0);
     for (const j of this.smJobs) smSets += j.sets.length;
+    for (const j of this.smaJobs) smSets += j.sets.length;
     return !this.closed && this.jobs.length + smJobs < MAX_JOBS_CAN_ACCEPT_WORK && this.queuedSets + smSets < this.maxSetsPerDeviceBatch;
   }
 
@@ -503,6 +564,72 @@ class BlsGpuVerifier {
     }
     this.smRunning = false;
     if (this.smJobs.length > 0) setTimeout(this.runSameMessage, 0);
+  }
+
+  // verifySignatureSetsSameMessage for aggregate sets (the aggregates of gossip
+  // beacon_aggregate_and_proof objects, chain/validation/aggregateAndProof.ts:164-179,
+  // or of one block's attestations for one committee and data):
+  // sets = [{publicKeys: [{index} | {raw} | validator index, ...], signature}] that all
+  // sign `message`; resolves one boolean per set, false for a rejected set.
+  // Batchable calls wait in a buffer of their own, apart from the single-key
+  // one, under the same rule, and go out as ONE merged device call
+  // (bgv_verify_same_message_agg), one group per call.
+  async verifyAggregateSetsSameMessage(sets, message, opts = {}) {
+    if (this.closed) throw new QueueError();
+    if (sets.length === 0) return [];
+    checkAggregateSameMessage(sets, message);
+    return new Promise((resolve, reject) => {
+      const job = {resolve, reject, sets, message, addedTimeMs: Date.now()};
+      if (opts.batchable) {
+        if (!this.smaBuffered) this.smaBuffered = {jobs: [], sigCount: 0, timeout: setTimeout(this.flushSameMessageAgg, MAX_BUFFER_WAIT_MS)};
+        this.smaBuffered.jobs.push(job);
+        this.smaBuffered.sigCount += sets.length;
+        if (this.smaBuffered.sigCount > MAX_BUFFERED_SIGS) {
+          clearTimeout(this.smaBuffered.timeout);
+          this.flushSameMessageAgg();
+        }
+      } else {
+        this.smaJobs.push(job);
+        setTimeout(this.runSameMessageAgg, 0);
+      }
+    });
+  }
+
+  flushSameMessageAgg() {
+    if (this.smaBuffered) {
+      this.smaJobs.push(...this.smaBuffered.jobs);
+      this.smaBuffered = null;
+      setTimeout(this.runSameMessageAgg, 0);
+    }
+  }
+
+  async runSameMessageAgg() {
+    if (this.closed || this.smaRunning || this.smaJobs.length === 0) return;
+    this.smaRunning = true;
+    const jobs = [];
+    let n = 0;
+    while (this.smaJobs.length > 0 && (jobs.length === 0 || n + this.smaJobs[0].sets.length <= this.maxSetsPerDeviceBatch)) {
+      const j = this.smaJobs.shift();
+      jobs.push(j);
+      n += j.sets.length;
+    }
+    const m = this.metrics;
+    try {
+      const {groups, where} = mergeSameMessage(jobs);
+      const {best} = this.idleContexts();
+      const batch = encodeSameMessageAgg(groups);
+      this.smaDeviceCalls++;
+      m.lodestar_bls_thread_pool_same_message_agg_sig_sets_started_total += n;
+      m.lodestar_bls_aggregated_pubkeys_total += batch.pkOffsets[n];
+      const res = await addon.verifySameMessageAgg(this.ctxs[best >= 0 ? best : 0], batch);
+      m.lodestar_bls_thread_pool_same_message_agg_retries_total += res.groupsRetried;
+      m.lodestar_bls_thread_pool_time_seconds_sum += (res.workerEndMs - res.workerStartMs) / 1000;
+      jobs.forEach((job, k) => job.resolve(Array.from(res.valid.subarray(where[k][0], where[k][1]), (v) => v === 1)));
+    } catch (e) {
+      for (const job of jobs) job.reject(e);
+    }
+    this.smaRunning = false;
+    if (this.smaJobs.length > 0) setTimeout(this.runSameMessageAgg, 0);
   }
 
   async verifySignatureSets(sets, opts = {}) {
@@ -773,6 +900,13 @@ class BlsGpuVerifier {
     }
     for (const job of this.smJobs) job.reject(new QueueError());
     this.smJobs = [];
+    if (this.smaBuffered) {
+      clearTimeout(this.smaBuffered.timeout);
+      for (const job of this.smaBuffered.jobs) job.reject(new QueueError());
+      this.smaBuffered = null;
+    }
+    for (const job of this.smaJobs) job.reject(new QueueError());
+    this.smaJobs = [];
     for (const c of this.allContexts()) addon.close(c); // each waits for its batch in flight (the context mutex)
   }
 }
@@ -818,6 +952,17 @@ class BlsGpuSingleThreadVerifier {
     return Array.from(res.valid, (v) => v === 1);
   }
 
+  // verifyAggregateSetsSameMessage on the calling thread: one device call, one group
+  async verifyAggregateSetsSameMessage(sets, message) {
+    if (this.closed) throw new QueueError();
+    if (sets.length === 0) return [];
+    checkAggregateSameMessage(sets, message);
+    const batch = encodeSameMessageAgg([{message, sets}]);
+    this.metrics.lodestar_bls_aggregated_pubkeys_total += batch.pkOffsets[sets.length];
+    const res = addon.verifySameMessageAggSync(this.ctx, batch);
+    return Array.from(res.valid, (v) => v === 1);
+  }
+
   async close() {
     if (this.closed) return;
     this.closed = true;
@@ -831,6 +976,6 @@ class BlsGpuSingleThreadVerifier {
 
 module.exports = {
   addon, BlsGpuVerifier, BlsGpuSingleThreadVerifier, QueueError, sourceHash, checkBuildId, chunkifyMaximizeChunkSize, encodeJobs, checkSets, shardJobs, jobWork,
-  encodeSameMessage, mergeSameMessage, checkSameMessage,
+  encodeSameMessage, mergeSameMessage, checkSameMessage, encodeSameMessageAgg, checkAggregateSameMessage,
   MAX_BUFFERED_SIGS, MAX_BUFFER_WAIT_MS, MAX_JOBS_CAN_ACCEPT_WORK, SHARD_MIN_SETS, PRIORITY_CUS, RESERVED_CAP, CONTEXTS_PER_DEVICE,
 };

@@ -52,6 +52,7 @@ EXPORTS = [
     "bgv_partial", "bgv_partial_finish", "bgv_combine_final", "bgv_debug_stages", "bgv_gen_keys", "bgv_gen_sign", "bgv_bench_fpmul",
     "bgv_bench_mad", "bgv_debug_fp_ops", "bgv_debug_g2_decode",
     "bgv_verify_same_message", "bgv_sm_check", "bgv_debug_same_message",
+    "bgv_verify_same_message_agg", "bgv_sma_check", "bgv_debug_same_message_agg",
 ]
 FP_OPS_N = 13
 
@@ -123,6 +124,24 @@ class BgvSmBatch(ctypes.Structure):
         ("n_sets", ctypes.c_uint32),
         ("n_groups", ctypes.c_uint32),
         ("group_offsets", ctypes.c_void_p),
+        ("pk_indices", ctypes.c_void_p),
+        ("raw_pks", ctypes.c_void_p),
+        ("n_raw", ctypes.c_uint32),
+        ("msgs", ctypes.c_void_p),
+        ("sigs", ctypes.c_void_p),
+        ("sig_len", ctypes.c_void_p),
+        ("scalars", ctypes.c_void_p),
+        ("on_device", ctypes.c_uint32),
+    ]
+
+
+class BgvSmaBatch(ctypes.Structure):
+    """bgv_sma_batch (include/bgv.h): aggregate sets grouped by message."""
+    _fields_ = [
+        ("n_sets", ctypes.c_uint32),
+        ("n_groups", ctypes.c_uint32),
+        ("group_offsets", ctypes.c_void_p),
+        ("pk_offsets", ctypes.c_void_p),
         ("pk_indices", ctypes.c_void_p),
         ("raw_pks", ctypes.c_void_p),
         ("n_raw", ctypes.c_uint32),
@@ -267,6 +286,10 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
             "bgv_verify_same_message": ([P, ctypes.POINTER(BgvSmBatch), P, P, ctypes.POINTER(BgvSmStats)], ctypes.c_int),
             "bgv_sm_check": ([ctypes.POINTER(BgvSmBatch)], ctypes.c_int),
             "bgv_debug_same_message": ([P, ctypes.POINTER(BgvSmBatch), P, P, ctypes.POINTER(BgvSmStats), P, P, P], ctypes.c_int),
+            "bgv_verify_same_message_agg": ([P, ctypes.POINTER(BgvSmaBatch), P, P, ctypes.POINTER(BgvSmStats)], ctypes.c_int),
+            "bgv_sma_check": ([ctypes.POINTER(BgvSmaBatch)], ctypes.c_int),
+            "bgv_debug_same_message_agg": ([P, ctypes.POINTER(BgvSmaBatch), P, P, ctypes.POINTER(BgvSmStats), P, P, P, P],
+                                           ctypes.c_int),
         }
         for name, (args, res) in sig.items():
             fn = getattr(lib, name)
@@ -310,6 +333,15 @@ def _sync_producers(*objs) -> None:
             seen.add(key)
             import torch
             torch.cuda.current_stream(dev).synchronize()
+
+
+def sma_check(arrays: dict, on_device: bool = False) -> tuple[int, str]:
+    """bgv_sma_check: the host-side contract of bgv_verify_same_message_agg, without
+    a device.  (status, bgv_last_error() text); the text is empty for BGV_OK."""
+    lib = load_library()
+    b = Device.make_sma_batch(arrays, on_device, sync_inputs=False)
+    st = lib.bgv_sma_check(ctypes.byref(b))
+    return st, ("" if st == BGV_OK else lib.bgv_last_error().decode())
 
 
 class Device:
@@ -454,6 +486,55 @@ class Device:
                                                     hg.ctypes.data))
         return {"set_valid": ok[:n].astype(bool), "set_code": sc[:n], "p_group": pg[:G], "s_group": sg[:G],
                 "h_group": hg[:G], "stats": self.last_sm_stats.as_dict()}
+
+    @staticmethod
+    def make_sma_batch(arrays: dict, on_device: bool = False, sync_inputs: bool = True) -> BgvSmaBatch:
+        """arrays as verifier.encode_same_message_agg returns them"""
+        b = BgvSmaBatch()
+        b.n_sets = int(arrays["n_sets"])
+        b.n_groups = int(arrays["n_groups"])
+        b.group_offsets = _ptr(arrays["group_offsets"])
+        b.pk_offsets = _ptr(arrays["pk_offsets"])
+        b.pk_indices = _ptr(arrays["pk_indices"])
+        b.raw_pks = _ptr(arrays.get("raw_pks"))
+        b.n_raw = int(arrays.get("n_raw", 0))
+        b.msgs = _ptr(arrays["msgs"])
+        b.sigs = _ptr(arrays["sigs"])
+        b.sig_len = _ptr(arrays["sig_len"])
+        b.scalars = _ptr(arrays.get("scalars"))
+        b.on_device = 1 if on_device else 0
+        if on_device and sync_inputs:
+            _sync_producers(arrays)
+        return b
+
+    def verify_same_message_agg(self, arrays: dict, on_device: bool = False, sync_inputs: bool = True):
+        """bgv_verify_same_message_agg: (set_valid bool[n_sets], set_code int32[n_sets]);
+        the counters of the call are left in last_sm_stats"""
+        b = self.make_sma_batch(arrays, on_device, sync_inputs)
+        ok = np.zeros(max(b.n_sets, 1), dtype=np.uint8)
+        sc = np.zeros(max(b.n_sets, 1), dtype=np.int32)
+        self.last_sm_stats = BgvSmStats()
+        self._check(self.lib.bgv_verify_same_message_agg(self.h, ctypes.byref(b), ok.ctypes.data, sc.ctypes.data,
+                                                         ctypes.byref(self.last_sm_stats)))
+        return ok[: b.n_sets].astype(bool), sc[: b.n_sets]
+
+    def debug_same_message_agg(self, arrays: dict, on_device: bool = False) -> dict:
+        """bgv_debug_same_message_agg (test only): the verdicts plus PK_i per set and
+        P_g, S_g and H(m_g) per group"""
+        b = self.make_sma_batch(arrays, on_device)
+        n, G = b.n_sets, b.n_groups
+        ok = np.zeros(max(n, 1), dtype=np.uint8)
+        sc = np.zeros(max(n, 1), dtype=np.int32)
+        ps = np.zeros((max(n, 1), 96), np.uint8)
+        pg = np.zeros((max(G, 1), 96), np.uint8)
+        sg = np.zeros((max(G, 1), 192), np.uint8)
+        hg = np.zeros((max(G, 1), 192), np.uint8)
+        self.last_sm_stats = BgvSmStats()
+        self._check(self.lib.bgv_debug_same_message_agg(self.h, ctypes.byref(b), ok.ctypes.data, sc.ctypes.data,
+                                                        ctypes.byref(self.last_sm_stats), ps.ctypes.data, pg.ctypes.data,
+                                                        sg.ctypes.data, hg.ctypes.data))
+        return {"set_valid": ok[:n].astype(bool), "set_code": sc[:n], "pk_set": ps[:n], "p_group": pg[:G],
+                "s_group": sg[:G], "h_group": hg[:G], "stats": self.last_sm_stats.as_dict()}
 
     def partial(self, arrays: dict, on_device: bool = False, sync_inputs: bool = True):
         """bgv_partial: (miller576 bytes, set codes, provisional job results

@@ -487,6 +487,108 @@ class SameMessageQueue:
         self._buffered.clear()
 
 
+# --------------------------------- same-message batches of aggregate sets
+def _as_pubkeys(pks) -> list:
+    """a set's keys: PublicKeys, or validator indices (ints, or an integer array)"""
+    return [pk if isinstance(pk, PublicKey) else PublicKey(index=int(pk)) for pk in pks]
+
+
+def check_aggregate_same_message(sets, message: bytes) -> None:
+    """Caller-side checks of one verifyAggregateSetsSameMessage call, as
+    check_sets makes them: every set is (pubkeys, signature) with at least one
+    key (PublicKey.aggregate throws EMPTY_AGGREGATE_ARRAY), given as PublicKeys
+    or as validator indices; a raw key is a 96-byte uncompressed point; the
+    signing root is 32 bytes."""
+    if len(message) != 32:
+        raise BlsError("signingRoot must be 32 bytes")
+    for pks, _sig in sets:
+        if pks is None or len(pks) == 0:
+            raise BlsError("EMPTY_AGGREGATE_ARRAY")
+        for pk in pks:
+            if pk is None:
+                raise BlsError("EMPTY_AGGREGATE_ARRAY")
+            if not isinstance(pk, PublicKey):
+                pk = PublicKey(index=int(pk))
+            if pk.index is None and len(pk.raw) != 96:
+                _decompress_raw48(pk.raw)
+            if pk.index is not None and not (0 <= pk.index < 0x80000000):
+                raise BlsError(f"pubkey index {pk.index} out of range")
+
+
+def encode_same_message_agg(groups, scalars: np.ndarray | None = None) -> dict:
+    """Flatten groups [(message, [(pubkeys, signature), ...]), ...] into the
+    arrays of bgv_sma_batch (include/bgv.h): one message per group, a key list
+    and one signature per set.  `pubkeys` holds PublicKeys or validator indices,
+    as encode_jobs takes them from an aggregate set."""
+    n = sum(len(g[1]) for g in groups)
+    G = len(groups)
+    off = [0]
+    pk_off = [0]
+    idx: list[int] = []
+    raw: list[bytes] = []
+    raw_pos: dict[bytes, int] = {}
+    msgs = np.zeros((max(G, 1), 32), dtype=np.uint8)
+    sigs = np.zeros((max(n, 1), 192), dtype=np.uint8)
+    sig_len = np.zeros(max(n, 1), dtype=np.uint32)
+    i = 0
+    for g, (message, sets) in enumerate(groups):
+        if len(sets) == 0:
+            raise BlsError("Empty signature set", 10)
+        if len(message) != 32:
+            raise BlsError("signingRoot must be 32 bytes")
+        msgs[g] = np.frombuffer(bytes(message), dtype=np.uint8)
+        for pks, sig in sets:
+            if len(pks) == 0:
+                raise BlsError("EMPTY_AGGREGATE_ARRAY")
+            for pk in _as_pubkeys(pks):
+                if pk.index is not None:
+                    idx.append(pk.index)
+                else:
+                    r = pk.raw if len(pk.raw) == 96 else _decompress_raw48(pk.raw)
+                    if r not in raw_pos:
+                        raw_pos[r] = len(raw)
+                        raw.append(r)
+                    idx.append(0x80000000 | raw_pos[r])
+            pk_off.append(len(idx))
+            sl = len(sig)
+            sig_len[i] = sl
+            if sl in (96, 192):
+                sigs[i, :sl] = np.frombuffer(bytes(sig), dtype=np.uint8)
+            i += 1
+        off.append(i)
+    return {
+        "n_sets": n,
+        "n_groups": G,
+        "group_offsets": np.array(off, dtype=np.uint32),
+        "pk_offsets": np.array(pk_off, dtype=np.uint32),
+        "pk_indices": np.array(idx if idx else [0], dtype=np.uint32),
+        "raw_pks": np.frombuffer(b"".join(raw), dtype=np.uint8).copy() if raw else None,
+        "n_raw": len(raw),
+        "msgs": msgs,
+        "sigs": sigs,
+        "sig_len": sig_len,
+        "scalars": scalars,
+    }
+
+
+def run_same_message_agg_calls(device, calls, scalars_for=None, metrics: dict | None = None) -> list:
+    """One device call (Device.verify_same_message_agg) for the merged calls
+    (merge_same_message: one group per call, equal messages share one);
+    returns list[bool] per call."""
+    groups, where = merge_same_message(calls)
+    n = sum(len(g[1]) for g in groups)
+    arrays = encode_same_message_agg(groups, scalars_for(n) if scalars_for else None)
+    ok, _codes = device.verify_same_message_agg(arrays)
+    if metrics is not None:
+        st = getattr(device, "last_sm_stats", None)
+        metrics["same_message_agg_sets_started"] = metrics.get("same_message_agg_sets_started", 0) + n
+        metrics["same_message_agg_retries"] = (metrics.get("same_message_agg_retries", 0)
+                                               + (int(st.groups_retried) if st is not None else 0))
+        metrics["aggregated_pubkeys_total"] = metrics.get("aggregated_pubkeys_total", 0) + int(arrays["pk_offsets"][-1])
+    ok = [bool(x) for x in ok]
+    return [ok[w] for w in where]
+
+
 # ----------------------------------------------------------------- verifier
 @dataclass
 class _Job:
@@ -561,6 +663,7 @@ class BlsGpuVerifier:
         self._exec = ThreadPoolExecutor(max_workers=len(self.devices) + 1)  # + the main-thread path
         self._dev_locks = [threading.Lock() for _ in self.devices]
         self._sm = SameMessageQueue(self._run_same_message, self._exec, max_sets_per_device_batch)
+        self._sma = SameMessageQueue(self._run_same_message_agg, self._exec, max_sets_per_device_batch)
 
     # -- IBlsVerifier ---------------------------------------------------
     def can_accept_work(self) -> bool:
@@ -570,8 +673,9 @@ class BlsGpuVerifier:
         sets, whether or not a batch is in flight (a GPU wants large batches;
         gating on idle devices would stall the network processor for every
         batch, network/processor/index.ts:406)."""
-        return (not self._closed and len(self._jobs) + self._sm.pending_jobs() < MAX_JOBS_CAN_ACCEPT_WORK
-                and sum(len(j.sets) for j in self._jobs) + self._sm.pending_sets() < self._max_batch)
+        return (not self._closed
+                and len(self._jobs) + self._sm.pending_jobs() + self._sma.pending_jobs() < MAX_JOBS_CAN_ACCEPT_WORK
+                and sum(len(j.sets) for j in self._jobs) + self._sm.pending_sets() + self._sma.pending_sets() < self._max_batch)
 
     async def verify_signature_sets_same_message(self, sets, message: bytes, opts: VerifySignatureOpts | None = None) -> list:
         """IBlsVerifier.verifySignatureSetsSameMessage (upstream Lodestar; the
@@ -588,6 +692,24 @@ class BlsGpuVerifier:
         if self._closed:
             raise QueueError(QueueErrorCode.QUEUE_ABORTED)
         return await self._sm.submit(sets, message, opts.batchable)
+
+    async def verify_aggregate_sets_same_message(self, sets, message: bytes, opts: VerifySignatureOpts | None = None) -> list:
+        """verifySignatureSetsSameMessage for aggregate sets: `sets` is a list of
+        (pubkeys, signature) that all sign `message` (the aggregates of gossip
+        beacon_aggregate_and_proof objects, chain/validation/
+        aggregateAndProof.ts:164-179, or of one block's attestations for one
+        committee and data); one boolean per set, False for a rejected set.
+        Batchable calls wait in a buffer of their own, apart from the single-key
+        one, and are merged into one device call
+        (bgv_verify_same_message_agg), one group per call."""
+        opts = opts or VerifySignatureOpts()
+        sets = list(sets)
+        if not sets:
+            return []
+        check_aggregate_same_message(sets, message)
+        if self._closed:
+            raise QueueError(QueueErrorCode.QUEUE_ABORTED)
+        return await self._sma.submit(sets, message, opts.batchable)
 
     async def verify_signature_sets(self, sets: list[ISignatureSet], opts: VerifySignatureOpts | None = None) -> bool:
         opts = opts or VerifySignatureOpts()
@@ -621,6 +743,7 @@ class BlsGpuVerifier:
         self._jobs.clear()
         self._buffered.clear()
         self._sm.abort()
+        self._sma.abort()
         self._exec.shutdown(wait=True)
         for d in self._contexts():
             d.close()
@@ -798,6 +921,17 @@ class BlsGpuVerifier:
             self.metrics["device_time_s"] = self.metrics.get("device_time_s", 0.0) + time.perf_counter() - t0
         return out
 
+    def _run_same_message_agg(self, calls) -> list:
+        """the merged same-message calls of aggregate sets on one bulk context"""
+        idle = [k for k, f in enumerate(self._idle) if f]
+        d = idle[0] if idle else 0
+        with self._dev_locks[d]:
+            t0 = time.perf_counter()
+            out = run_same_message_agg_calls(self.devices[d], calls, self._scalars if self._rng is not None else None,
+                                             self.metrics)
+            self.metrics["device_time_s"] = self.metrics.get("device_time_s", 0.0) + time.perf_counter() - t0
+        return out
+
     def _run_device_batch(self, jobs: list[list[ISignatureSet]], devs: list[int] | None = None) -> list:
         """Verify a list of jobs on the devices `devs` (default: all); returns
         per job True / False / BlsError.  One device: bgv_verify.  Several: the
@@ -939,6 +1073,16 @@ class BlsGpuSingleThreadVerifier:
         check_same_message(sets, message)
         return run_same_message_calls(self.device, [(sets, message)], None, self.metrics)[0]
 
+    async def verify_aggregate_sets_same_message(self, sets, message: bytes, opts: VerifySignatureOpts | None = None) -> list:
+        """verify_aggregate_sets_same_message in the calling thread: one device call, one group"""
+        if self._closed:
+            raise QueueError(QueueErrorCode.QUEUE_ABORTED)
+        sets = list(sets)
+        if not sets:
+            return []
+        check_aggregate_same_message(sets, message)
+        return run_same_message_agg_calls(self.device, [(sets, message)], None, self.metrics)[0]
+
     def can_accept_work(self) -> bool:
         return True
 
@@ -1012,4 +1156,6 @@ def _new_metrics() -> dict:
         "job_wait_time_s": [],
         "same_message_sets_started": 0,
         "same_message_retries": 0,
+        "same_message_agg_sets_started": 0,
+        "same_message_agg_retries": 0,
     }

@@ -11,7 +11,7 @@
  * success or a negative BGV_E* status; per-set verification outcomes are
  * reported as the positive blst error codes listed in bgv_set_code.
  *
- * Threading: a bgv_ctx owns one HIP device and one stream.  Calls on one
+ * Threading: a bgv_ctx owns one HIP device and four streams.  Calls on one
  * context must be serialised by the caller (the N-API / Python host layers
  * do this); different contexts may be used from different threads.
  */
@@ -383,6 +383,96 @@ int bgv_sma_check(const bgv_sma_batch* batch);
 int bgv_debug_same_message_agg(bgv_ctx* ctx, const bgv_sma_batch* batch, uint8_t* set_valid, int32_t* set_code,
                                bgv_sm_stats* stats, uint8_t* pk_set96, uint8_t* p_group96, uint8_t* s_group192,
                                uint8_t* h_group192);
+
+/* ---- committee bitfields over resident index lists --------------------------
+ * The reference never holds attesters as index lists.  It holds a committee (a
+ * slice of the epoch's shuffling, or the 512-member sync committee) and a
+ * participation bitfield, and expands them on the main thread at every
+ * producer: aggregationBits.intersectValues(committeeIndices)
+ * (state-transition/src/cache/epochContext.ts:620-623,
+ * block/processSyncCommittee.ts:89, chain/validation/aggregateAndProof.ts:129,
+ * syncCommitteeContributionAndProof.ts:118).  Here the committees live in HBM
+ * beside the index2pubkey table and a set says "list L, window [off, off +
+ * len), these bits"; the device expands it.  Additive to ABI 4.
+ *
+ * Index lists are per context, like the table replica.  bgv_index_list_set
+ * replaces list `list_id` (n == 0 drops it).  Entries are table rows: an entry
+ * with bit 31 set fails with BGV_E_INVALID_ARG and leaves the list unchanged.
+ * An entry at or past the current table count is allowed (the table is
+ * append-only and may grow later); the range check stays per set, in the
+ * gather.  The list being replaced is freed only after every stream of the
+ * context has drained.                                                       */
+#define BGV_MAX_INDEX_LISTS 8 /* previous/current/next shuffling, current/next sync committee, spare */
+int bgv_index_list_set(bgv_ctx* ctx, uint32_t list_id, const uint32_t* indices /* host */, uint32_t n);
+int bgv_index_list_len(bgv_ctx* ctx, uint32_t list_id, uint32_t* n);
+
+/* The keys of set i:
+ *  - src[i].list < BGV_MAX_INDEX_LISTS: L[off + j] for every j < len whose bit
+ *    is set, in ascending j; bit j is (bits[bits_off + (j >> 3)] >> (j & 7)) & 1
+ *    (the SSZ bit order).  bits_off is a byte offset of any alignment; two sets
+ *    may point at the same bytes.
+ *  - src[i].list == BGV_SRC_EXPLICIT: pk_indices[off .. off + len), all of
+ *    them (bit 31 selects raw_pks); bits_off is ignored.  Randao, proposer and
+ *    exit signatures and raw BLS-to-execution keys come this way.
+ * job_result, set_code and stats are those of bgv_verify on the bgv_batch whose
+ * pk_offsets / pk_indices are that expansion and whose other fields are equal.
+ *
+ * Host batches are staged into pinned memory and checked on that copy
+ * (bgv_bits_check runs the same checks alone); every refusal names the set in
+ * bgv_last_error().  BGV_E_INVALID_ARG: job offsets that break the bgv_batch
+ * rules; a list id that names no list that is set; off + len (in 64 bits) past
+ * the list, or past n_indices for an explicit set; bits_off + ceil(len / 8) >
+ * bits_len; a non-zero padding bit above len in the last byte (intersectValues
+ * throws on a length mismatch); a key total that does not fit 32 bits.
+ * BGV_E_EMPTY_SET: a set with no bit set, or an explicit set with len == 0.
+ * On-device batches are trusted, but cause no access outside the lists, bits,
+ * pk_indices or the expansion: a source that fails the span checks expands to
+ * the single index 0x7fffffff (past any table), so its job is rejected with
+ * BGV_SET_INDEX_RANGE, and padding bits are masked off.
+ *
+ * When it pays (tools/bench_bits.py; host-resident
+ * batches, one MI355X): the call stages 16 B per set and the bitfields instead
+ * of 4 B per key.  At the C4 range-sync segment (100,352 sets, 12.98 M keys)
+ * that is 26.1 MB instead of 75.2 MB and the call is about 1.6 ms faster than
+ * bgv_verify on explicit lists (39.7 against 41.3 ms, beyond either path's
+ * run-to-run spread; the expansion kernels take 0.18 ms).  At one epoch (3,136
+ * sets) and at a 64-set gossip batch the two are within the baseline's spread:
+ * there the gain is the index lists the caller no longer builds on its main
+ * thread, not device time.                                                   */
+#define BGV_SRC_EXPLICIT 0xffffffffu
+typedef struct bgv_set_src { uint32_t list, off, len, bits_off; } bgv_set_src; /* 16 B per set */
+typedef struct bgv_bits_batch {
+  uint32_t n_sets, n_jobs;
+  const uint32_t* job_offsets; /* [n_jobs + 1], as bgv_batch */
+  const bgv_set_src* src;      /* [n_sets] */
+  const uint8_t* bits;         /* all bitfields, byte-packed */
+  uint32_t bits_len;
+  const uint32_t* pk_indices;  /* keys of explicit sets; bit 31 selects raw_pks */
+  uint32_t n_indices;
+  const uint8_t* raw_pks;      /* [n_raw][96], may be NULL */
+  uint32_t n_raw;
+  const uint8_t* msgs;         /* [n_sets][32] */
+  const uint8_t* sigs;         /* [n_sets][192] */
+  const uint32_t* sig_len;     /* [n_sets] */
+  const uint64_t* scalars;     /* [n_sets] or NULL, as bgv_batch */
+  uint32_t on_device;
+} bgv_bits_batch;
+/* Outputs as bgv_verify.  Counts as a batch in flight like bgv_verify. */
+int bgv_verify_bits(bgv_ctx* ctx, const bgv_bits_batch* batch, int32_t* job_result, int32_t* set_code, bgv_stats* stats);
+/* The host-side contract check on its own (no device, no context), against the
+ * lengths of the lists (0: not set).  The arrays of an on-device batch are not
+ * read. */
+int bgv_bits_check(const bgv_bits_batch* batch, const uint32_t* list_len /* [BGV_MAX_INDEX_LISTS] */);
+/* test-only: the expansion alone; msgs, sigs, sig_len and scalars are not read.
+ * pk_offsets[n_sets + 1] and *total (host memory) are always written; the
+ * indices are copied to pk_indices (host memory, cap entries) when total <= cap,
+ * else the call fails with BGV_E_INVALID_ARG. */
+int bgv_debug_bits_expand(bgv_ctx* ctx, const bgv_bits_batch* batch, uint32_t* pk_offsets /* [n_sets+1] */,
+                          uint32_t* pk_indices, uint32_t cap, uint32_t* total);
+/* Device time (ms, HIP events) of the expansion kernels of the last
+ * bgv_verify_bits on a context that records stage timings (bgv_cfg.timing = 1,
+ * or a batch of >= 65,536 sets); 0 otherwise. */
+int bgv_bits_expand_ms(bgv_ctx* ctx, float* ms);
 
 /* Multi-GPU partials: run the batch up to, but excluding, the
  * final exponentiation and return this shard's Miller product (576 B, 12

@@ -138,6 +138,12 @@ struct bgv_ctx {
   dbuf<g1j> sma_pk;           // per set: PK_i, Jacobian
   dbuf<int32_t> sma_pk_code;  // per set: its key code
   dbuf<g1a> sma_aff;          // PK_i affine: the retry's sets, or every set for the debug entry
+  // resident index lists (bgv_index_list_set) and the expansion of bgv_verify_bits
+  uint32_t* idx_list[BGV_MAX_INDEX_LISTS] = {};
+  uint32_t idx_list_n[BGV_MAX_INDEX_LISTS] = {};
+  dbuf<uint32_t> bits_off, bits_idx;  // pk_off[n_sets + 1], pk_idx[key total]
+  hipEvent_t ev_bits[2] = {};         // around the expansion kernels (timed runs)
+  bool bits_timed = false;
   // microbench scratch
   dbuf<fp_t> mb_fp;
   dbuf<uint64_t> mb_u64;
@@ -283,6 +289,7 @@ int bgv_open_cfg(int device, const bgv_cfg* cfg, bgv_ctx** out) {
   HIPCHK(hipEventCreateWithFlags(&c->ev_grp, hipEventDisableTiming));
   HIPCHK(hipEventCreateWithFlags(&c->ev_maps, hipEventDisableTiming));
   HIPCHK(hipEventCreateWithFlags(&c->ev_chk, hipEventDisableTiming));
+  for (auto& e : c->ev_bits) HIPCHK(hipEventCreate(&e));
   *out = c;
   c = nullptr;  // owned by the caller now
   return BGV_OK;
@@ -305,6 +312,10 @@ int bgv_close(bgv_ctx* c) {
   (void)hipEventDestroy(c->ev_grp);
   (void)hipEventDestroy(c->ev_maps);
   (void)hipEventDestroy(c->ev_chk);
+  for (auto& e : c->ev_bits) (void)hipEventDestroy(e);
+  for (auto& l : c->idx_list)
+    if (l) (void)hipFree(l);
+  c->bits_off.release(); c->bits_idx.release();
   if (c->pin_in) (void)hipHostFree(c->pin_in);
   if (c->pin_out) (void)hipHostFree(c->pin_out);
   if (c->table) (void)hipFree(c->table);
@@ -538,6 +549,8 @@ static int early_maps(bgv_ctx* c, dev_batch& d, bool after_staging) {
   return 0;
 }
 
+static int prepare_layout(bgv_ctx* c, dev_batch& d, const uint64_t* scalars, bool scalars_staged);
+
 // Build the device view of a batch: stage host arrays, convert raw pubkeys.
 // Host batches: the arrays are copied into pinned memory FIRST and every
 // contract check reads that copy, so the device only ever sees checked
@@ -619,6 +632,15 @@ static int prepare(bgv_ctx* c, const bgv_batch* b, dev_batch& d, bool need_sigs)
     if (n) HIPCHK(hipMemcpyAsync(&c->pk_total, b->pk_offsets + n, 4, hipMemcpyDeviceToHost, c->st));
     HIPCHK(hipStreamSynchronize(c->st));
   }
+  return prepare_layout(c, d, b->scalars, b->scalars && !b->on_device);
+}
+
+// The tail of prepare(), shared with bgv_verify_bits: the pipeline variant of a
+// batch whose device view (arrays, n_sets, span_log2) and key total
+// (c->pk_total) are set, and its scalars.  scalars_staged: d.scalars already
+// points at the staged copy of a host batch.
+static int prepare_layout(bgv_ctx* c, dev_batch& d, const uint64_t* scalars, bool scalars_staged) {
+  const uint32_t n = d.n_sets;
   const uint32_t total = c->pk_total;
   // grid bound of the chunked pubkey gather: sum ceil(k_i/32) <= total/32 + n
   d.chunk_bound = total / 32 + n;
@@ -724,10 +746,10 @@ static int prepare(bgv_ctx* c, const bgv_batch* b, dev_batch& d, bool need_sigs)
   d.job_lanes = k.job_lanes ? (uint32_t)k.job_lanes : 36u;
   // the scalars are allocated before the line decision below, so a line buffer
   // that ensure_or_release_lines gives up here is seen by that decision
-  if (b->scalars && !b->on_device) {
-    // staged with the other host arrays above
-  } else if (b->scalars) {
-    d.scalars = b->scalars;
+  if (scalars_staged) {
+    // staged with the other host arrays by the caller
+  } else if (scalars) {
+    d.scalars = scalars;
   } else {
     // fresh 64-bit multipliers on the device: ChaCha20 keyed by 32 bytes of
     // getrandom() (+ 12-byte nonce) per call, rng.h
@@ -994,6 +1016,260 @@ int bgv_verify(bgv_ctx* c, const bgv_batch* b, int32_t* job_result, int32_t* set
   if (int r = work_alloc(c, d, w)) return r;
   if (int r = run_stages(c, d, w, 0, ST_COUNT)) return r;
   return finish_results(c, d, w, job_result, set_code, stats);
+}
+
+// ---- committee bitfields over resident index lists ---------------------------
+// include/bgv.h bgv_verify_bits.  The expansion (bgv_bits.hip) runs on the main
+// stream in front of the ordinary pipeline and leaves an on-device bgv_batch in
+// all but name: pk_off / pk_idx in context-owned buffers, everything else the
+// staged (or the caller's device) arrays.
+static_assert(sizeof(bgv_set_src) == sizeof(bits_src) && BGV_MAX_INDEX_LISTS == BITS_MAX_LISTS &&
+                  BGV_SRC_EXPLICIT == BITS_SRC_EXPLICIT,
+              "bits_expand.h mirrors include/bgv.h");
+
+int bgv_index_list_set(bgv_ctx* c, uint32_t id, const uint32_t* idx, uint32_t n) {
+  if (!c || (!idx && n)) return fail(BGV_E_INVALID_ARG, "null argument");
+  if (id >= BGV_MAX_INDEX_LISTS) return fail(BGV_E_INVALID_ARG, "index list %u: ids are below %u", id, (unsigned)BGV_MAX_INDEX_LISTS);
+  for (uint32_t i = 0; i < n; i++)
+    if (idx[i] & 0x80000000u)
+      return fail(BGV_E_INVALID_ARG, "index list %u: entry %u (0x%08x) has bit 31 set (lists hold table rows only)", id, i, idx[i]);
+  HIPCHK(hipSetDevice(c->device));
+  uint32_t* p = nullptr;
+  if (n) {
+    if (hipMalloc((void**)&p, (size_t)n * 4) != hipSuccess) return fail(BGV_E_HIP, "hipMalloc(%zu) failed", (size_t)n * 4);
+    hipError_t e = hipMemcpyAsync(p, idx, (size_t)n * 4, hipMemcpyHostToDevice, c->st);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->st);
+    if (e != hipSuccess) {
+      (void)hipFree(p);
+      return fail(BGV_E_HIP, "index list %u upload: %s", id, hipGetErrorString(e));
+    }
+  }
+  if (c->idx_list[id]) {
+    // a batch of this context that is still in flight (bgv_partial leaves one,
+    // a failed call may) can read the old list from any of the four streams
+    HIPCHK(hipStreamSynchronize(c->st));
+    HIPCHK(hipStreamSynchronize(c->st_hash));
+    HIPCHK(hipStreamSynchronize(c->st_pk));
+    HIPCHK(hipStreamSynchronize(c->st_chk));
+    (void)hipFree(c->idx_list[id]);
+  }
+  c->idx_list[id] = p;
+  c->idx_list_n[id] = n;
+  return BGV_OK;
+}
+
+int bgv_index_list_len(bgv_ctx* c, uint32_t id, uint32_t* n) {
+  if (!c || !n) return fail(BGV_E_INVALID_ARG, "null argument");
+  if (id >= BGV_MAX_INDEX_LISTS) return fail(BGV_E_INVALID_ARG, "index list %u: ids are below %u", id, (unsigned)BGV_MAX_INDEX_LISTS);
+  *n = c->idx_list_n[id];
+  return BGV_OK;
+}
+
+static int bits_check_args(const bgv_bits_batch* b, bool need_sigs) {
+  if (!b) return fail(BGV_E_INVALID_ARG, "batch is NULL");
+  if (!b->job_offsets || (b->n_sets && (!b->src || (need_sigs && (!b->msgs || !b->sigs || !b->sig_len)))))
+    return fail(BGV_E_INVALID_ARG, "missing batch array");
+  if (b->bits_len && !b->bits) return fail(BGV_E_INVALID_ARG, "bits_len > 0 but bits is NULL");
+  if (b->n_indices && !b->pk_indices) return fail(BGV_E_INVALID_ARG, "n_indices > 0 but pk_indices is NULL");
+  if (b->n_raw && !b->raw_pks) return fail(BGV_E_INVALID_ARG, "n_raw > 0 but raw_pks is NULL");
+  return BGV_OK;
+}
+
+// The contract of a host batch, on the copies the device will see: `v` holds
+// host pointers to bits and pk_indices; of the lists only "is set" and the
+// length are looked at.  Fills the key total and the largest job.
+static int bits_check_core(uint32_t n, uint32_t J, const uint32_t* jo, const bits_src* src, const bits_view& v,
+                           uint32_t* total_out, uint32_t* max_job_out) {
+  if (jo[0] != 0 || jo[J] != n) return fail(BGV_E_INVALID_ARG, "job_offsets must span [0, n_sets]");
+  uint32_t max_job = 1;
+  for (uint32_t j = 0; j < J; j++) {
+    if (jo[j + 1] < jo[j]) return fail(BGV_E_INVALID_ARG, "job_offsets not monotone");
+    if (jo[j + 1] - jo[j] > max_job) max_job = jo[j + 1] - jo[j];
+  }
+  uint64_t total = 0;
+  for (uint32_t i = 0; i < n; i++) {
+    const bits_src s = src[i];
+    const bool expl = s.list == BITS_SRC_EXPLICIT;
+    switch (bits_src_check(s, v)) {
+      case BITS_OK: break;
+      case BITS_E_LIST: return fail(BGV_E_INVALID_ARG, "set %u: index list %u is not set", i, s.list);
+      case BITS_E_SPAN:
+        if (expl) return fail(BGV_E_INVALID_ARG, "set %u: off %u + len %u past the %u explicit indices", i, s.off, s.len, v.n_indices);
+        return fail(BGV_E_INVALID_ARG, "set %u: off %u + len %u past the %u entries of list %u", i, s.off, s.len,
+                    bits_list_len(v, s.list), s.list);
+      default:
+        return fail(BGV_E_INVALID_ARG, "set %u: bits_off %u + %u bitfield bytes past bits_len %u", i, s.bits_off, bits_bytes(s.len), v.bits_len);
+    }
+    uint64_t cnt = s.len;
+    if (!expl) {
+      // aggregationBits.intersectValues throws on a length mismatch: a bit above len is one
+      if ((s.len & 7u) && (v.bits[(size_t)s.bits_off + bits_bytes(s.len) - 1] >> (s.len & 7u)))
+        return fail(BGV_E_INVALID_ARG, "set %u: padding bits above len %u are not zero", i, s.len);
+      cnt = 0;
+      const uint32_t words = bits_words(s.len);
+      for (uint32_t w = 0; w < words; w++) cnt += bits_popc(bits_src_word(s, v, w));
+    }
+    if (cnt == 0) return fail(BGV_E_EMPTY_SET, "EMPTY_AGGREGATE_ARRAY (set %u)", i);
+    total += cnt;
+  }
+  if (total > 0xffffffffull) return fail(BGV_E_INVALID_ARG, "the batch's %llu keys do not fit 32 bits", (unsigned long long)total);
+  *total_out = (uint32_t)total;
+  *max_job_out = max_job;
+  return BGV_OK;
+}
+
+int bgv_bits_check(const bgv_bits_batch* b, const uint32_t* list_len) {
+  if (int r = bits_check_args(b, true)) return r;
+  if (!list_len) return fail(BGV_E_INVALID_ARG, "list_len is NULL");
+  if (b->on_device) return BGV_OK;
+  static const uint32_t present = 0;  // a non-NULL stand-in: the check reads no list entry
+  bits_view v;
+  memset(&v, 0, sizeof v);
+  for (uint32_t k = 0; k < BGV_MAX_INDEX_LISTS; k++) {
+    v.list[k] = list_len[k] ? &present : nullptr;
+    v.list_len[k] = list_len[k];
+  }
+  v.bits = b->bits; v.bits_len = b->bits_len; v.pk_indices = b->pk_indices; v.n_indices = b->n_indices;
+  uint32_t total = 0, max_job = 0;
+  return bits_check_core(b->n_sets, b->n_jobs, b->job_offsets, (const bits_src*)b->src, v, &total, &max_job);
+}
+
+// prepare() for a bits batch up to the expanded device view: staging and checks
+// (host batches), early hash maps, raw keys, the expansion.  Leaves d.pk_off /
+// d.pk_idx, c->jo_host and c->pk_total as prepare() does.
+static int bits_front(bgv_ctx* c, const bgv_bits_batch* b, dev_batch& d, bool need_sigs) {
+  if (int r = bits_check_args(b, need_sigs)) return r;
+  const uint32_t n = b->n_sets, J = b->n_jobs;
+  memset(&d, 0, sizeof d);
+  c->busy = c->device >= 0 && c->device < 64 && g_active[c->device].load() >= 2;
+  d.n_sets = n; d.n_jobs = J; d.n_raw = b->n_raw; d.table_n = c->table_n; d.table = c->table;
+  d.span_log2 = 7;
+  c->jo_host.resize((size_t)J + 1);
+  bits_args a;
+  memset(&a, 0, sizeof a);
+  a.n_sets = n;
+  for (uint32_t k = 0; k < BGV_MAX_INDEX_LISTS; k++) { a.v.list[k] = c->idx_list[k]; a.v.list_len[k] = c->idx_list_n[k]; }
+  a.v.bits_len = b->bits_len;
+  a.v.n_indices = b->n_indices;
+  if (int r = ensure_or_release_lines(c, c->bits_off, (size_t)n + 1)) return r;
+  a.pk_off = c->bits_off.p;
+  c->bits_timed = need_sigs && (c->cfg.timing >= 0 ? c->cfg.timing != 0 : n >= 65536);
+  if (!b->on_device) {
+    const uint8_t* raw_dev = nullptr;
+    stage_seg segs[9] = {
+        {b->job_offsets, ((size_t)J + 1) * 4, (const void**)&d.job_off, 0},
+        {b->src, (size_t)n * sizeof(bits_src), (const void**)&a.src, 0},
+        {b->bits, (size_t)b->bits_len, (const void**)&a.v.bits, 0},
+        {b->pk_indices, (size_t)b->n_indices * 4, (const void**)&a.v.pk_indices, 0},
+        {b->msgs, need_sigs ? (size_t)n * 32 : 0, (const void**)&d.msgs, 0},
+        {b->raw_pks, (size_t)b->n_raw * 96, (const void**)&raw_dev, 0},
+        {b->scalars, need_sigs && b->scalars ? (size_t)n * 8 : 0, (const void**)&d.scalars, 0},
+        {b->sigs, need_sigs ? (size_t)n * 192 : 0, (const void**)&d.sigs, 0},
+        {b->sig_len, need_sigs ? (size_t)n * 4 : 0, (const void**)&d.sig_len, 0},
+    };
+    size_t bytes = 0;
+    if (int r = stage_pack(c, segs, 9, bytes)) return r;
+    // the checks read the pinned copy; the key total sizes the expansion and
+    // the gather's grid without a read-back
+    bits_view hv = a.v;
+    hv.bits = c->pin_in + segs[2].off;
+    hv.pk_indices = (const uint32_t*)(c->pin_in + segs[3].off);
+    const uint32_t* jo = (const uint32_t*)(c->pin_in + segs[0].off);
+    uint32_t total = 0, max_job = 1;
+    if (int r = bits_check_core(n, J, jo, (const bits_src*)(c->pin_in + segs[1].off), hv, &total, &max_job)) return r;
+    d.span_log2 = 0;
+    while ((1u << d.span_log2) < max_job && d.span_log2 < 16) d.span_log2++;
+    memcpy(c->jo_host.data(), jo, c->jo_host.size() * 4);
+    c->pk_total = total;
+    if (int r = stage_issue(c, bytes)) return r;
+    // the messages sit in the staging buffer whose copy is in flight on the
+    // main stream: the hash stream waits for it (early_maps, after_staging)
+    if (need_sigs)
+      if (int r = early_maps(c, d, true)) return r;
+    if (!(need_sigs && b->scalars)) d.scalars = nullptr;
+    if (!need_sigs) { d.sigs = nullptr; d.sig_len = nullptr; d.msgs = nullptr; }
+    if (int r = ensure_or_release_lines(c, c->raw_conv, b->n_raw ? b->n_raw : 1)) return r;
+    launch_raw_pks(c->st, raw_dev, c->raw_conv.p, b->n_raw);
+    d.raw_pks = c->raw_conv.p;
+    if (int r = ensure_or_release_lines(c, c->bits_idx, total ? total : 1)) return r;
+    a.pk_idx = c->bits_idx.p;
+    a.cap = total;
+    if (c->bits_timed) HIPCHK(hipEventRecord(c->ev_bits[0], c->st));
+    launch_bits_count(c->st, a);
+    if (n) launch_scan(c->st, a.pk_off, n);
+    launch_bits_expand(c->st, a);
+    if (c->bits_timed) HIPCHK(hipEventRecord(c->ev_bits[1], c->st));
+  } else {
+    d.job_off = b->job_offsets;
+    a.src = (const bits_src*)b->src;
+    a.v.bits = b->bits;
+    a.v.pk_indices = b->pk_indices;
+    d.msgs = b->msgs; d.sigs = b->sigs; d.sig_len = b->sig_len;
+    if (need_sigs)
+      if (int r = early_maps(c, d, false)) return r;
+    if (int r = ensure_or_release_lines(c, c->raw_conv, b->n_raw ? b->n_raw : 1)) return r;
+    launch_raw_pks(c->st, b->raw_pks, c->raw_conv.p, b->n_raw);
+    d.raw_pks = c->raw_conv.p;
+    if (c->bits_timed) HIPCHK(hipEventRecord(c->ev_bits[0], c->st));
+    launch_bits_count(c->st, a);
+    if (n) launch_scan(c->st, a.pk_off, n);
+    HIPCHK(hipGetLastError());
+    // the host needs the job offsets (stats) and the key total (buffer and grid bound)
+    HIPCHK(hipMemcpyAsync(c->jo_host.data(), b->job_offsets, c->jo_host.size() * 4, hipMemcpyDeviceToHost, c->st));
+    c->pk_total = 0;
+    if (n) HIPCHK(hipMemcpyAsync(&c->pk_total, a.pk_off + n, 4, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(hipStreamSynchronize(c->st));
+    if (int r = ensure_or_release_lines(c, c->bits_idx, c->pk_total ? c->pk_total : 1)) return r;
+    a.pk_idx = c->bits_idx.p;
+    a.cap = c->pk_total;
+    launch_bits_expand(c->st, a);
+    if (c->bits_timed) HIPCHK(hipEventRecord(c->ev_bits[1], c->st));
+  }
+  HIPCHK(hipGetLastError());
+  d.pk_off = c->bits_off.p;
+  d.pk_idx = c->bits_idx.p;
+  return 0;
+}
+
+int bgv_verify_bits(bgv_ctx* c, const bgv_bits_batch* b, int32_t* job_result, int32_t* set_code, bgv_stats* stats) {
+  if (!c || !b || (!job_result && b->n_jobs)) return fail(BGV_E_INVALID_ARG, "null argument");
+  c->partial_pending = false;
+  HIPCHK(hipSetDevice(c->device));
+  active_guard ag(c->device);
+  dev_batch d;
+  if (int r = bits_front(c, b, d, true)) return r;
+  if (int r = prepare_layout(c, d, b->scalars, b->scalars && !b->on_device)) return r;
+  dev_work w;
+  if (int r = work_alloc(c, d, w)) return r;
+  if (int r = run_stages(c, d, w, 0, ST_COUNT)) return r;
+  return finish_results(c, d, w, job_result, set_code, stats);
+}
+
+int bgv_bits_expand_ms(bgv_ctx* c, float* ms) {
+  if (!c || !ms) return fail(BGV_E_INVALID_ARG, "null argument");
+  *ms = 0.f;
+  if (!c->bits_timed) return BGV_OK;
+  HIPCHK(hipSetDevice(c->device));
+  HIPCHK(hipEventSynchronize(c->ev_bits[1]));
+  HIPCHK(hipEventElapsedTime(ms, c->ev_bits[0], c->ev_bits[1]));
+  return BGV_OK;
+}
+
+int bgv_debug_bits_expand(bgv_ctx* c, const bgv_bits_batch* b, uint32_t* pk_offsets, uint32_t* pk_indices, uint32_t cap,
+                          uint32_t* total) {
+  if (!c || !b || !pk_offsets || !total || (!pk_indices && cap)) return fail(BGV_E_INVALID_ARG, "null argument");
+  c->partial_pending = false;
+  HIPCHK(hipSetDevice(c->device));
+  dev_batch d;
+  if (int r = bits_front(c, b, d, false)) return r;
+  HIPCHK(hipMemcpyAsync(pk_offsets, d.pk_off, ((size_t)b->n_sets + 1) * 4, hipMemcpyDeviceToHost, c->st));
+  const uint32_t t = c->pk_total;
+  if (t && t <= cap) HIPCHK(hipMemcpyAsync(pk_indices, d.pk_idx, (size_t)t * 4, hipMemcpyDeviceToHost, c->st));
+  HIPCHK(hipStreamSynchronize(c->st));
+  c->staged_pending = false;
+  *total = t;
+  if (t > cap) return fail(BGV_E_INVALID_ARG, "the expansion holds %u indices, pk_indices has room for %u", t, cap);
+  return BGV_OK;
 }
 
 // ---- same-message batches ---------------------------------------------------

@@ -3,6 +3,7 @@
 #pragma once
 #include "pairing.h"
 #include "rng.h"
+#include "bits_expand.h"
 
 namespace bgv {
 
@@ -220,5 +221,19 @@ void launch_sma_classify(hipStream_t st, const sm_view& v);
 void launch_sma_g1_sum(hipStream_t st, const sm_view& v);
 void launch_sma_pk_aff(hipStream_t st, const g1j* pk_set, g1a* out, uint32_t n);
 void launch_sma_retry_gather(hipStream_t st, const sm_retry& r, const g1j* pk_set, g1a* o_pk);
+
+// ---- committee bitfields over resident index lists (bgv_verify_bits, bgv_bits.hip)
+struct bits_args {
+  uint32_t n_sets;
+  const bits_src* src;  // [n_sets]
+  bits_view v;
+  uint32_t* pk_off;     // [n_sets + 1]: per-set key counts, then their scan
+  uint32_t* pk_idx;     // the expansion
+  uint32_t cap;         // entries of pk_idx
+};
+void launch_bits_count(hipStream_t st, const bits_args& a);
+void launch_bits_expand(hipStream_t st, const bits_args& a);
+// exclusive scan of a[0..n) in place, total at a[n] (bgv_kernels.hip k_scan)
+void launch_scan(hipStream_t st, uint32_t* a, uint32_t n);
 
 }  // namespace bgv

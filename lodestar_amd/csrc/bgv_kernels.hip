@@ -1171,6 +1171,8 @@ void launch_hash_maps(hipStream_t st, const dev_batch& b, const dev_work& w) {
   BGV_LAUNCH(k_hash_map, 2u * b.n_sets, b, w);
 }
 
+void launch_scan(hipStream_t st, uint32_t* a, uint32_t n) { hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, st, a, n); }
+
 void launch_prep(hipStream_t st, const dev_batch& b, const dev_work& w) {
   BGV_LAUNCH(k_chunk_count, b.n_sets, b, w);
   if (b.n_sets) hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, st, w.chunk_off, b.n_sets);

@@ -24,6 +24,12 @@
  *                                                bgv_verify_same_message (see "same-message batches" below)
  *   verifySameMessageAgg(ctx, smaBatch) -> Promise<smResult>, verifySameMessageAggSync(ctx, smaBatch) -> smResult
  *                                                bgv_verify_same_message_agg: the sets' keys are aggregates
+ *   setIndexList(ctx, id, Uint32Array)           bgv_index_list_set: a resident index list (an epoch's shuffling,
+ *                                                a sync committee); an empty array drops it
+ *   indexListLen(ctx, id) -> number              bgv_index_list_len
+ *   verifyBits(ctx, bitsBatch) -> Promise<result>, verifyBitsSync(ctx, bitsBatch) -> result
+ *                                                bgv_verify_bits: sets given as (list, window, participation bits)
+ *                                                or as explicit index runs (see "committee bitfields" below)
  *
  * batch = {jobOffsets: Uint32Array, pkOffsets: Uint32Array, pkIndices:
  * Uint32Array, msgs: Uint8Array, sigs: Uint8Array (192 B per set), sigLen:
@@ -255,12 +261,17 @@ static const napi_typedarray_type FIELD_T[N_FIELDS] = {napi_uint32_array, napi_u
                                                        napi_uint8_array,  napi_uint8_array,  napi_uint32_array,
                                                        napi_uint8_array};
 
-enum { K_VERIFY, K_PARTIAL, K_FINISH, K_COMBINE };
+enum { K_VERIFY, K_PARTIAL, K_FINISH, K_COMBINE, K_BITS };
+/* bgv_bits_batch fields (K_BITS) */
+enum { B_JOB, B_SRC, B_BITS, B_PKI, B_MSG, B_SIG, B_LEN, B_RAW, NB_FIELDS };
 
 typedef struct {
   int kind;
   addon_ctx* c;
   bgv_batch b;
+  bgv_bits_batch bb;    /* K_BITS (b.n_jobs / b.n_sets mirror its counts) */
+  uint32_t* src_copy;   /* K_BITS: the sources, copied at call time like the offsets */
+  napi_ref brefs[NB_FIELDS];
   uint8_t miller[576];  /* K_PARTIAL */
   int32_t ok;           /* K_PARTIAL: no job rejected; K_COMBINE: the product is 1 in GT */
   uint8_t* parts;       /* K_COMBINE: a copy of the partials */
@@ -283,6 +294,8 @@ static void free_job_arrays(verify_job* j) {
   free(j->pk_off);
   free(j->job_result);
   free(j->parts);
+  free(j->src_copy);
+  j->src_copy = NULL;
   j->job_off = j->pk_off = NULL;
   j->job_result = NULL;
   j->parts = NULL;
@@ -375,6 +388,7 @@ static void run_verify(verify_job* j) {
         j->status = j->job_result ? bgv_partial_finish(j->c->ctx, j->job_result, &j->stats) : BGV_E_INVALID_ARG;
         break;
       case K_COMBINE: j->status = bgv_combine_final(j->c->ctx, j->parts, j->n_parts, &j->ok); break;
+      case K_BITS: j->status = bgv_verify_bits(j->c->ctx, &j->bb, j->job_result, NULL, &j->stats); break;
       default: j->status = bgv_verify(j->c->ctx, &j->b, j->job_result, NULL, &j->stats); break;
     }
     if (j->status != BGV_OK) snprintf(j->err, sizeof j->err, "bgv error %d: %s", j->status, bgv_last_error());
@@ -440,6 +454,8 @@ static void done_verify(napi_env env, napi_status st, void* data) { /* main thre
   }
   for (int k = 0; k < N_FIELDS; k++)
     if (j->refs[k]) napi_delete_reference(env, j->refs[k]); /* unpin the inputs */
+  for (int k = 0; k < NB_FIELDS; k++)
+    if (j->brefs[k]) napi_delete_reference(env, j->brefs[k]);
   if (j->ctx_ref) napi_delete_reference(env, j->ctx_ref);
   napi_delete_async_work(env, j->work);
   free_job_arrays(j);
@@ -782,6 +798,162 @@ static napi_value VerifySameMessageSync(napi_env env, napi_callback_info info) {
 static napi_value VerifySameMessageAgg(napi_env env, napi_callback_info info) { return sm_async(env, info, 1); }
 static napi_value VerifySameMessageAggSync(napi_env env, napi_callback_info info) { return sm_sync(env, info, 1); }
 
+/* ------------------------------------------------------- committee bitfields
+ * verifyBits(ctx, batch) -> Promise<result>, verifyBitsSync(ctx, batch) -> result (bgv_verify_bits).
+ * batch = {jobOffsets: Uint32Array, src: Uint32Array (4 per set: list, off, len, bitsOff; list 0xffffffff = an
+ * explicit run pkIndices[off .. off + len)), bits: Uint8Array (all bitfields, byte-packed, SSZ bit order),
+ * pkIndices: Uint32Array (keys of the explicit sets), msgs, sigs, sigLen, rawPks? as for verify}.
+ * result as for verify.  jobOffsets and src are copied at call time; the library stages every array into pinned
+ * memory and checks the copy against the lengths taken here, so a caller that mutates its arrays while the work
+ * is queued cannot make the device read past them. */
+static const char* BFIELD[NB_FIELDS] = {"jobOffsets", "src", "bits", "pkIndices", "msgs", "sigs", "sigLen", "rawPks"};
+static const napi_typedarray_type BFIELD_T[NB_FIELDS] = {napi_uint32_array, napi_uint32_array, napi_uint8_array,  napi_uint32_array,
+                                                         napi_uint8_array,  napi_uint8_array,  napi_uint32_array, napi_uint8_array};
+
+static int read_bits_batch(napi_env env, napi_value obj, verify_job* j, int pin) {
+  void* p[NB_FIELDS] = {0};
+  size_t n[NB_FIELDS] = {0};
+  napi_value v[NB_FIELDS];
+  for (int k = 0; k < NB_FIELDS; k++) {
+    bool has = false;
+    napi_has_named_property(env, obj, BFIELD[k], &has);
+    if (!has) {
+      if (k == B_RAW) continue;
+      napi_throw_type_error(env, NULL, "bits batch field missing");
+      return -1;
+    }
+    napi_get_named_property(env, obj, BFIELD[k], &v[k]);
+    if (typed(env, v[k], BFIELD_T[k], &p[k], &n[k])) {
+      napi_throw_type_error(env, NULL, "bits batch field has the wrong typed-array type");
+      return -1;
+    }
+  }
+  if (n[B_JOB] < 1 || n[B_SRC] % 4) {
+    napi_throw_range_error(env, NULL, "jobOffsets needs at least one entry, src four entries per set");
+    return -1;
+  }
+  const size_t n_sets = n[B_SRC] / 4;
+  if (n[B_MSG] < 32ull * n_sets || n[B_SIG] < 192ull * n_sets || n[B_LEN] < n_sets) {
+    napi_throw_range_error(env, NULL, "msgs / sigs / sigLen shorter than the set count");
+    return -1;
+  }
+  if (n_sets > 0xffffffffull || n[B_BITS] > 0xffffffffull || n[B_PKI] > 0xffffffffull) {
+    napi_throw_range_error(env, NULL, "bits batch too large");
+    return -1;
+  }
+  j->job_off = (uint32_t*)malloc(4 * n[B_JOB]);
+  j->src_copy = (uint32_t*)malloc(n[B_SRC] ? 4 * n[B_SRC] : 4);
+  if (!j->job_off || !j->src_copy) {
+    napi_throw_error(env, NULL, "out of memory");
+    return -1;
+  }
+  memcpy(j->job_off, p[B_JOB], 4 * n[B_JOB]);
+  if (n[B_SRC]) memcpy(j->src_copy, p[B_SRC], 4 * n[B_SRC]);
+  if (pin)
+    for (int k = 0; k < NB_FIELDS; k++)
+      if (p[k] && k != B_JOB && k != B_SRC) napi_create_reference(env, v[k], 1, &j->brefs[k]);
+  memset(&j->bb, 0, sizeof j->bb);
+  j->bb.n_sets = (uint32_t)n_sets;
+  j->bb.n_jobs = (uint32_t)(n[B_JOB] - 1);
+  j->bb.job_offsets = j->job_off;
+  j->bb.src = (const bgv_set_src*)j->src_copy;
+  j->bb.bits = (const uint8_t*)p[B_BITS];
+  j->bb.bits_len = (uint32_t)n[B_BITS];
+  j->bb.pk_indices = (const uint32_t*)p[B_PKI];
+  j->bb.n_indices = (uint32_t)n[B_PKI];
+  j->bb.raw_pks = (const uint8_t*)p[B_RAW];
+  j->bb.n_raw = (uint32_t)(n[B_RAW] / 96);
+  j->bb.msgs = (const uint8_t*)p[B_MSG];
+  j->bb.sigs = (const uint8_t*)p[B_SIG];
+  j->bb.sig_len = (const uint32_t*)p[B_LEN];
+  j->bb.scalars = NULL; /* drawn inside the library */
+  j->bb.on_device = 0;
+  j->b.n_jobs = j->bb.n_jobs; /* result_object sizes `results` from it */
+  j->b.n_sets = j->bb.n_sets;
+  return 0;
+}
+
+static napi_value VerifyBits(napi_env env, napi_callback_info info) {
+  size_t argc = 2;
+  napi_value a[2];
+  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, a, NULL, NULL));
+  addon_ctx* c = get_ctx(env, a[0]);
+  if (!c) return NULL;
+  verify_job* j = (verify_job*)calloc(1, sizeof *j);
+  j->c = c;
+  j->kind = K_BITS;
+  if (read_bits_batch(env, a[1], j, 1)) {
+    for (int k = 0; k < NB_FIELDS; k++)
+      if (j->brefs[k]) napi_delete_reference(env, j->brefs[k]);
+    free_job_arrays(j);
+    free(j);
+    return NULL;
+  }
+  j->job_result = (int32_t*)calloc(j->b.n_jobs ? j->b.n_jobs : 1, 4);
+  return queue_job(env, a[0], j, "bgv_verify_bits");
+}
+
+static napi_value VerifyBitsSync(napi_env env, napi_callback_info info) {
+  size_t argc = 2;
+  napi_value a[2];
+  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, a, NULL, NULL));
+  addon_ctx* c = get_ctx(env, a[0]);
+  if (!c) return NULL;
+  verify_job j;
+  memset(&j, 0, sizeof j);
+  j.c = c;
+  j.kind = K_BITS;
+  if (read_bits_batch(env, a[1], &j, 0)) {
+    free_job_arrays(&j);
+    return NULL;
+  }
+  j.job_result = (int32_t*)calloc(j.b.n_jobs ? j.b.n_jobs : 1, 4);
+  run_verify(&j);
+  napi_value r = NULL;
+  if (j.status != BGV_OK) napi_throw_error(env, NULL, j.err);
+  else r = result_object(env, &j);
+  free_job_arrays(&j);
+  return r;
+}
+
+static napi_value SetIndexList(napi_env env, napi_callback_info info) {
+  size_t argc = 3;
+  napi_value a[3];
+  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, a, NULL, NULL));
+  addon_ctx* c = get_ctx(env, a[0]);
+  if (!c) return NULL;
+  uint32_t id = 0;
+  void* data = NULL;
+  size_t len = 0;
+  if (argc < 3 || napi_get_value_uint32(env, a[1], &id) != napi_ok || typed(env, a[2], napi_uint32_array, &data, &len) ||
+      len > 0xffffffffull) {
+    napi_throw_type_error(env, NULL, "setIndexList(ctx, id, Uint32Array)");
+    return NULL;
+  }
+  pthread_mutex_lock(&c->mu); /* waits for the context's batch in flight */
+  const int st = bgv_index_list_set(c->ctx, id, (const uint32_t*)data, (uint32_t)len);
+  pthread_mutex_unlock(&c->mu);
+  if (st != BGV_OK) return throw_bgv(env, st);
+  return NULL;
+}
+
+static napi_value IndexListLen(napi_env env, napi_callback_info info) {
+  size_t argc = 2;
+  napi_value a[2];
+  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, a, NULL, NULL));
+  addon_ctx* c = get_ctx(env, a[0]);
+  if (!c) return NULL;
+  uint32_t id = 0, n = 0;
+  NAPI_CALL(env, napi_get_value_uint32(env, a[1], &id));
+  pthread_mutex_lock(&c->mu);
+  const int st = bgv_index_list_len(c->ctx, id, &n);
+  pthread_mutex_unlock(&c->mu);
+  if (st != BGV_OK) return throw_bgv(env, st);
+  napi_value r;
+  NAPI_CALL(env, napi_create_uint32(env, n, &r));
+  return r;
+}
+
 static napi_value Init(napi_env env, napi_value exports) {
   napi_property_descriptor d[] = {
       {"abiVersion", NULL, AbiVersion, NULL, NULL, NULL, napi_enumerable, NULL},
@@ -801,6 +973,10 @@ static napi_value Init(napi_env env, napi_value exports) {
       {"verifySameMessageSync", NULL, VerifySameMessageSync, NULL, NULL, NULL, napi_enumerable, NULL},
       {"verifySameMessageAgg", NULL, VerifySameMessageAgg, NULL, NULL, NULL, napi_enumerable, NULL},
       {"verifySameMessageAggSync", NULL, VerifySameMessageAggSync, NULL, NULL, NULL, napi_enumerable, NULL},
+      {"setIndexList", NULL, SetIndexList, NULL, NULL, NULL, napi_enumerable, NULL},
+      {"indexListLen", NULL, IndexListLen, NULL, NULL, NULL, napi_enumerable, NULL},
+      {"verifyBits", NULL, VerifyBits, NULL, NULL, NULL, napi_enumerable, NULL},
+      {"verifyBitsSync", NULL, VerifyBitsSync, NULL, NULL, NULL, napi_enumerable, NULL},
   };
   if (napi_define_properties(env, exports, sizeof d / sizeof d[0], d) != napi_ok) return NULL;
   return exports;

@@ -100,6 +100,9 @@ const CONTEXTS_PER_DEVICE = 3;
 // (verifyBlocksSignatures.ts:30-47, sleep(0) every 8 blocks) coalesce
 const MAX_QUIET_WAITS = 8;
 const RAW_BIT = 0x80000000;
+const MAX_INDEX_LISTS = 8; // BGV_MAX_INDEX_LISTS
+const SRC_EXPLICIT = 0xffffffff; // BGV_SRC_EXPLICIT
+const POPCOUNT8 = Uint8Array.from({length: 256}, (_, v) => { let c = 0; for (let x = v; x; x >>= 1) c += x & 1; return c; });
 // the G1 generator, 96-byte uncompressed, and the identity signature: the priority context's sizing job
 const G1_GENERATOR_96 = Uint8Array.from(Buffer.from(
   "17f1d3a73197d7942695638c4fa9ac0fc3688c4f9774b905a14e3a3f171bac586c55e83ff97a1aeffb3af00adb22c6bb" +
@@ -130,6 +133,16 @@ function chunkifyMaximizeChunkSize(arr, minPerChunk) {
 // made before queueing so a bad call cannot fail a batch it shares
 function checkSets(sets) {
   for (const s of sets) {
+    if (s.type === "committee") {
+      const c = s.committee;
+      if (!c || !s.bits || !(c.list >= 0 && c.list < MAX_INDEX_LISTS)) throw Error("committee set without a committee, bits or a valid list id");
+      if (!(c.offset >= 0) || !(c.length >= 0) || c.offset + c.length > 0xffffffff || s.bits.length !== ((c.length + 7) >> 3)) {
+        throw Error(`committee set: ${s.bits.length} bitfield bytes for ${c.length} members`);
+      }
+      if (!s.bits.some((b) => b !== 0)) throw Error("EMPTY_AGGREGATE_ARRAY"); // intersectValues gives no index
+      if (!s.signingRoot || s.signingRoot.length !== 32) throw Error("signingRoot must be 32 bytes");
+      continue;
+    }
     const pks = s.type === "single" ? [s.pubkey] : s.pubkeys;
     if (!pks || pks.length === 0 || pks.some((pk) => !pk)) throw Error("EMPTY_AGGREGATE_ARRAY");
     for (const pk of pks) if (pk.raw && pk.raw.length !== 96) throw Error("raw pubkeys must be 96-byte uncompressed");
@@ -139,8 +152,73 @@ function checkSets(sets) {
 
 function aggregatedPubkeysCount(sets) {
   let n = 0;
-  for (const s of sets) if (s.type === "aggregate") n += s.pubkeys.length;
+  for (const s of sets) {
+    if (s.type === "aggregate") n += s.pubkeys.length;
+    else if (s.type === "committee") for (const b of s.bits) n += POPCOUNT8[b];
+  }
   return n;
+}
+
+function hasCommitteeSets(jobs) {
+  return jobs.some((j) => j.some((s) => s.type === "committee"));
+}
+
+// jobs -> the arrays of include/bgv.h bgv_bits_batch: single and aggregate sets
+// become explicit sources over pkIndices, committee sets
+// ({type: "committee", committee: {list, offset, length}, bits, signingRoot, signature})
+// list sources over the byte-packed bitfields.  src holds 4 words per set:
+// list, off, len, bitsOff.
+function encodeJobsBits(jobs) {
+  let n = 0, nIdx = 0, nRaw = 0, nBits = 0;
+  for (const j of jobs) {
+    n += j.length;
+    for (const s of j) {
+      if (s.type === "committee") { nBits += s.bits.length; continue; }
+      const pks = s.type === "single" ? [s.pubkey] : s.pubkeys;
+      if (!pks || pks.length === 0) throw Error("EMPTY_AGGREGATE_ARRAY");
+      nIdx += pks.length;
+      for (const pk of pks) if (pk.raw) nRaw++;
+    }
+  }
+  const jobOffsets = new Uint32Array(jobs.length + 1);
+  const src = new Uint32Array(4 * n);
+  const bits = new Uint8Array(nBits);
+  const pkIndices = new Uint32Array(nIdx);
+  const rawPks = new Uint8Array(Math.max(nRaw, 1) * 96);
+  const msgs = new Uint8Array(Math.max(n, 1) * 32);
+  const sigs = new Uint8Array(Math.max(n, 1) * 192);
+  const sigLen = new Uint32Array(Math.max(n, 1));
+  let i = 0, x = 0, r = 0, b = 0;
+  jobs.forEach((job, k) => {
+    for (const s of job) {
+      if (s.type === "committee") {
+        const c = s.committee;
+        if (s.bits.length !== ((c.length + 7) >> 3)) throw Error(`committee set: ${s.bits.length} bitfield bytes for ${c.length} members`);
+        src.set([c.list, c.offset, c.length, b], 4 * i);
+        bits.set(s.bits, b);
+        b += s.bits.length;
+      } else {
+        const pks = s.type === "single" ? [s.pubkey] : s.pubkeys;
+        src.set([SRC_EXPLICIT, x, pks.length, 0], 4 * i);
+        for (const pk of pks) {
+          if (pk.raw) { pkIndices[x++] = (RAW_BIT | r) >>> 0; rawPks.set(pk.raw, 96 * r++); } else pkIndices[x++] = pk.index >>> 0;
+        }
+      }
+      msgs.set(s.signingRoot, 32 * i);
+      sigLen[i] = s.signature.length;
+      if (s.signature.length === 96 || s.signature.length === 192) sigs.set(s.signature, 192 * i);
+      i++;
+    }
+    jobOffsets[k + 1] = i;
+  });
+  return {jobOffsets, src, bits, pkIndices, msgs, sigs, sigLen, rawPks};
+}
+
+// The routing rule of both classes: a device batch that holds a committee set
+// goes through bgv_verify_bits; any other batch takes exactly the path it took before.
+function verifyJobs(ctx, jobSets, sync = false) {
+  if (hasCommitteeSets(jobSets)) return (sync ? addon.verifyBitsSync : addon.verifyBits)(ctx, encodeJobsBits(jobSets));
+  return (sync ? addon.verifySync : addon.verify)(ctx, encodeJobs(jobSets));
 }
 
 // jobs (arrays of sets) -> the SoA batch of include/bgv.h bgv_batch.  Two
@@ -474,6 +552,14 @@ class BlsGpuVerifier {
     for (const c of this.allContexts()) addon.pubkeysSet(c, firstIndex, bytes, format);
   }
 
+  // A resident index list (an epoch's shuffling, a sync committee) into every
+  // context, like the pubkey table (bgv_index_list_set); an empty array drops
+  // it.  Committee sets name it by committee.list.  Each context's call waits
+  // for that context's batch in flight.
+  setIndexList(id, indices) {
+    for (const c of this.allContexts()) addon.setIndexList(c, id, indices);
+  }
+
   // sizes the priority context's work buffers for a full job (128 sets) at
   // construction, so a verifyOnMainThread call never frees and regrows them
   // (a hipFree synchronises the device: it would wait for the bulk contexts'
@@ -653,9 +739,10 @@ class BlsGpuVerifier {
     this.prioBusy++;
     const t0 = now();
     try {
-      const batch = encodeJobs([sets]);
+      const bits = hasCommitteeSets([sets]);
+      const batch = bits ? encodeJobsBits([sets]) : encodeJobs([sets]);
       const t1 = now();
-      const pending = addon.verify(this.prio, batch);
+      const pending = bits ? addon.verifyBits(this.prio, batch) : addon.verify(this.prio, batch);
       this.lastPriorityIssue = {encodeMs: t1 - t0, queueMs: now() - t1};
       const res = await pending;
       this.recordWork([{sets}], res);
@@ -676,7 +763,7 @@ class BlsGpuVerifier {
   verifySignatureSetsSync(sets) {
     if (this.closed) throw new QueueError();
     checkSets(sets);
-    const res = addon.verifySync(this.prio || this.ctx, encodeJobs([sets]));
+    const res = verifyJobs(this.prio || this.ctx, [sets], true);
     this.recordWork([{sets}], res);
     const o = jobOutcome(res.results[0]);
     if (!o.ok) throw o.error;
@@ -801,9 +888,11 @@ class BlsGpuVerifier {
       m.lodestar_bls_thread_pool_job_groups_started_total += 1;
       m.lodestar_bls_thread_pool_jobs_started_total += jobs.length;
       m.lodestar_bls_thread_pool_sig_sets_started_total += started;
-      const res = devs.length === 1
-        ? await addon.verify(this.ctxs[devs[0]], encodeJobs(jobs.map((j) => j.sets)))
-        : await this.verifySharded(jobs.map((j) => j.sets), devs);
+      // bgv_partial takes no bitfields: a batch with a committee set goes whole to one context
+      const jobSets = jobs.map((j) => j.sets);
+      const res = devs.length === 1 || hasCommitteeSets(jobSets)
+        ? await verifyJobs(this.ctxs[devs[0]], jobSets)
+        : await this.verifySharded(jobSets, devs);
       this.recordWork(jobs, res);
       jobs.forEach((job, k) => {
         const o = jobOutcome(res.results[k]);
@@ -931,12 +1020,16 @@ class BlsGpuSingleThreadVerifier {
     addon.pubkeysSet(this.ctx, firstIndex, bytes, format);
   }
 
+  setIndexList(id, indices) {
+    addon.setIndexList(this.ctx, id, indices);
+  }
+
   async verifySignatureSets(sets) {
     if (this.closed) throw new QueueError();
     this.metrics.lodestar_bls_aggregated_pubkeys_total += aggregatedPubkeysCount(sets);
     checkSets(sets); // getAggregatedPubkey's checks (utils.ts:5-16)
     const t0 = now();
-    const res = addon.verifySync(this.ctx, encodeJobs([sets]));
+    const res = verifyJobs(this.ctx, [sets], true);
     const o = jobOutcome(res.results[0]);
     if (!o.ok) throw o.error; // only runs without exceptions are timed, as in the reference
     observe(this.metrics.lodestar_bls_thread_pool_main_thread_time_seconds, (now() - t0) / 1e3);
@@ -976,6 +1069,6 @@ class BlsGpuSingleThreadVerifier {
 
 module.exports = {
   addon, BlsGpuVerifier, BlsGpuSingleThreadVerifier, QueueError, sourceHash, checkBuildId, chunkifyMaximizeChunkSize, encodeJobs, checkSets, shardJobs, jobWork,
-  encodeSameMessage, mergeSameMessage, checkSameMessage, encodeSameMessageAgg, checkAggregateSameMessage,
+  encodeJobsBits, hasCommitteeSets, encodeSameMessage, mergeSameMessage, checkSameMessage, encodeSameMessageAgg, checkAggregateSameMessage,
   MAX_BUFFERED_SIGS, MAX_BUFFER_WAIT_MS, MAX_JOBS_CAN_ACCEPT_WORK, SHARD_MIN_SETS, PRIORITY_CUS, RESERVED_CAP, CONTEXTS_PER_DEVICE,
 };

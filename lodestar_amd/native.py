@@ -53,7 +53,13 @@ EXPORTS = [
     "bgv_bench_mad", "bgv_debug_fp_ops", "bgv_debug_g2_decode",
     "bgv_verify_same_message", "bgv_sm_check", "bgv_debug_same_message",
     "bgv_verify_same_message_agg", "bgv_sma_check", "bgv_debug_same_message_agg",
+    "bgv_index_list_set", "bgv_index_list_len", "bgv_verify_bits", "bgv_bits_check", "bgv_debug_bits_expand",
+    "bgv_bits_expand_ms",
 ]
+MAX_INDEX_LISTS = 8
+SRC_EXPLICIT = 0xFFFFFFFF
+# bgv_set_src as a numpy record: (list, off, len, bits_off), 16 B per set
+SET_SRC_DTYPE = np.dtype([("list", "<u4"), ("off", "<u4"), ("len", "<u4"), ("bits_off", "<u4")])
 FP_OPS_N = 13
 
 
@@ -143,6 +149,28 @@ class BgvSmaBatch(ctypes.Structure):
         ("group_offsets", ctypes.c_void_p),
         ("pk_offsets", ctypes.c_void_p),
         ("pk_indices", ctypes.c_void_p),
+        ("raw_pks", ctypes.c_void_p),
+        ("n_raw", ctypes.c_uint32),
+        ("msgs", ctypes.c_void_p),
+        ("sigs", ctypes.c_void_p),
+        ("sig_len", ctypes.c_void_p),
+        ("scalars", ctypes.c_void_p),
+        ("on_device", ctypes.c_uint32),
+    ]
+
+
+class BgvBitsBatch(ctypes.Structure):
+    """bgv_bits_batch (include/bgv.h): sets given as committee bitfields over
+    resident index lists, or as explicit index runs."""
+    _fields_ = [
+        ("n_sets", ctypes.c_uint32),
+        ("n_jobs", ctypes.c_uint32),
+        ("job_offsets", ctypes.c_void_p),
+        ("src", ctypes.c_void_p),
+        ("bits", ctypes.c_void_p),
+        ("bits_len", ctypes.c_uint32),
+        ("pk_indices", ctypes.c_void_p),
+        ("n_indices", ctypes.c_uint32),
         ("raw_pks", ctypes.c_void_p),
         ("n_raw", ctypes.c_uint32),
         ("msgs", ctypes.c_void_p),
@@ -290,6 +318,12 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
             "bgv_sma_check": ([ctypes.POINTER(BgvSmaBatch)], ctypes.c_int),
             "bgv_debug_same_message_agg": ([P, ctypes.POINTER(BgvSmaBatch), P, P, ctypes.POINTER(BgvSmStats), P, P, P, P],
                                            ctypes.c_int),
+            "bgv_index_list_set": ([P, u32, P, u32], ctypes.c_int),
+            "bgv_index_list_len": ([P, u32, ctypes.POINTER(u32)], ctypes.c_int),
+            "bgv_verify_bits": ([P, ctypes.POINTER(BgvBitsBatch), P, P, ctypes.POINTER(BgvStats)], ctypes.c_int),
+            "bgv_bits_check": ([ctypes.POINTER(BgvBitsBatch), P], ctypes.c_int),
+            "bgv_debug_bits_expand": ([P, ctypes.POINTER(BgvBitsBatch), P, P, u32, ctypes.POINTER(u32)], ctypes.c_int),
+            "bgv_bits_expand_ms": ([P, ctypes.POINTER(ctypes.c_float)], ctypes.c_int),
         }
         for name, (args, res) in sig.items():
             fn = getattr(lib, name)
@@ -341,6 +375,51 @@ def sma_check(arrays: dict, on_device: bool = False) -> tuple[int, str]:
     lib = load_library()
     b = Device.make_sma_batch(arrays, on_device, sync_inputs=False)
     st = lib.bgv_sma_check(ctypes.byref(b))
+    return st, ("" if st == BGV_OK else lib.bgv_last_error().decode())
+
+
+def _count(a, width: int = 1) -> int:
+    """entries of a numpy array / torch tensor / None (bytes / width for u8 views)"""
+    if a is None:
+        return 0
+    n = a.size if isinstance(a, np.ndarray) else a.numel()
+    return int(n) // width
+
+
+def make_bits_batch(arrays: dict, on_device: bool = False, sync_inputs: bool = True) -> BgvBitsBatch:
+    """arrays as verifier.encode_jobs_bits returns them: src is a SET_SRC_DTYPE
+    record array (or an (n_sets, 4) uint32 array / tensor), bits a uint8 array;
+    bits_len and n_indices default to the arrays' sizes"""
+    b = BgvBitsBatch()
+    b.n_sets = int(arrays["n_sets"])
+    b.n_jobs = int(arrays["n_jobs"])
+    b.job_offsets = _ptr(arrays["job_offsets"])
+    b.src = _ptr(arrays["src"])
+    b.bits = _ptr(arrays.get("bits"))
+    b.bits_len = int(arrays["bits_len"]) if "bits_len" in arrays else _count(arrays.get("bits"))
+    b.pk_indices = _ptr(arrays.get("pk_indices"))
+    b.n_indices = int(arrays["n_indices"]) if "n_indices" in arrays else _count(arrays.get("pk_indices"))
+    b.raw_pks = _ptr(arrays.get("raw_pks"))
+    b.n_raw = int(arrays.get("n_raw", 0))
+    b.msgs = _ptr(arrays.get("msgs"))
+    b.sigs = _ptr(arrays.get("sigs"))
+    b.sig_len = _ptr(arrays.get("sig_len"))
+    b.scalars = _ptr(arrays.get("scalars"))
+    b.on_device = 1 if on_device else 0
+    if on_device and sync_inputs:
+        _sync_producers(arrays)
+    return b
+
+
+def bits_check(arrays: dict, list_len, on_device: bool = False) -> tuple[int, str]:
+    """bgv_bits_check: the host-side contract of bgv_verify_bits, without a
+    device.  list_len: the lengths of the index lists (0: not set).  Returns
+    (status, bgv_last_error() text); the text is empty for BGV_OK."""
+    lib = load_library()
+    b = make_bits_batch(arrays, on_device, sync_inputs=False)
+    ll = np.zeros(MAX_INDEX_LISTS, np.uint32)
+    ll[: len(list_len)] = np.asarray(list_len, np.uint32)
+    st = lib.bgv_bits_check(ctypes.byref(b), ll.ctypes.data)
     return st, ("" if st == BGV_OK else lib.bgv_last_error().decode())
 
 
@@ -535,6 +614,50 @@ class Device:
                                                         sg.ctypes.data, hg.ctypes.data))
         return {"set_valid": ok[:n].astype(bool), "set_code": sc[:n], "pk_set": ps[:n], "p_group": pg[:G],
                 "s_group": sg[:G], "h_group": hg[:G], "stats": self.last_sm_stats.as_dict()}
+
+    # ------------------------------------------- committee bitfields (bgv_verify_bits)
+    def index_list_set(self, list_id: int, indices) -> None:
+        """bgv_index_list_set: replace resident index list list_id (an empty one drops it)"""
+        arr = np.ascontiguousarray(indices, dtype=np.uint32)
+        self._check(self.lib.bgv_index_list_set(self.h, list_id, arr.ctypes.data if arr.size else None, arr.size))
+
+    def index_list_len(self, list_id: int) -> int:
+        n = ctypes.c_uint32()
+        self._check(self.lib.bgv_index_list_len(self.h, list_id, ctypes.byref(n)))
+        return n.value
+
+    make_bits_batch = staticmethod(make_bits_batch)
+
+    def verify_bits(self, arrays: dict, on_device: bool = False, want_set_codes: bool = True, sync_inputs: bool = True):
+        """bgv_verify_bits: (job_result int32[n_jobs], set_code int32[n_sets] | None), as verify()"""
+        b = make_bits_batch(arrays, on_device, sync_inputs)
+        jr = np.zeros(max(b.n_jobs, 1), dtype=np.int32)
+        sc = np.zeros(max(b.n_sets, 1), dtype=np.int32) if want_set_codes else None
+        self._check(self.lib.bgv_verify_bits(self.h, ctypes.byref(b), jr.ctypes.data,
+                                             sc.ctypes.data if sc is not None else None, ctypes.byref(self.last_stats)))
+        return jr[: b.n_jobs], (sc[: b.n_sets] if sc is not None else None)
+
+    def debug_bits_expand(self, arrays: dict, on_device: bool = False, cap: int | None = None):
+        """bgv_debug_bits_expand (test only): (pk_offsets uint32[n_sets + 1], pk_indices uint32[total]).
+        cap: room for the indices (default: found by a first call)"""
+        b = make_bits_batch(arrays, on_device)
+        po = np.zeros(b.n_sets + 1, np.uint32)
+        total = ctypes.c_uint32()
+        if cap is None:
+            st = self.lib.bgv_debug_bits_expand(self.h, ctypes.byref(b), po.ctypes.data, None, 0, ctypes.byref(total))
+            if st != BGV_OK and not (st == BGV_E_INVALID_ARG and total.value > 0):
+                self._check(st)
+            cap = total.value
+        idx = np.zeros(max(cap, 1), np.uint32)
+        self._check(self.lib.bgv_debug_bits_expand(self.h, ctypes.byref(b), po.ctypes.data, idx.ctypes.data, cap,
+                                                   ctypes.byref(total)))
+        return po, idx[: total.value]
+
+    def bits_expand_ms(self) -> float:
+        """device time of the last verify_bits' expansion kernels (timed contexts; else 0)"""
+        ms = ctypes.c_float()
+        self._check(self.lib.bgv_bits_expand_ms(self.h, ctypes.byref(ms)))
+        return ms.value
 
     def partial(self, arrays: dict, on_device: bool = False, sync_inputs: bool = True):
         """bgv_partial: (miller576 bytes, set codes, provisional job results

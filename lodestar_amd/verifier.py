@@ -101,6 +101,7 @@ def error_for_code(code: int) -> BlsError:
 class SignatureSetType(str, enum.Enum):
     single = "single"
     aggregate = "aggregate"
+    committee = "committee"
 
 
 @dataclass(frozen=True)
@@ -118,6 +119,17 @@ class PublicKey:
         return PublicKey(raw=bytes(b))
 
 
+@dataclass(frozen=True)
+class CommitteeRef:
+    """A window of a resident index list (bgv_index_list_set): entries
+    [offset, offset + length) of list ``list_id``, e.g. one committee's slice of
+    an epoch shuffling, or the whole sync committee."""
+
+    list_id: int
+    offset: int
+    length: int
+
+
 @dataclass
 class VerifySignatureOpts:
     batchable: bool = False
@@ -131,6 +143,8 @@ class ISignatureSet:
     signature: bytes
     pubkey: PublicKey | None = None
     pubkeys: list[PublicKey] = field(default_factory=list)
+    committee: CommitteeRef | None = None  # type committee: the keys are the committee members whose bit is set
+    bits: bytes | None = None              # ceil(length / 8) bytes, SSZ bit order
 
 
 def create_single_signature_set_from_components(pubkey: PublicKey, signing_root: bytes, signature: bytes) -> ISignatureSet:
@@ -143,9 +157,24 @@ def create_aggregate_signature_set_from_components(pubkeys, signing_root: bytes,
     return ISignatureSet(SignatureSetType.aggregate, bytes(signing_root), bytes(signature), pubkeys=list(pubkeys))
 
 
+def create_committee_signature_set_from_components(committee: CommitteeRef, bits: bytes, signing_root: bytes,
+                                                   signature: bytes) -> ISignatureSet:
+    """An aggregate set whose keys are given as (committee, participation bits)
+    instead of indices: what the reference holds before
+    aggregationBits.intersectValues(committeeIndices) (cache/epochContext.ts:620-623,
+    block/processSyncCommittee.ts:89).  The device expands it (bgv_verify_bits)."""
+    return ISignatureSet(SignatureSetType.committee, bytes(signing_root), bytes(signature), committee=committee,
+                         bits=bytes(bits))
+
+
+def _popcount(b: bytes) -> int:
+    return bin(int.from_bytes(b, "little")).count("1") if b else 0
+
+
 def get_aggregated_pubkeys_count(sets) -> int:
-    """chain/bls/utils.ts:18-26"""
-    return sum(len(s.pubkeys) for s in sets if s.type == SignatureSetType.aggregate)
+    """chain/bls/utils.ts:18-26; a committee set counts its set bits"""
+    return sum(len(s.pubkeys) if s.type == SignatureSetType.aggregate else _popcount(s.bits)
+               for s in sets if s.type != SignatureSetType.single)
 
 
 def chunkify_maximize_chunk_size(arr: list, min_per_chunk: int) -> list[list]:
@@ -258,6 +287,90 @@ def encode_jobs(jobs: list[list[ISignatureSet]], scalars: np.ndarray | None = No
     return out
 
 
+def has_committee_sets(jobs) -> bool:
+    return any(s.type == SignatureSetType.committee for job in jobs for s in job)
+
+
+def encode_jobs_bits(jobs: list[list[ISignatureSet]], scalars: np.ndarray | None = None) -> dict:
+    """Flatten jobs of sets into the arrays of bgv_bits_batch (include/bgv.h):
+    single and aggregate sets become explicit sources over pk_indices, committee
+    sets list sources over the packed bitfields.  Raises BlsError like encode_jobs."""
+    job_off = [0]
+    idx: list[int] = []
+    raw: list[bytes] = []
+    raw_pos: dict[bytes, int] = {}
+    bits = bytearray()
+    n = sum(len(j) for j in jobs)
+    src = np.zeros(max(n, 1), dtype=native.SET_SRC_DTYPE)
+    msgs = np.zeros((max(n, 1), 32), dtype=np.uint8)
+    sigs = np.zeros((max(n, 1), 192), dtype=np.uint8)
+    sig_len = np.zeros(max(n, 1), dtype=np.uint32)
+    i = 0
+    for job in jobs:
+        for s in job:
+            if s.type == SignatureSetType.committee:
+                c = s.committee
+                if len(s.bits) != (c.length + 7) // 8:
+                    raise BlsError(f"committee set: {len(s.bits)} bitfield bytes for {c.length} members")
+                src[i] = (c.list_id, c.offset, c.length, len(bits))
+                bits += s.bits
+            else:
+                pks = [s.pubkey] if s.type == SignatureSetType.single else s.pubkeys
+                if len(pks) == 0:
+                    raise BlsError("EMPTY_AGGREGATE_ARRAY")
+                src[i] = (native.SRC_EXPLICIT, len(idx), len(pks), 0)
+                for pk in pks:
+                    if pk.index is not None:
+                        idx.append(pk.index)
+                    else:
+                        r = pk.raw if len(pk.raw) == 96 else _decompress_raw48(pk.raw)
+                        if r not in raw_pos:
+                            raw_pos[r] = len(raw)
+                            raw.append(r)
+                        idx.append(0x80000000 | raw_pos[r])
+            if len(s.signingRoot) != 32:
+                raise BlsError("signingRoot must be 32 bytes")
+            msgs[i] = np.frombuffer(s.signingRoot, dtype=np.uint8)
+            sl = len(s.signature)
+            sig_len[i] = sl
+            if sl in (96, 192):
+                sigs[i, :sl] = np.frombuffer(s.signature, dtype=np.uint8)
+            i += 1
+        job_off.append(i)
+    return {
+        "n_sets": n,
+        "n_jobs": len(jobs),
+        "job_offsets": np.array(job_off, dtype=np.uint32),
+        "src": src,
+        "bits": np.frombuffer(bytes(bits), dtype=np.uint8).copy() if bits else np.zeros(1, np.uint8),
+        "bits_len": len(bits),
+        "pk_indices": np.array(idx if idx else [0], dtype=np.uint32),
+        "n_indices": len(idx),
+        "raw_pks": np.frombuffer(b"".join(raw), dtype=np.uint8).copy() if raw else None,
+        "n_raw": len(raw),
+        "msgs": msgs,
+        "sigs": sigs,
+        "sig_len": sig_len,
+        "scalars": scalars,
+    }
+
+
+def encode_device_batch(jobs: list[list[ISignatureSet]], scalars: np.ndarray | None = None) -> tuple[bool, dict]:
+    """The routing rule of both verifiers: a device batch that holds a committee
+    set goes through bgv_verify_bits (True, encode_jobs_bits arrays); any other
+    batch takes exactly the path it took before (False, encode_jobs arrays)."""
+    if has_committee_sets(jobs):
+        return True, encode_jobs_bits(jobs, scalars)
+    return False, encode_jobs(jobs, scalars)
+
+
+def verify_device_batch(device, jobs: list[list[ISignatureSet]], scalars: np.ndarray | None = None):
+    """encode_device_batch + the matching device call: job results as Device.verify returns them"""
+    use_bits, arrays = encode_device_batch(jobs, scalars)
+    call = device.verify_bits if use_bits else device.verify
+    return call(arrays, want_set_codes=False)[0]
+
+
 def _decompress_raw48(b: bytes) -> bytes:
     raise BlsError("raw compressed pubkeys must be added to the table (PubkeyTable.add_pubkey)")
 
@@ -269,6 +382,17 @@ def check_sets(sets: list[ISignatureSet]) -> None:
     root is 32 bytes.  Pubkey indices past the table are reported per set by
     the device (BGV_INDEX_RANGE rejects only that job)."""
     for s in sets:
+        if s.type == SignatureSetType.committee:
+            c = s.committee
+            if c is None or s.bits is None or not (0 <= c.list_id < native.MAX_INDEX_LISTS):
+                raise BlsError("committee set without a committee, bits or a valid list id")
+            if c.offset < 0 or c.length < 0 or c.offset + c.length > 0xFFFFFFFF or len(s.bits) != (c.length + 7) // 8:
+                raise BlsError(f"committee set: {len(s.bits)} bitfield bytes for {c.length} members")
+            if not any(s.bits):  # intersectValues gives no index: PublicKey.aggregate throws
+                raise BlsError("EMPTY_AGGREGATE_ARRAY")
+            if len(s.signingRoot) != 32:
+                raise BlsError("signingRoot must be 32 bytes")
+            continue
         pks = [s.pubkey] if s.type == SignatureSetType.single else s.pubkeys
         if s.type == SignatureSetType.aggregate and len(pks) == 0:
             raise BlsError("EMPTY_AGGREGATE_ARRAY")
@@ -665,6 +789,18 @@ class BlsGpuVerifier:
         self._sm = SameMessageQueue(self._run_same_message, self._exec, max_sets_per_device_batch)
         self._sma = SameMessageQueue(self._run_same_message_agg, self._exec, max_sets_per_device_batch)
 
+    def set_index_list(self, list_id: int, indices) -> None:
+        """Upload a resident index list (an epoch's shuffling, a sync committee)
+        to every context, like the pubkey table (bgv_index_list_set); an empty
+        list drops it.  Committee sets refer to it by CommitteeRef.list_id."""
+        arr = np.ascontiguousarray(indices, dtype=np.uint32)
+        for k, d in enumerate(self.devices):
+            with self._dev_locks[k]:
+                d.index_list_set(list_id, arr)
+        if self.prio is not None:
+            with self._prio_lock:
+                self.prio.index_list_set(list_id, arr)
+
     # -- IBlsVerifier ---------------------------------------------------
     def can_accept_work(self) -> bool:
         """multithread/index.ts:143-149.  A queued job joins the next device
@@ -897,10 +1033,10 @@ class BlsGpuVerifier:
         """verifyOnMainThread's device batch on the priority context"""
         t0 = time.perf_counter()
         try:
-            arrays = encode_jobs([sets], self._scalars(len(sets)))
+            use_bits, arrays = encode_device_batch([sets], self._scalars(len(sets)))
             with self._prio_lock:
                 t1 = time.perf_counter()
-                jr, _ = self.prio.verify(arrays, want_set_codes=False)
+                jr, _ = (self.prio.verify_bits if use_bits else self.prio.verify)(arrays, want_set_codes=False)
                 self._record(self.prio.last_stats, time.perf_counter() - t1)
         except Exception as e:  # noqa: BLE001 -- a device error rejects the call
             return e
@@ -943,6 +1079,8 @@ class BlsGpuVerifier:
         if not jobs:
             return []
         devs = self._spread_contexts() if devs is None else list(devs)
+        if len(devs) > 1 and has_committee_sets(jobs):
+            devs = devs[:1]  # bgv_partial takes no bitfields: the batch goes whole to one context
         if len(devs) > 1:
             refs = [sum(1 if s.type == SignatureSetType.single else len(s.pubkeys) for s in j) for j in jobs]
             caps = [RESERVED_CAP if self._ctx_dev[d] == 0 and self.prio_reserved else 1.0 for d in devs]
@@ -956,10 +1094,10 @@ class BlsGpuVerifier:
         if len(live) == 1:
             d, ids = live[0]
             try:
-                arrays = encode_jobs(jobs, self._scalars(sum(len(j) for j in jobs)))
+                use_bits, arrays = encode_device_batch(jobs, self._scalars(sum(len(j) for j in jobs)))
                 with self._dev_locks[d]:
                     t0 = time.perf_counter()
-                    jr, _ = self.devices[d].verify(arrays, want_set_codes=False)
+                    jr, _ = (self.devices[d].verify_bits if use_bits else self.devices[d].verify)(arrays, want_set_codes=False)
                     self._record(self.devices[d].last_stats, time.perf_counter() - t0)
             except Exception as e:  # noqa: BLE001 -- a device error rejects the package (index.ts:386-393)
                 return [e] * len(jobs)
@@ -1055,7 +1193,7 @@ class BlsGpuSingleThreadVerifier:
         self.metrics["aggregated_pubkeys_total"] += get_aggregated_pubkeys_count(sets)
         check_sets(sets)  # getAggregatedPubkey's checks (utils.ts:5-16)
         t0 = time.perf_counter()
-        jr, _ = self.device.verify(encode_jobs([sets]), want_set_codes=False)
+        jr = verify_device_batch(self.device, [sets])
         r = BlsGpuVerifier._verdict(int(jr[0]))
         if isinstance(r, Exception):
             raise r  # only runs without exceptions are timed, as in the reference
@@ -1082,6 +1220,10 @@ class BlsGpuSingleThreadVerifier:
             return []
         check_aggregate_same_message(sets, message)
         return run_same_message_agg_calls(self.device, [(sets, message)], None, self.metrics)[0]
+
+    def set_index_list(self, list_id: int, indices) -> None:
+        """bgv_index_list_set on this verifier's context (see BlsGpuVerifier.set_index_list)"""
+        self.device.index_list_set(list_id, np.ascontiguousarray(indices, dtype=np.uint32))
 
     def can_accept_work(self) -> bool:
         return True

@@ -464,6 +464,7 @@ int bgv_verify_bits(bgv_ctx* ctx, const bgv_bits_batch* batch, int32_t* job_resu
  * read. */
 int bgv_bits_check(const bgv_bits_batch* batch, const uint32_t* list_len /* [BGV_MAX_INDEX_LISTS] */);
 /* test-only: the expansion alone; msgs, sigs, sig_len and scalars are not read.
+ * Always the full expansion: resident sums (below) are ignored.
  * pk_offsets[n_sets + 1] and *total (host memory) are always written; the
  * indices are copied to pk_indices (host memory, cap entries) when total <= cap,
  * else the call fails with BGV_E_INVALID_ARG. */
@@ -473,6 +474,85 @@ int bgv_debug_bits_expand(bgv_ctx* ctx, const bgv_bits_batch* batch, uint32_t* p
  * bgv_verify_bits on a context that records stage timings (bgv_cfg.timing = 1,
  * or a batch of >= 65,536 sets); 0 otherwise. */
 int bgv_bits_expand_ms(bgv_ctx* ctx, float* ms);
+
+/* ---- key sums for bitfield sets: window sum minus absent members ------------
+ * On mainnet nearly every bit of a committee's bitfield is set, so the gather of
+ * bgv_verify_bits reads almost the whole window of the list.  With the prefix
+ * sums of a list resident, S[k] = sum of table[L[j]] over j < k (k = 0 .. n),
+ * a set's aggregate key is
+ *     PK = S[off + len] - S[off] - sum of table[L[off + j]] over the ABSENT j,
+ * two reads and one addition for the window plus one addition per absent
+ * member.  Additive to ABI 4; nothing changes for a context that never asks.
+ *
+ * bgv_index_list_sums(ctx, id, 1) builds the n + 1 sums of list `id` on the
+ * device from the table rows as they are now (once per epoch, when a shuffling
+ * or a sync committee is installed); enable = 0 drops them.  Stored form:
+ * Jacobian, 144 B per entry (a 2^20-entry list: 151 MB per context), so the
+ * build needs no inversion.  BGV_E_INVALID_ARG for a list that is not set;
+ * BGV_E_TABLE_RANGE when an entry is at or past the current table count (the
+ * list stays usable without sums).  Identity rows add nothing; equal
+ * neighbours, a row beside its negation and a prefix that is the identity are
+ * all exact (complete addition throughout).
+ * Sums are never stale: bgv_index_list_set on a list drops that list's sums;
+ * a bgv_pubkeys_set or bgv_gen_keys that writes any row below the table count
+ * (a rewrite) drops the sums of EVERY list; pure appends keep them (every entry
+ * of a list with sums was below the count when they were built).  The caller
+ * asks again.  A dropped buffer is freed only after every stream of the context
+ * has drained.  Sums are per context, like the lists and the table.
+ *
+ * The rule (one function, bits_complement in csrc/bits_expand.h, shared by the
+ * host check and the kernels): with pop the set bits inside len and absent =
+ * len - pop, a list set takes the complement path iff its list has sums and
+ * absent + 2 < pop (the 2: the window's two reads and one addition cost what
+ * two gathered keys cost).  Explicit sets, sources that fail the span checks
+ * and sets of lists without sums take the direct path as before.  A complement
+ * set with no absent member gathers no key at all; BGV_E_EMPTY_SET stays a
+ * rule on pop.  job_result, set_code and bgv_stats are those of the direct path
+ * (pubkeys_aggregated stays the participating keys; an identity aggregate is
+ * BGV_SET_PK_IS_INFINITY).  Same-message entries and bgv_partial do not use sums.
+ *
+ * When it pays (tools/bench_bits_sums.py; one MI355X,
+ * host-resident batches, a context with sums against one without in the same
+ * process, alternating): at the C4 range-sync segment (100,352 sets) the gather
+ * stage falls from 14.8 to 3.3 ms at 100% participation and from 15.1 to 4.2 ms
+ * at 99%, where 1% of the participating keys are still read.  The pubkey chain
+ * does not gate a lone batch, so the call gains less: 39.6 -> 37.9 ms at 100%,
+ * 39.7 -> 39.1 ms at 99% and 39.2 -> 38.6 ms at 90%, each beyond both paths'
+ * run-to-run spread, through a shorter hash kernel.  With three batches in
+ * flight the 99% shape takes 31.6 instead of 36.2 ms per batch.  At 60% and 50%
+ * participation, at one epoch (3,136 sets) and at a 64-set gossip batch the two
+ * contexts are within the baseline's spread: no shape measured is slower.  The
+ * build takes 9.2 ms for a 2^20-entry list and 2.2 ms for a 512-entry list.  Not
+ * measured: on-device batches, the callers' side.                             */
+int bgv_index_list_sums(bgv_ctx* ctx, uint32_t list_id, uint32_t enable);
+int bgv_index_list_has_sums(bgv_ctx* ctx, uint32_t list_id, uint32_t* has);
+/* Device time (ms, HIP events around the scan kernels) of the context's last
+ * successful bgv_index_list_sums(.., 1); 0 before the first. */
+int bgv_index_list_sums_ms(bgv_ctx* ctx, float* ms);
+/* Path counters of the last bgv_verify_bits on the context: sets on the
+ * complement path, participating keys (sum of pop and explicit lengths) and
+ * the keys the gather read. */
+typedef struct bgv_bits_path {
+  uint32_t sets_complement, keys_expanded, keys_gathered;
+} bgv_bits_path;
+int bgv_bits_path_stats(bgv_ctx* ctx, bgv_bits_path* out);
+/* Host-only plan (no device, no context): bgv_bits_check's checks, then the
+ * rule against list_has_sums[BGV_MAX_INDEX_LISTS] (NULL: no list has sums).
+ * path[i] = 1 for a complement set (path may be NULL); *keys_gathered the keys
+ * the gather would read.  The arrays of an on-device batch are not read (path
+ * untouched, *keys_gathered = 0). */
+int bgv_bits_plan(const bgv_bits_batch* batch, const uint32_t* list_len, const uint8_t* list_has_sums,
+                  uint8_t* path /* [n_sets] or NULL */, uint64_t* keys_gathered);
+/* test-only: the aggregate key of every set before scaling, through the
+ * expansion, the rule and the gather of bgv_verify_bits: pk_agg96[n_sets][96] in
+ * the layout of bgv_debug.pk_agg (all-zero for the identity or a rejected
+ * key), path[n_sets], pk_code[n_sets] (0, BGV_SET_PK_IS_INFINITY or
+ * BGV_SET_INDEX_RANGE).  msgs, sigs, sig_len and scalars are not read.  Any
+ * output may be NULL. */
+int bgv_debug_bits_keys(bgv_ctx* ctx, const bgv_bits_batch* batch, uint8_t* pk_agg96, uint8_t* path, int32_t* pk_code);
+/* test-only: entries S[first .. first + n) of a list's sums as affine 96 B
+ * (x || y big-endian), all-zero for the identity. */
+int bgv_debug_index_list_sums(bgv_ctx* ctx, uint32_t list_id, uint32_t first, uint32_t n, uint8_t* out96);
 
 /* Multi-GPU partials: run the batch up to, but excluding, the
  * final exponentiation and return this shard's Miller product (576 B, 12

@@ -141,7 +141,17 @@ struct bgv_ctx {
   // resident index lists (bgv_index_list_set) and the expansion of bgv_verify_bits
   uint32_t* idx_list[BGV_MAX_INDEX_LISTS] = {};
   uint32_t idx_list_n[BGV_MAX_INDEX_LISTS] = {};
-  dbuf<uint32_t> bits_off, bits_idx;  // pk_off[n_sets + 1], pk_idx[key total]
+  dbuf<uint32_t> bits_off, bits_idx;  // pk_off[n_sets + 1] (+ 2 tally words with sums), pk_idx[gathered keys]
+  // resident prefix sums (bgv_index_list_sums): n + 1 Jacobian entries per list
+  g1j* idx_sums[BGV_MAX_INDEX_LISTS] = {};
+  float sums_build_ms = 0.f;  // device time of the last build (ev_bits around its kernels)
+  uint32_t idx_list_max[BGV_MAX_INDEX_LISTS] = {};  // largest entry of the list (range check of the sums)
+  dbuf<pk_window> bits_win;           // per-set windows of the last bits batch (contexts with sums)
+  bool bits_any_sums = false;         // the last bits batch ran with sums resident
+  bool bits_on_device = false;        // ... and was an on-device batch (its path counters live in HBM)
+  bgv_bits_path bits_path = {};       // path counters of the last bgv_verify_bits
+  uint32_t bits_n = 0;                // sets of the last bits batch
+  uint32_t bits_extra_chunks = 0;     // window chunks of the last bits batch (an upper bound for on-device batches)
   hipEvent_t ev_bits[2] = {};         // around the expansion kernels (timed runs)
   bool bits_timed = false;
   // microbench scratch
@@ -315,7 +325,9 @@ int bgv_close(bgv_ctx* c) {
   for (auto& e : c->ev_bits) (void)hipEventDestroy(e);
   for (auto& l : c->idx_list)
     if (l) (void)hipFree(l);
-  c->bits_off.release(); c->bits_idx.release();
+  for (auto& l : c->idx_sums)
+    if (l) (void)hipFree(l);
+  c->bits_off.release(); c->bits_idx.release(); c->bits_win.release();
   if (c->pin_in) (void)hipHostFree(c->pin_in);
   if (c->pin_out) (void)hipHostFree(c->pin_out);
   if (c->table) (void)hipFree(c->table);
@@ -339,6 +351,30 @@ int bgv_close(bgv_ctx* c) {
   (void)hipStreamDestroy(c->st_chk);
   delete c;
   return BGV_OK;
+}
+
+// every stream of the context: a batch still in flight (bgv_partial leaves
+// one, a failed call may) can read a list or its sums from any of the four
+static int ctx_drain(bgv_ctx* c) {
+  HIPCHK(hipStreamSynchronize(c->st));
+  HIPCHK(hipStreamSynchronize(c->st_hash));
+  HIPCHK(hipStreamSynchronize(c->st_pk));
+  HIPCHK(hipStreamSynchronize(c->st_chk));
+  return 0;
+}
+
+// drop the resident sums of one list / of every list, after the streams drained
+static int sums_drop(bgv_ctx* c, uint32_t id) {
+  if (!c->idx_sums[id]) return 0;
+  if (int r = ctx_drain(c)) return r;
+  (void)hipFree(c->idx_sums[id]);
+  c->idx_sums[id] = nullptr;
+  return 0;
+}
+static int sums_drop_all(bgv_ctx* c) {
+  for (uint32_t k = 0; k < BGV_MAX_INDEX_LISTS; k++)
+    if (int r = sums_drop(c, k)) return r;
+  return 0;
 }
 
 static int table_reserve(bgv_ctx* c, uint32_t n) {
@@ -385,6 +421,8 @@ int bgv_pubkeys_set(bgv_ctx* c, uint32_t first, uint32_t n, const uint8_t* data,
   for (uint32_t i = 0; i < n; i++)
     if (c->pk_codes_host[i] != 0)  // PublicKey.fromBytes throws: nothing is stored
       return fail(BGV_E_BAD_PUBKEY, "pubkey %u: BLST_ERROR: %s", first + i, bgv_set_code_name(c->pk_codes_host[i]));
+  if (first < c->table_n)  // a rewrite: no prefix sum may outlive the rows it was built from
+    if (int r = sums_drop_all(c)) return r;
   HIPCHK(hipMemcpyAsync(c->table + first, c->pk_tmp.p, (size_t)n * sizeof(g1a), hipMemcpyDeviceToDevice, c->st));
   HIPCHK(hipStreamSynchronize(c->st));
   if (first + n > c->table_n) c->table_n = first + n;
@@ -1047,14 +1085,81 @@ int bgv_index_list_set(bgv_ctx* c, uint32_t id, const uint32_t* idx, uint32_t n)
   if (c->idx_list[id]) {
     // a batch of this context that is still in flight (bgv_partial leaves one,
     // a failed call may) can read the old list from any of the four streams
-    HIPCHK(hipStreamSynchronize(c->st));
-    HIPCHK(hipStreamSynchronize(c->st_hash));
-    HIPCHK(hipStreamSynchronize(c->st_pk));
-    HIPCHK(hipStreamSynchronize(c->st_chk));
+    if (int r = ctx_drain(c)) { if (p) (void)hipFree(p); return r; }
     (void)hipFree(c->idx_list[id]);
+    if (c->idx_sums[id]) (void)hipFree(c->idx_sums[id]);  // sums of the old list: the caller asks again
+    c->idx_sums[id] = nullptr;
   }
   c->idx_list[id] = p;
   c->idx_list_n[id] = n;
+  uint32_t mx = 0;
+  for (uint32_t i = 0; i < n; i++) mx = idx[i] > mx ? idx[i] : mx;
+  c->idx_list_max[id] = mx;
+  return BGV_OK;
+}
+
+int bgv_index_list_sums(bgv_ctx* c, uint32_t id, uint32_t enable) {
+  if (!c) return fail(BGV_E_INVALID_ARG, "null argument");
+  if (id >= BGV_MAX_INDEX_LISTS) return fail(BGV_E_INVALID_ARG, "index list %u: ids are below %u", id, (unsigned)BGV_MAX_INDEX_LISTS);
+  HIPCHK(hipSetDevice(c->device));
+  if (!enable) return sums_drop(c, id);
+  if (!c->idx_list[id]) return fail(BGV_E_INVALID_ARG, "index list %u is not set", id);
+  const uint32_t n = c->idx_list_n[id];
+  if (c->idx_list_max[id] >= c->table_n)
+    return fail(BGV_E_TABLE_RANGE, "index list %u holds row %u, the table has %u rows: a prefix over a row that does not exist cannot be built",
+                id, c->idx_list_max[id], c->table_n);
+  if (int r = sums_drop(c, id)) return r;  // rebuilt from the rows as they are now
+  g1j *S = nullptr, *tmp = nullptr;
+  const size_t entries = (size_t)n + 1, n_tmp = sums_tmp_entries(n);
+  if (hipMalloc((void**)&S, entries * sizeof(g1j)) != hipSuccess) return fail(BGV_E_HIP, "hipMalloc(%zu) failed", entries * sizeof(g1j));
+  if (hipMalloc((void**)&tmp, n_tmp * sizeof(g1j)) != hipSuccess) {
+    (void)hipFree(S);
+    return fail(BGV_E_HIP, "hipMalloc(%zu) failed", n_tmp * sizeof(g1j));
+  }
+  // timed with the expansion's event pair: no batch is in flight on this stream here
+  c->bits_timed = false;
+  c->sums_build_ms = 0.f;
+  (void)hipEventRecord(c->ev_bits[0], c->st);
+  launch_list_sums(c->st, c->table, c->table_n, c->idx_list[id], n, S, tmp);
+  hipError_t e = hipGetLastError();
+  (void)hipEventRecord(c->ev_bits[1], c->st);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->st);
+  if (e == hipSuccess) (void)hipEventElapsedTime(&c->sums_build_ms, c->ev_bits[0], c->ev_bits[1]);
+  (void)hipFree(tmp);
+  if (e != hipSuccess) {
+    (void)hipFree(S);
+    return fail(BGV_E_HIP, "index list %u sums: %s", id, hipGetErrorString(e));
+  }
+  c->idx_sums[id] = S;
+  return BGV_OK;
+}
+
+int bgv_index_list_sums_ms(bgv_ctx* c, float* ms) {
+  if (!c || !ms) return fail(BGV_E_INVALID_ARG, "null argument");
+  *ms = c->sums_build_ms;
+  return BGV_OK;
+}
+
+int bgv_index_list_has_sums(bgv_ctx* c, uint32_t id, uint32_t* has) {
+  if (!c || !has) return fail(BGV_E_INVALID_ARG, "null argument");
+  if (id >= BGV_MAX_INDEX_LISTS) return fail(BGV_E_INVALID_ARG, "index list %u: ids are below %u", id, (unsigned)BGV_MAX_INDEX_LISTS);
+  *has = c->idx_sums[id] ? 1u : 0u;
+  return BGV_OK;
+}
+
+int bgv_debug_index_list_sums(bgv_ctx* c, uint32_t id, uint32_t first, uint32_t n, uint8_t* out96) {
+  if (!c || (!out96 && n)) return fail(BGV_E_INVALID_ARG, "null argument");
+  if (id >= BGV_MAX_INDEX_LISTS || !c->idx_sums[id]) return fail(BGV_E_INVALID_ARG, "index list %u has no sums", id);
+  if ((uint64_t)first + n > (uint64_t)c->idx_list_n[id] + 1)
+    return fail(BGV_E_INVALID_ARG, "entries [%u, %llu) past the %llu sums of list %u", first, (unsigned long long)first + n,
+                (unsigned long long)c->idx_list_n[id] + 1, id);
+  if (n == 0) return BGV_OK;
+  HIPCHK(hipSetDevice(c->device));
+  if (int r = c->gen_out.ensure((size_t)n * 96)) return r;
+  launch_sums_export(c->st, c->idx_sums[id] + first, c->gen_out.p, n);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(out96, c->gen_out.p, (size_t)n * 96, hipMemcpyDeviceToHost, c->st));
+  HIPCHK(hipStreamSynchronize(c->st));
   return BGV_OK;
 }
 
@@ -1077,16 +1182,24 @@ static int bits_check_args(const bgv_bits_batch* b, bool need_sigs) {
 
 // The contract of a host batch, on the copies the device will see: `v` holds
 // host pointers to bits and pk_indices; of the lists only "is set" and the
-// length are looked at.  Fills the key total and the largest job.
+// length are looked at, and of their sums only "has sums".  Fills the key
+// total, the largest job and what the complement rule (bits_expand.h) makes of
+// the batch: the sets it sends down the complement path (path, may be NULL)
+// and the keys the gather then reads.
+struct bits_plan_out {
+  uint32_t total = 0, max_job = 1;
+  uint32_t gathered = 0, n_complement = 0;
+};
 static int bits_check_core(uint32_t n, uint32_t J, const uint32_t* jo, const bits_src* src, const bits_view& v,
-                           uint32_t* total_out, uint32_t* max_job_out) {
+                           bits_plan_out* out, uint8_t* path) {
   if (jo[0] != 0 || jo[J] != n) return fail(BGV_E_INVALID_ARG, "job_offsets must span [0, n_sets]");
   uint32_t max_job = 1;
   for (uint32_t j = 0; j < J; j++) {
     if (jo[j + 1] < jo[j]) return fail(BGV_E_INVALID_ARG, "job_offsets not monotone");
     if (jo[j + 1] - jo[j] > max_job) max_job = jo[j + 1] - jo[j];
   }
-  uint64_t total = 0;
+  uint64_t total = 0, gathered = 0;
+  uint32_t n_complement = 0;
   for (uint32_t i = 0; i < n; i++) {
     const bits_src s = src[i];
     const bool expl = s.list == BITS_SRC_EXPLICIT;
@@ -1111,33 +1224,47 @@ static int bits_check_core(uint32_t n, uint32_t J, const uint32_t* jo, const bit
     }
     if (cnt == 0) return fail(BGV_E_EMPTY_SET, "EMPTY_AGGREGATE_ARRAY (set %u)", i);
     total += cnt;
+    const bool cm = bits_src_complement(s, v, (uint32_t)cnt);
+    gathered += cm ? s.len - cnt : cnt;
+    n_complement += cm ? 1u : 0u;
+    if (path) path[i] = cm ? 1 : 0;
   }
   if (total > 0xffffffffull) return fail(BGV_E_INVALID_ARG, "the batch's %llu keys do not fit 32 bits", (unsigned long long)total);
-  *total_out = (uint32_t)total;
-  *max_job_out = max_job;
+  out->total = (uint32_t)total;
+  out->max_job = max_job;
+  out->gathered = (uint32_t)gathered;
+  out->n_complement = n_complement;
   return BGV_OK;
 }
 
-int bgv_bits_check(const bgv_bits_batch* b, const uint32_t* list_len) {
+int bgv_bits_plan(const bgv_bits_batch* b, const uint32_t* list_len, const uint8_t* list_has_sums, uint8_t* path,
+                  uint64_t* keys_gathered) {
+  if (keys_gathered) *keys_gathered = 0;
   if (int r = bits_check_args(b, true)) return r;
   if (!list_len) return fail(BGV_E_INVALID_ARG, "list_len is NULL");
   if (b->on_device) return BGV_OK;
-  static const uint32_t present = 0;  // a non-NULL stand-in: the check reads no list entry
+  static const uint32_t present = 0;  // a non-NULL stand-in: the check reads no list entry and no sum
   bits_view v;
   memset(&v, 0, sizeof v);
   for (uint32_t k = 0; k < BGV_MAX_INDEX_LISTS; k++) {
     v.list[k] = list_len[k] ? &present : nullptr;
     v.list_len[k] = list_len[k];
+    v.sums[k] = list_len[k] && list_has_sums && list_has_sums[k] ? &present : nullptr;
   }
   v.bits = b->bits; v.bits_len = b->bits_len; v.pk_indices = b->pk_indices; v.n_indices = b->n_indices;
-  uint32_t total = 0, max_job = 0;
-  return bits_check_core(b->n_sets, b->n_jobs, b->job_offsets, (const bits_src*)b->src, v, &total, &max_job);
+  bits_plan_out po;
+  if (int r = bits_check_core(b->n_sets, b->n_jobs, b->job_offsets, (const bits_src*)b->src, v, &po, path)) return r;
+  if (keys_gathered) *keys_gathered = po.gathered;
+  return BGV_OK;
 }
+
+int bgv_bits_check(const bgv_bits_batch* b, const uint32_t* list_len) { return bgv_bits_plan(b, list_len, nullptr, nullptr, nullptr); }
 
 // prepare() for a bits batch up to the expanded device view: staging and checks
 // (host batches), early hash maps, raw keys, the expansion.  Leaves d.pk_off /
 // d.pk_idx, c->jo_host and c->pk_total as prepare() does.
-static int bits_front(bgv_ctx* c, const bgv_bits_batch* b, dev_batch& d, bool need_sigs) {
+// use_sums = false: the full expansion on the direct path whatever is resident.
+static int bits_front(bgv_ctx* c, const bgv_bits_batch* b, dev_batch& d, bool need_sigs, bool use_sums = true) {
   if (int r = bits_check_args(b, need_sigs)) return r;
   const uint32_t n = b->n_sets, J = b->n_jobs;
   memset(&d, 0, sizeof d);
@@ -1148,11 +1275,31 @@ static int bits_front(bgv_ctx* c, const bgv_bits_batch* b, dev_batch& d, bool ne
   bits_args a;
   memset(&a, 0, sizeof a);
   a.n_sets = n;
-  for (uint32_t k = 0; k < BGV_MAX_INDEX_LISTS; k++) { a.v.list[k] = c->idx_list[k]; a.v.list_len[k] = c->idx_list_n[k]; }
+  bool any_sums = false;
+  for (uint32_t k = 0; k < BGV_MAX_INDEX_LISTS; k++) {
+    a.v.list[k] = c->idx_list[k]; a.v.list_len[k] = c->idx_list_n[k];
+    a.v.sums[k] = use_sums ? c->idx_sums[k] : nullptr;
+    any_sums = any_sums || a.v.sums[k];
+  }
   a.v.bits_len = b->bits_len;
   a.v.n_indices = b->n_indices;
-  if (int r = ensure_or_release_lines(c, c->bits_off, (size_t)n + 1)) return r;
+  // with sums resident: two tally words behind the scan's total (bgv_internal.h bits_args)
+  if (int r = ensure_or_release_lines(c, c->bits_off, (size_t)n + 3)) return r;
   a.pk_off = c->bits_off.p;
+  c->bits_any_sums = any_sums;
+  c->bits_on_device = b->on_device != 0;
+  c->bits_path = {};
+  c->bits_extra_chunks = 0;
+  c->bits_n = n;
+  if (any_sums) {
+    if (int r = ensure_or_release_lines(c, c->bits_win, n ? n : 1)) return r;
+    a.win = c->bits_win.p;
+    if (b->on_device) {
+      a.tally = a.pk_off + n + 1;
+      HIPCHK(hipMemsetAsync(a.tally, 0, 8, c->st));
+    }
+    d.win = c->bits_win.p;
+  }
   c->bits_timed = need_sigs && (c->cfg.timing >= 0 ? c->cfg.timing != 0 : n >= 65536);
   if (!b->on_device) {
     const uint8_t* raw_dev = nullptr;
@@ -1175,12 +1322,17 @@ static int bits_front(bgv_ctx* c, const bgv_bits_batch* b, dev_batch& d, bool ne
     hv.bits = c->pin_in + segs[2].off;
     hv.pk_indices = (const uint32_t*)(c->pin_in + segs[3].off);
     const uint32_t* jo = (const uint32_t*)(c->pin_in + segs[0].off);
-    uint32_t total = 0, max_job = 1;
-    if (int r = bits_check_core(n, J, jo, (const bits_src*)(c->pin_in + segs[1].off), hv, &total, &max_job)) return r;
+    bits_plan_out po;
+    if (int r = bits_check_core(n, J, jo, (const bits_src*)(c->pin_in + segs[1].off), hv, &po, nullptr)) return r;
+    const uint32_t total = po.gathered;  // what the expansion holds and the gather reads
     d.span_log2 = 0;
-    while ((1u << d.span_log2) < max_job && d.span_log2 < 16) d.span_log2++;
+    while ((1u << d.span_log2) < po.max_job && d.span_log2 < 16) d.span_log2++;
     memcpy(c->jo_host.data(), jo, c->jo_host.size() * 4);
-    c->pk_total = total;
+    c->pk_total = po.total;
+    c->bits_path.sets_complement = po.n_complement;
+    c->bits_path.keys_expanded = po.total;
+    c->bits_path.keys_gathered = po.gathered;
+    c->bits_extra_chunks = po.n_complement;
     if (int r = stage_issue(c, bytes)) return r;
     // the messages sit in the staging buffer whose copy is in flight on the
     // main stream: the hash stream waits for it (early_maps, after_staging)
@@ -1216,12 +1368,18 @@ static int bits_front(bgv_ctx* c, const bgv_bits_batch* b, dev_batch& d, bool ne
     HIPCHK(hipGetLastError());
     // the host needs the job offsets (stats) and the key total (buffer and grid bound)
     HIPCHK(hipMemcpyAsync(c->jo_host.data(), b->job_offsets, c->jo_host.size() * 4, hipMemcpyDeviceToHost, c->st));
-    c->pk_total = 0;
-    if (n) HIPCHK(hipMemcpyAsync(&c->pk_total, a.pk_off + n, 4, hipMemcpyDeviceToHost, c->st));
+    // ... with sums resident the gathered total and the participating total together
+    uint32_t tot[2] = {0, 0};
+    if (n) HIPCHK(hipMemcpyAsync(tot, a.pk_off + n, any_sums ? 8 : 4, hipMemcpyDeviceToHost, c->st));
     HIPCHK(hipStreamSynchronize(c->st));
-    if (int r = ensure_or_release_lines(c, c->bits_idx, c->pk_total ? c->pk_total : 1)) return r;
+    const uint32_t gathered = tot[0];
+    c->pk_total = any_sums ? tot[1] : tot[0];
+    c->bits_path.keys_expanded = c->pk_total;
+    c->bits_path.keys_gathered = gathered;
+    c->bits_extra_chunks = any_sums ? n : 0u;  // the complement sets are counted on the device only
+    if (int r = ensure_or_release_lines(c, c->bits_idx, gathered ? gathered : 1)) return r;
     a.pk_idx = c->bits_idx.p;
-    a.cap = c->pk_total;
+    a.cap = gathered;
     launch_bits_expand(c->st, a);
     if (c->bits_timed) HIPCHK(hipEventRecord(c->ev_bits[1], c->st));
   }
@@ -1231,6 +1389,26 @@ static int bits_front(bgv_ctx* c, const bgv_bits_batch* b, dev_batch& d, bool ne
   return 0;
 }
 
+// prepare_layout() for a bits batch: the pipeline variant goes by the set
+// count as ever; the gather's grid bound by the keys it reads, plus one window
+// chunk per complement set: sum ceil(k_i / 32) + windows <= gathered / 32 + n + windows
+static int bits_layout(bgv_ctx* c, dev_batch& d, const uint64_t* scalars, bool scalars_staged) {
+  if (int r = prepare_layout(c, d, scalars, scalars_staged)) return r;
+  if (d.win) d.chunk_bound = c->bits_path.keys_gathered / PK_CHUNK + d.n_sets + c->bits_extra_chunks;
+  return 0;
+}
+
+int bgv_bits_path_stats(bgv_ctx* c, bgv_bits_path* out) {
+  if (!c || !out) return fail(BGV_E_INVALID_ARG, "null argument");
+  if (c->bits_any_sums && c->bits_on_device) {  // counted by k_bits_count: fetched when asked for
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipMemcpyAsync(&c->bits_path.sets_complement, c->bits_off.p + c->bits_n + 2, 4, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(hipStreamSynchronize(c->st));
+  }
+  *out = c->bits_path;
+  return BGV_OK;
+}
+
 int bgv_verify_bits(bgv_ctx* c, const bgv_bits_batch* b, int32_t* job_result, int32_t* set_code, bgv_stats* stats) {
   if (!c || !b || (!job_result && b->n_jobs)) return fail(BGV_E_INVALID_ARG, "null argument");
   c->partial_pending = false;
@@ -1238,7 +1416,7 @@ int bgv_verify_bits(bgv_ctx* c, const bgv_bits_batch* b, int32_t* job_result, in
   active_guard ag(c->device);
   dev_batch d;
   if (int r = bits_front(c, b, d, true)) return r;
-  if (int r = prepare_layout(c, d, b->scalars, b->scalars && !b->on_device)) return r;
+  if (int r = bits_layout(c, d, b->scalars, b->scalars && !b->on_device)) return r;
   dev_work w;
   if (int r = work_alloc(c, d, w)) return r;
   if (int r = run_stages(c, d, w, 0, ST_COUNT)) return r;
@@ -1261,7 +1439,7 @@ int bgv_debug_bits_expand(bgv_ctx* c, const bgv_bits_batch* b, uint32_t* pk_offs
   c->partial_pending = false;
   HIPCHK(hipSetDevice(c->device));
   dev_batch d;
-  if (int r = bits_front(c, b, d, false)) return r;
+  if (int r = bits_front(c, b, d, false, false)) return r;
   HIPCHK(hipMemcpyAsync(pk_offsets, d.pk_off, ((size_t)b->n_sets + 1) * 4, hipMemcpyDeviceToHost, c->st));
   const uint32_t t = c->pk_total;
   if (t && t <= cap) HIPCHK(hipMemcpyAsync(pk_indices, d.pk_idx, (size_t)t * 4, hipMemcpyDeviceToHost, c->st));
@@ -1269,6 +1447,33 @@ int bgv_debug_bits_expand(bgv_ctx* c, const bgv_bits_batch* b, uint32_t* pk_offs
   c->staged_pending = false;
   *total = t;
   if (t > cap) return fail(BGV_E_INVALID_ARG, "the expansion holds %u indices, pk_indices has room for %u", t, cap);
+  return BGV_OK;
+}
+
+int bgv_debug_bits_keys(bgv_ctx* c, const bgv_bits_batch* b, uint8_t* pk_agg96, uint8_t* path, int32_t* pk_code) {
+  if (!c || !b) return fail(BGV_E_INVALID_ARG, "null argument");
+  c->partial_pending = false;
+  HIPCHK(hipSetDevice(c->device));
+  dev_batch d;
+  if (int r = bits_front(c, b, d, false)) return r;
+  if (int r = bits_layout(c, d, nullptr, false)) return r;  // the scaling needs scalars: drawn on the device
+  dev_work w;
+  if (int r = work_alloc(c, d, w)) return r;
+  const uint32_t n = d.n_sets;
+  if (int r = c->pk_agg.ensure(n ? n : 1)) return r;
+  w.pk_agg = c->pk_agg.p;
+  if (int r = run_stages(c, d, w, ST_PK, ST_PK_SCALE + 1)) return r;
+  if (int r = c->dbg_out.ensure((size_t)n * 96 + 1)) return r;
+  launch_export_g1a(c->st, w.pk_agg, c->dbg_out.p, n);
+  HIPCHK(hipGetLastError());
+  std::vector<pk_window> win(d.win ? n : 0);
+  if (n && pk_agg96) HIPCHK(hipMemcpyAsync(pk_agg96, c->dbg_out.p, (size_t)n * 96, hipMemcpyDeviceToHost, c->st));
+  if (n && pk_code) HIPCHK(hipMemcpyAsync(pk_code, w.pk_code, (size_t)n * 4, hipMemcpyDeviceToHost, c->st));
+  if (n && d.win) HIPCHK(hipMemcpyAsync(win.data(), d.win, (size_t)n * sizeof(pk_window), hipMemcpyDeviceToHost, c->st));
+  HIPCHK(hipStreamSynchronize(c->st));
+  c->staged_pending = false;
+  if (path)
+    for (uint32_t i = 0; i < n; i++) path[i] = d.win && win[i].hi ? 1 : 0;
   return BGV_OK;
 }
 
@@ -2048,6 +2253,8 @@ int bgv_gen_keys(bgv_ctx* c, uint32_t first, uint32_t n, uint64_t seed) {
     c->sk.release();
     c->sk = nb;
   }
+  if (first < c->table_n)  // a rewrite: drops every list's sums (bgv_index_list_sums)
+    if (int r = sums_drop_all(c)) return r;
   launch_gen_keys(c->st, c->table, c->sk.p, first, n, seed);
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(c->st));

@@ -2,7 +2,10 @@
 // include/bgv.h): the expansion of every set's (list window, participation
 // bits) into the pk_offsets / pk_indices arrays the rest of the pipeline reads.
 // Three steps on the context's main stream:
-//   k_bits_count   per set: its key count (masked popcount, or len)
+//   k_bits_count   per set: its key count (masked popcount, or len); on a
+//                  context with resident sums (bgv_index_list_sums) also the
+//                  set's path: a complement set counts and expands its ABSENT
+//                  members and gets its window of the sums (pk_window)
 //   k_scan         counts -> pk_off[n_sets + 1]        (bgv_kernels.hip)
 //   k_bits_expand  per set: the list entries of its set bits, in order
 //
@@ -44,8 +47,9 @@ __global__ void __launch_bounds__(64) k_bits_count(bits_args a) {
   const bool live = i < a.n_sets;
   uint32_t cnt = 0;
   bool ok = false;
+  bits_src s = {0, 0, 0, 0};
   if (live) {
-    const bits_src s = a.src[i];
+    s = a.src[i];
     ok = bits_src_check(s, a.v) == BITS_OK;
     if (ok && s.list == BITS_SRC_EXPLICIT) {
       cnt = l == 0 ? s.len : 0u;
@@ -55,7 +59,37 @@ __global__ void __launch_bounds__(64) k_bits_count(bits_args a) {
     }
   }
   cnt = group_sum(cnt);
-  if (live && l == 0) a.pk_off[i] = ok ? cnt : 1u;
+  const bool lead = live && l == 0;
+  uint32_t pop = 0, cmpl = 0;  // this set's share of the two tallies
+  if (lead) {
+    if (a.win) {  // the context holds sums: the rule of bits_expand.h, per set
+      pk_window wd = {nullptr, nullptr};
+      pop = ok ? cnt : 1u;
+      if (ok && bits_src_complement(s, a.v, cnt)) {
+        // s passed the span check: off + len lies inside the list's n + 1 sums
+        const g1j* S = (const g1j*)bits_list_sums(a.v, s.list);
+        wd.lo = S + s.off;
+        wd.hi = S + s.off + s.len;
+        cnt = s.len - cnt;  // the absent members are gathered
+        cmpl = 1;
+      }
+      a.win[i] = wd;
+    }
+    a.pk_off[i] = ok ? cnt : 1u;
+  }
+  // on-device batches: the host has no bits to count, so the device tallies
+  // the participating keys and the complement sets, one atomic pair per wave
+  if (a.tally) {
+#pragma unroll
+    for (uint32_t d = 1; d < 64; d <<= 1) {
+      pop += __shfl_xor(pop, d, 64);
+      cmpl += __shfl_xor(cmpl, d, 64);
+    }
+    if ((threadIdx.x & 63u) == 0) {
+      atomicAdd(&a.tally[0], pop);
+      atomicAdd(&a.tally[1], cmpl);
+    }
+  }
 }
 
 __global__ void __launch_bounds__(64) k_bits_expand(bits_args a) {
@@ -64,12 +98,14 @@ __global__ void __launch_bounds__(64) k_bits_expand(bits_args a) {
   const bool live = i < a.n_sets;
   bits_src s = {0, 0, 0, 0};
   uint32_t base = 0, end = 0, words = 0;
+  bool cmpl = false;  // complement path: the clear bits below len are expanded
   if (live) {
     s = a.src[i];
     base = a.pk_off[i];
     end = min(a.pk_off[i + 1], a.cap);
     if (bits_src_check(s, a.v) == BITS_OK) {
       words = bits_words(s.len);
+      cmpl = a.win && a.win[i].hi;
     } else if (l == 0 && base < end) {
       a.pk_idx[base] = BITS_BAD_INDEX;
     }
@@ -82,7 +118,7 @@ __global__ void __launch_bounds__(64) k_bits_expand(bits_args a) {
   uint32_t carry = 0;
   for (uint32_t p = 0; p < passes; p++) {
     const uint32_t w = p * BITS_LANES + l;
-    const uint32_t m = w < words ? bits_src_word(s, a.v, w) : 0u;
+    const uint32_t m = w < words ? bits_gather_word(s, a.v, w, cmpl) : 0u;
     const uint32_t c = bits_popc(m);
     uint32_t x = c;  // inclusive prefix over the set's lanes
 #pragma unroll

@@ -27,11 +27,39 @@ namespace bgv {
 // (bgv_kernels.hip k_chunk_count / k_scan / k_chunk_set).  Offsets that run
 // backwards give the set no chunks, and the chunk scan is clipped at
 // chunk_bound: no access leaves the buffers.
+//
+// CMPL (batches of bgv_verify_bits on a context with resident sums, b.win set):
+// a set on the complement path (bits_expand.h bits_complement) has one chunk
+// more, its first, which is the window difference S[off + len] - S[off] by the
+// complete addition (equal sums give the identity, opposite ones the
+// doubling); its other chunks hold the ABSENT members and their sum is stored
+// negated.  k_pk and its variants fold the chunk sums unchanged, and the range
+// marker keeps X = 0 under negation.  Every other batch runs the instance
+// without that code.
+template <bool CMPL>
 __global__ void __launch_bounds__(64, BGV_PKC_WAVES) k_pk_chunk(dev_batch b, dev_work w) {
   const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
   if (g >= min(w.chunk_off[b.n_sets], b.chunk_bound)) return;
   const uint32_t i = w.chunk_set[g];
-  const uint32_t beg = b.pk_off[i] + (g - w.chunk_off[i]) * PK_CHUNK;
+  uint32_t ci = g - w.chunk_off[i];  // chunk of the set's gathered keys
+  bool negate = false;
+  if (CMPL) {
+    const pk_window wd = b.win[i];
+    if (wd.hi) {
+      if (ci == 0) {
+        const g1j hi = *wd.hi;
+        g1j lo = *wd.lo;
+        fp_neg(lo.y, lo.y);  // the identity (Z = 0) stays the identity
+        g1j d;
+        jac_add(d, hi, lo);
+        w.pk_part[g] = d;
+        return;
+      }
+      ci--;
+      negate = true;
+    }
+  }
+  const uint32_t beg = b.pk_off[i] + ci * PK_CHUNK;
   const uint32_t end = min(beg + PK_CHUNK, b.pk_off[i + 1]);
   g1j acc;
   jac_set_inf(acc);
@@ -45,6 +73,7 @@ __global__ void __launch_bounds__(64, BGV_PKC_WAVES) k_pk_chunk(dev_batch b, dev
     if (g1a_is_zero(p)) continue;  // infinity entry adds nothing
     jac_add_aff(acc, acc, p);
   }
+  if (CMPL && negate) fp_neg(acc.y, acc.y);
   if (range_err) {  // marker (X, Y, Z) = (0, 1, 1): not on E1, never produced by point additions
     fp_set_zero(acc.x);
     acc.y = FP_ONE;
@@ -54,7 +83,9 @@ __global__ void __launch_bounds__(64, BGV_PKC_WAVES) k_pk_chunk(dev_batch b, dev
 }
 
 void launch_pk_gather(hipStream_t st, const dev_batch& b, const dev_work& w) {
-  if (b.chunk_bound) hipLaunchKernelGGL(k_pk_chunk, dim3((b.chunk_bound + 63u) / 64u), dim3(64), 0, st, b, w);
+  if (!b.chunk_bound) return;
+  if (b.win) hipLaunchKernelGGL(k_pk_chunk<true>, dim3((b.chunk_bound + 63u) / 64u), dim3(64), 0, st, b, w);
+  else hipLaunchKernelGGL(k_pk_chunk<false>, dim3((b.chunk_bound + 63u) / 64u), dim3(64), 0, st, b, w);
 }
 
 }  // namespace bgv

@@ -13,6 +13,15 @@ enum : int32_t {
   C_EMPTY_JOB = 10,
 };
 
+// A set on the complement path of bgv_verify_bits (bits_expand.h
+// bits_complement): its window of the list's resident prefix sums.  The
+// aggregate key is *hi - *lo minus the gathered (absent) members.  hi == NULL:
+// the set is on the direct path.
+struct pk_window {
+  const g1j* lo;
+  const g1j* hi;
+};
+
 // HBM layout of one batch (device pointers).  All arrays are dense and
 // indexed by set (or job); see include/bgv.h bgv_batch for their meaning.
 struct dev_batch {
@@ -46,6 +55,11 @@ struct dev_batch {
   const uint8_t* sigs;
   const uint32_t* sig_len;
   const uint64_t* scalars;
+  // bgv_verify_bits on a context with resident sums: per-set windows (NULL for
+  // every other entry point and for contexts without sums).  A complement set
+  // gets one extra chunk, its first: the window difference; its other chunks
+  // hold absent members and are stored negated (k_chunk_count, k_pk_chunk)
+  const pk_window* win;
 };
 
 // Per-batch intermediates resident in HBM.
@@ -230,9 +244,24 @@ struct bits_args {
   uint32_t* pk_off;     // [n_sets + 1]: per-set key counts, then their scan
   uint32_t* pk_idx;     // the expansion
   uint32_t cap;         // entries of pk_idx
+  // contexts with resident sums (else NULL): the per-set windows k_bits_count
+  // writes; pk_off then counts gathered keys.  On-device batches of such a
+  // context (else NULL) also get two counters k_bits_count adds to, zeroed by
+  // the caller: tally[0] the batch's participating keys (sum of pop and
+  // explicit lengths), tally[1] the sets on the complement path; host
+  // batches have both from the host check
+  pk_window* win;
+  uint32_t* tally;
 };
 void launch_bits_count(hipStream_t st, const bits_args& a);
 void launch_bits_expand(hipStream_t st, const bits_args& a);
+// resident prefix sums of an index list (bgv_index_list_sums, bgv_sums.hip):
+// sums[k] = sum of table[list[j]] for j < k, k = 0 .. n, Jacobian; tmp holds
+// sums_tmp_entries(n) entries of scratch
+size_t sums_tmp_entries(uint32_t n);
+void launch_list_sums(hipStream_t st, const g1a* table, uint32_t table_n, const uint32_t* list, uint32_t n, g1j* sums,
+                      g1j* tmp);
+void launch_sums_export(hipStream_t st, const g1j* sums, uint8_t* out96, uint32_t n);
 // exclusive scan of a[0..n) in place, total at a[n] (bgv_kernels.hip k_scan)
 void launch_scan(hipStream_t st, uint32_t* a, uint32_t n);
 

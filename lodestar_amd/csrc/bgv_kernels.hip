@@ -391,7 +391,9 @@ __global__ void BGV_BULK k_chunk_count(dev_batch b, dev_work w) {
   if (i >= b.n_sets) return;
   const uint32_t lo = b.pk_off[i], hi = b.pk_off[i + 1];
   const uint32_t k = hi > lo ? hi - lo : 0u;
-  w.chunk_off[i] = (k + PK_CHUNK - 1) / PK_CHUNK;
+  // a complement set (bgv_verify_bits over resident sums) has one chunk more, the window's
+  const uint32_t wnd = b.win && hi >= lo && b.win[i].hi ? 1u : 0u;
+  w.chunk_off[i] = (k + PK_CHUNK - 1) / PK_CHUNK + wnd;
 }
 
 // exclusive scan of a[0..n) in place, total at a[n]; one workgroup walking

@@ -28,6 +28,9 @@ struct bits_view {
   uint32_t bits_len;
   const uint32_t* pk_indices;  // keys of explicit sets
   uint32_t n_indices;
+  // resident prefix sums of a list (bgv_index_list_sums; NULL: none).  Only
+  // "has sums" matters here: the entry type belongs to the gather
+  const void* sums[BITS_MAX_LISTS];
 };
 
 enum : int {
@@ -100,6 +103,13 @@ BGV_HD uint32_t bits_list_len(const bits_view& v, uint32_t id) {
   return n;
 }
 
+BGV_HD const void* bits_list_sums(const bits_view& v, uint32_t id) {
+  const void* p = v.sums[0];
+  for (uint32_t k = 1; k < BITS_MAX_LISTS; k++)
+    if (id == k) p = v.sums[k];
+  return p;
+}
+
 // The span checks of one source, in 64-bit arithmetic (off = 0xfffffff0 with
 // len = 0x20 must not wrap into the list).
 BGV_HD int bits_src_check(const bits_src& s, const bits_view& v) {
@@ -115,6 +125,29 @@ BGV_HD int bits_src_check(const bits_src& s, const bits_view& v) {
 BGV_HD uint32_t bits_src_word(const bits_src& s, const bits_view& v, uint32_t w) {
   if (s.list == BITS_SRC_EXPLICIT) return bits_len_mask(s.len, w);
   return bits_word(v.bits, v.bits_len, s.bits_off, s.len, w);
+}
+
+// The complement rule (bgv_index_list_sums).  A list set with `pop` of its
+// `len` bits set has the aggregate key S[off + len] - S[off] - (the sum of
+// its len - pop absent members): the window costs two row reads and one
+// addition, as much as two gathered keys, so the complement path is taken iff
+// the list has sums and absent + 2 < pop.  Padding bits above len are in
+// neither count (pop comes from masked words).
+BGV_HD bool bits_complement(bool has_sums, uint32_t len, uint32_t pop) {
+  return has_sums && (uint64_t)(len - pop) + 2u < pop;
+}
+
+// the rule for a source that passed bits_src_check: explicit sets and sets of
+// lists without sums stay on the direct path
+BGV_HD bool bits_src_complement(const bits_src& s, const bits_view& v, uint32_t pop) {
+  return s.list != BITS_SRC_EXPLICIT && bits_complement(bits_list_sums(v, s.list) != nullptr, s.len, pop);
+}
+
+// word w of the keys a source gathers: its set bits, or on the complement path
+// its clear bits below len
+BGV_HD uint32_t bits_gather_word(const bits_src& s, const bits_view& v, uint32_t w, bool complement) {
+  const uint32_t m = bits_src_word(s, v, w);
+  return complement ? ~m & bits_len_mask(s.len, w) : m;
 }
 
 // entry j of a source that passed bits_src_check

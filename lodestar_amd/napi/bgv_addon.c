@@ -27,6 +27,9 @@
  *   setIndexList(ctx, id, Uint32Array)           bgv_index_list_set: a resident index list (an epoch's shuffling,
  *                                                a sync committee); an empty array drops it
  *   indexListLen(ctx, id) -> number              bgv_index_list_len
+ *   setIndexListSums(ctx, id, bool)              bgv_index_list_sums: build (or drop) the list's resident prefix sums
+ *   indexListHasSums(ctx, id) -> boolean         bgv_index_list_has_sums
+ *   bitsPathStats(ctx) -> {setsComplement, keysExpanded, keysGathered}   bgv_bits_path_stats (the last verifyBits)
  *   verifyBits(ctx, bitsBatch) -> Promise<result>, verifyBitsSync(ctx, bitsBatch) -> result
  *                                                bgv_verify_bits: sets given as (list, window, participation bits)
  *                                                or as explicit index runs (see "committee bitfields" below)
@@ -954,6 +957,64 @@ static napi_value IndexListLen(napi_env env, napi_callback_info info) {
   return r;
 }
 
+static napi_value SetIndexListSums(napi_env env, napi_callback_info info) {
+  size_t argc = 3;
+  napi_value a[3];
+  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, a, NULL, NULL));
+  addon_ctx* c = get_ctx(env, a[0]);
+  if (!c) return NULL;
+  uint32_t id = 0;
+  bool enable = false;
+  if (argc < 3 || napi_get_value_uint32(env, a[1], &id) != napi_ok || napi_get_value_bool(env, a[2], &enable) != napi_ok) {
+    napi_throw_type_error(env, NULL, "setIndexListSums(ctx, id, boolean)");
+    return NULL;
+  }
+  pthread_mutex_lock(&c->mu); /* waits for the context's batch in flight */
+  const int st = bgv_index_list_sums(c->ctx, id, enable ? 1u : 0u);
+  pthread_mutex_unlock(&c->mu);
+  if (st != BGV_OK) return throw_bgv(env, st);
+  return NULL;
+}
+
+static napi_value IndexListHasSums(napi_env env, napi_callback_info info) {
+  size_t argc = 2;
+  napi_value a[2];
+  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, a, NULL, NULL));
+  addon_ctx* c = get_ctx(env, a[0]);
+  if (!c) return NULL;
+  uint32_t id = 0, has = 0;
+  NAPI_CALL(env, napi_get_value_uint32(env, a[1], &id));
+  pthread_mutex_lock(&c->mu);
+  const int st = bgv_index_list_has_sums(c->ctx, id, &has);
+  pthread_mutex_unlock(&c->mu);
+  if (st != BGV_OK) return throw_bgv(env, st);
+  napi_value r;
+  NAPI_CALL(env, napi_get_boolean(env, has != 0, &r));
+  return r;
+}
+
+static napi_value BitsPathStats(napi_env env, napi_callback_info info) {
+  size_t argc = 1;
+  napi_value a[1];
+  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, a, NULL, NULL));
+  addon_ctx* c = get_ctx(env, a[0]);
+  if (!c) return NULL;
+  bgv_bits_path p;
+  pthread_mutex_lock(&c->mu);
+  const int st = bgv_bits_path_stats(c->ctx, &p);
+  pthread_mutex_unlock(&c->mu);
+  if (st != BGV_OK) return throw_bgv(env, st);
+  napi_value r, v;
+  NAPI_CALL(env, napi_create_object(env, &r));
+  NAPI_CALL(env, napi_create_uint32(env, p.sets_complement, &v));
+  NAPI_CALL(env, napi_set_named_property(env, r, "setsComplement", v));
+  NAPI_CALL(env, napi_create_uint32(env, p.keys_expanded, &v));
+  NAPI_CALL(env, napi_set_named_property(env, r, "keysExpanded", v));
+  NAPI_CALL(env, napi_create_uint32(env, p.keys_gathered, &v));
+  NAPI_CALL(env, napi_set_named_property(env, r, "keysGathered", v));
+  return r;
+}
+
 static napi_value Init(napi_env env, napi_value exports) {
   napi_property_descriptor d[] = {
       {"abiVersion", NULL, AbiVersion, NULL, NULL, NULL, napi_enumerable, NULL},
@@ -975,6 +1036,9 @@ static napi_value Init(napi_env env, napi_value exports) {
       {"verifySameMessageAggSync", NULL, VerifySameMessageAggSync, NULL, NULL, NULL, napi_enumerable, NULL},
       {"setIndexList", NULL, SetIndexList, NULL, NULL, NULL, napi_enumerable, NULL},
       {"indexListLen", NULL, IndexListLen, NULL, NULL, NULL, napi_enumerable, NULL},
+      {"setIndexListSums", NULL, SetIndexListSums, NULL, NULL, NULL, napi_enumerable, NULL},
+      {"indexListHasSums", NULL, IndexListHasSums, NULL, NULL, NULL, napi_enumerable, NULL},
+      {"bitsPathStats", NULL, BitsPathStats, NULL, NULL, NULL, napi_enumerable, NULL},
       {"verifyBits", NULL, VerifyBits, NULL, NULL, NULL, napi_enumerable, NULL},
       {"verifyBitsSync", NULL, VerifyBitsSync, NULL, NULL, NULL, napi_enumerable, NULL},
   };

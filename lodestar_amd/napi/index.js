@@ -555,9 +555,15 @@ class BlsGpuVerifier {
   // A resident index list (an epoch's shuffling, a sync committee) into every
   // context, like the pubkey table (bgv_index_list_set); an empty array drops
   // it.  Committee sets name it by committee.list.  Each context's call waits
-  // for that context's batch in flight.
-  setIndexList(id, indices) {
-    for (const c of this.allContexts()) addon.setIndexList(c, id, indices);
+  // for that context's batch in flight.  {sums: true} also builds the list's
+  // resident prefix sums (bgv_index_list_sums): nearly full committees are then
+  // taken as window sum minus absent members.  Every entry must be a row the
+  // table already holds; a later pubkeysSet that rewrites a row drops the sums.
+  setIndexList(id, indices, opts = {}) {
+    for (const c of this.allContexts()) {
+      addon.setIndexList(c, id, indices);
+      if (opts.sums && indices.length) addon.setIndexListSums(c, id, true);
+    }
   }
 
   // sizes the priority context's work buffers for a full job (128 sets) at
@@ -1020,8 +1026,9 @@ class BlsGpuSingleThreadVerifier {
     addon.pubkeysSet(this.ctx, firstIndex, bytes, format);
   }
 
-  setIndexList(id, indices) {
+  setIndexList(id, indices, opts = {}) {
     addon.setIndexList(this.ctx, id, indices);
+    if (opts.sums && indices.length) addon.setIndexListSums(this.ctx, id, true);
   }
 
   async verifySignatureSets(sets) {

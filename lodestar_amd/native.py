@@ -55,6 +55,8 @@ EXPORTS = [
     "bgv_verify_same_message_agg", "bgv_sma_check", "bgv_debug_same_message_agg",
     "bgv_index_list_set", "bgv_index_list_len", "bgv_verify_bits", "bgv_bits_check", "bgv_debug_bits_expand",
     "bgv_bits_expand_ms",
+    "bgv_index_list_sums", "bgv_index_list_has_sums", "bgv_bits_path_stats", "bgv_bits_plan", "bgv_debug_bits_keys",
+    "bgv_debug_index_list_sums", "bgv_index_list_sums_ms",
 ]
 MAX_INDEX_LISTS = 8
 SRC_EXPLICIT = 0xFFFFFFFF
@@ -229,6 +231,14 @@ def source_files(root: str = ROOT) -> list[str]:
     return [os.path.join("lodestar_amd", "csrc", f) for f in names] + [os.path.join("include", "bgv.h")]
 
 
+class BgvBitsPath(ctypes.Structure):
+    """bgv_bits_path (include/bgv.h): path counters of the last bgv_verify_bits"""
+    _fields_ = [("sets_complement", ctypes.c_uint32), ("keys_expanded", ctypes.c_uint32), ("keys_gathered", ctypes.c_uint32)]
+
+    def as_dict(self) -> dict:
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
 def source_hash(root: str = ROOT) -> str:
     """SHA-256 over (path, content) of source_files(): the id tools/build.py
     compiles into the library (bgv_build_id) and load_library checks."""
@@ -324,6 +334,13 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
             "bgv_bits_check": ([ctypes.POINTER(BgvBitsBatch), P], ctypes.c_int),
             "bgv_debug_bits_expand": ([P, ctypes.POINTER(BgvBitsBatch), P, P, u32, ctypes.POINTER(u32)], ctypes.c_int),
             "bgv_bits_expand_ms": ([P, ctypes.POINTER(ctypes.c_float)], ctypes.c_int),
+            "bgv_index_list_sums": ([P, u32, u32], ctypes.c_int),
+            "bgv_index_list_has_sums": ([P, u32, ctypes.POINTER(u32)], ctypes.c_int),
+            "bgv_index_list_sums_ms": ([P, ctypes.POINTER(ctypes.c_float)], ctypes.c_int),
+            "bgv_bits_path_stats": ([P, ctypes.POINTER(BgvBitsPath)], ctypes.c_int),
+            "bgv_bits_plan": ([ctypes.POINTER(BgvBitsBatch), P, P, P, ctypes.POINTER(ctypes.c_uint64)], ctypes.c_int),
+            "bgv_debug_bits_keys": ([P, ctypes.POINTER(BgvBitsBatch), P, P, P], ctypes.c_int),
+            "bgv_debug_index_list_sums": ([P, u32, u32, u32, P], ctypes.c_int),
         }
         for name, (args, res) in sig.items():
             fn = getattr(lib, name)
@@ -421,6 +438,25 @@ def bits_check(arrays: dict, list_len, on_device: bool = False) -> tuple[int, st
     ll[: len(list_len)] = np.asarray(list_len, np.uint32)
     st = lib.bgv_bits_check(ctypes.byref(b), ll.ctypes.data)
     return st, ("" if st == BGV_OK else lib.bgv_last_error().decode())
+
+
+def bits_plan(arrays: dict, list_len, list_has_sums=None, on_device: bool = False):
+    """bgv_bits_plan: bgv_bits_check's checks, then the complement rule of
+    bgv_index_list_sums, without a device.  list_has_sums: one flag per list
+    (None: no list has sums).  Returns (status, error text, path uint8[n_sets],
+    keys_gathered); path and keys_gathered are meaningful for BGV_OK on a host
+    batch only."""
+    lib = load_library()
+    b = make_bits_batch(arrays, on_device, sync_inputs=False)
+    ll = np.zeros(MAX_INDEX_LISTS, np.uint32)
+    ll[: len(list_len)] = np.asarray(list_len, np.uint32)
+    hs = np.zeros(MAX_INDEX_LISTS, np.uint8)
+    if list_has_sums is not None:
+        hs[: len(list_has_sums)] = np.asarray(list_has_sums, bool)
+    path = np.zeros(max(b.n_sets, 1), np.uint8)
+    kg = ctypes.c_uint64()
+    st = lib.bgv_bits_plan(ctypes.byref(b), ll.ctypes.data, hs.ctypes.data, path.ctypes.data, ctypes.byref(kg))
+    return st, ("" if st == BGV_OK else lib.bgv_last_error().decode()), path[: b.n_sets], int(kg.value)
 
 
 class Device:
@@ -625,6 +661,45 @@ class Device:
         n = ctypes.c_uint32()
         self._check(self.lib.bgv_index_list_len(self.h, list_id, ctypes.byref(n)))
         return n.value
+
+    def index_list_sums(self, list_id: int, enable: bool = True) -> None:
+        """bgv_index_list_sums: build (or drop) the resident prefix sums of a list"""
+        self._check(self.lib.bgv_index_list_sums(self.h, list_id, 1 if enable else 0))
+
+    def index_list_sums_ms(self) -> float:
+        """device time of this context's last index_list_sums build (HIP events)"""
+        ms = ctypes.c_float()
+        self._check(self.lib.bgv_index_list_sums_ms(self.h, ctypes.byref(ms)))
+        return ms.value
+
+    def index_list_has_sums(self, list_id: int) -> bool:
+        has = ctypes.c_uint32()
+        self._check(self.lib.bgv_index_list_has_sums(self.h, list_id, ctypes.byref(has)))
+        return bool(has.value)
+
+    def bits_path_stats(self) -> dict:
+        """bgv_bits_path_stats: {sets_complement, keys_expanded, keys_gathered} of the last verify_bits"""
+        out = BgvBitsPath()
+        self._check(self.lib.bgv_bits_path_stats(self.h, ctypes.byref(out)))
+        return out.as_dict()
+
+    bits_plan = staticmethod(bits_plan)
+
+    def debug_bits_keys(self, arrays: dict, on_device: bool = False):
+        """bgv_debug_bits_keys (test only): (pk_agg uint8[n_sets, 96], path uint8[n_sets], pk_code int32[n_sets])"""
+        b = make_bits_batch(arrays, on_device)
+        n = b.n_sets
+        pk = np.zeros((max(n, 1), 96), np.uint8)
+        path = np.zeros(max(n, 1), np.uint8)
+        code = np.zeros(max(n, 1), np.int32)
+        self._check(self.lib.bgv_debug_bits_keys(self.h, ctypes.byref(b), pk.ctypes.data, path.ctypes.data, code.ctypes.data))
+        return pk[:n], path[:n], code[:n]
+
+    def debug_index_list_sums(self, list_id: int, first: int, n: int) -> np.ndarray:
+        """bgv_debug_index_list_sums (test only): S[first .. first + n) as affine 96 B rows (zero: the identity)"""
+        out = np.zeros((max(n, 1), 96), np.uint8)
+        self._check(self.lib.bgv_debug_index_list_sums(self.h, list_id, first, n, out.ctypes.data))
+        return out[:n]
 
     make_bits_batch = staticmethod(make_bits_batch)
 

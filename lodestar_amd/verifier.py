@@ -789,17 +789,24 @@ class BlsGpuVerifier:
         self._sm = SameMessageQueue(self._run_same_message, self._exec, max_sets_per_device_batch)
         self._sma = SameMessageQueue(self._run_same_message_agg, self._exec, max_sets_per_device_batch)
 
-    def set_index_list(self, list_id: int, indices) -> None:
+    def set_index_list(self, list_id: int, indices, sums: bool = False) -> None:
         """Upload a resident index list (an epoch's shuffling, a sync committee)
         to every context, like the pubkey table (bgv_index_list_set); an empty
-        list drops it.  Committee sets refer to it by CommitteeRef.list_id."""
+        list drops it.  Committee sets refer to it by CommitteeRef.list_id.
+        sums: also build the list's resident prefix sums (bgv_index_list_sums),
+        so nearly full committees are taken as window sum minus absent members;
+        every entry must then be a row the table already holds."""
         arr = np.ascontiguousarray(indices, dtype=np.uint32)
         for k, d in enumerate(self.devices):
             with self._dev_locks[k]:
                 d.index_list_set(list_id, arr)
+                if sums and arr.size:
+                    d.index_list_sums(list_id, True)
         if self.prio is not None:
             with self._prio_lock:
                 self.prio.index_list_set(list_id, arr)
+                if sums and arr.size:
+                    self.prio.index_list_sums(list_id, True)
 
     # -- IBlsVerifier ---------------------------------------------------
     def can_accept_work(self) -> bool:
@@ -1221,9 +1228,13 @@ class BlsGpuSingleThreadVerifier:
         check_aggregate_same_message(sets, message)
         return run_same_message_agg_calls(self.device, [(sets, message)], None, self.metrics)[0]
 
-    def set_index_list(self, list_id: int, indices) -> None:
-        """bgv_index_list_set on this verifier's context (see BlsGpuVerifier.set_index_list)"""
-        self.device.index_list_set(list_id, np.ascontiguousarray(indices, dtype=np.uint32))
+    def set_index_list(self, list_id: int, indices, sums: bool = False) -> None:
+        """bgv_index_list_set (and, with sums, bgv_index_list_sums) on this
+        verifier's context (see BlsGpuVerifier.set_index_list)"""
+        arr = np.ascontiguousarray(indices, dtype=np.uint32)
+        self.device.index_list_set(list_id, arr)
+        if sums and arr.size:
+            self.device.index_list_sums(list_id, True)
 
     def can_accept_work(self) -> bool:
         return True

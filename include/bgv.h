@@ -509,7 +509,8 @@ int bgv_bits_expand_ms(bgv_ctx* ctx, float* ms);
  * set with no absent member gathers no key at all; BGV_E_EMPTY_SET stays a
  * rule on pop.  job_result, set_code and bgv_stats are those of the direct path
  * (pubkeys_aggregated stays the participating keys; an identity aggregate is
- * BGV_SET_PK_IS_INFINITY).  Same-message entries and bgv_partial do not use sums.
+ * BGV_SET_PK_IS_INFINITY).  bgv_verify_same_message_bits (below) uses sums by the
+ * same rule; the explicit-list same-message entries and bgv_partial do not.
  *
  * When it pays (tools/bench_bits_sums.py; one MI355X,
  * host-resident batches, a context with sums against one without in the same
@@ -529,9 +530,12 @@ int bgv_index_list_has_sums(bgv_ctx* ctx, uint32_t list_id, uint32_t* has);
 /* Device time (ms, HIP events around the scan kernels) of the context's last
  * successful bgv_index_list_sums(.., 1); 0 before the first. */
 int bgv_index_list_sums_ms(bgv_ctx* ctx, float* ms);
-/* Path counters of the last bgv_verify_bits on the context: sets on the
- * complement path, participating keys (sum of pop and explicit lengths) and
- * the keys the gather read. */
+/* Path counters of the last bgv_verify_bits or bgv_verify_same_message_bits on
+ * the context: sets on the complement path, participating keys (sum of pop and
+ * explicit lengths) and the keys the gather read.  A caller of committee sets
+ * no longer holds the index lists, so the bindings take the aggregated-key
+ * count (lodestar_bls_aggregated_pubkeys_total) of a same-message call from
+ * keys_expanded. */
 typedef struct bgv_bits_path {
   uint32_t sets_complement, keys_expanded, keys_gathered;
 } bgv_bits_path;
@@ -553,6 +557,67 @@ int bgv_debug_bits_keys(bgv_ctx* ctx, const bgv_bits_batch* batch, uint8_t* pk_a
 /* test-only: entries S[first .. first + n) of a list's sums as affine 96 B
  * (x || y big-endian), all-zero for the identity. */
 int bgv_debug_index_list_sums(bgv_ctx* ctx, uint32_t list_id, uint32_t first, uint32_t n, uint8_t* out96);
+
+/* ---- same-message batches of committee sets ----------------------------------
+ * bgv_verify_same_message_agg for a caller that keeps its committees resident:
+ * the aggregates of one committee and one AttestationData are windows of one
+ * resident list with nearly every bit set, and the per-set key aggregation is
+ * the one cost a same-message group still pays in full.  Groups are those of
+ * bgv_sm_batch (one root per GROUP); the keys of set i are given exactly as in
+ * bgv_bits_batch: a list window plus participation bits, or a BGV_SRC_EXPLICIT
+ * run of pk_indices (bit 31 selects raw_pks).  Additive to ABI 4.
+ *
+ * The contract: set_valid, set_code and bgv_sm_stats (all but total_ms) are
+ * those of bgv_verify_same_message_agg on the bgv_sma_batch whose pk_offsets /
+ * pk_indices are the expansion of src and bits (bit order and expansion rule of
+ * bgv_verify_bits) and whose other fields are equal, whether or not the context
+ * holds sums: per-set verdicts, rejection before aggregation, 64-set segments,
+ * the whole-batch check, the per-segment final exponentiation, the per-set
+ * retry against PK_i as a raw key, an identity P of a segment going to the
+ * retry, signature codes before key codes.  With sums resident a list set takes
+ * the complement path by the rule of bgv_index_list_sums.
+ *
+ * Host batches are staged and checked on the pinned copy (bgv_smb_check runs
+ * the same checks alone).  The group rules are bgv_sma_check's (offsets
+ * monotone and spanning [0, n_sets], no empty group, n_groups <= n_sets,
+ * scalars non-zero), the source rules bgv_bits_check's (the list is set, off +
+ * len in 64 bits, bits_off + ceil(len / 8) <= bits_len, zero padding bits, a
+ * key total that fits 32 bits); a set with no bit set, or an explicit set with
+ * len == 0, is BGV_E_EMPTY_SET.  Every refusal names its set or group.
+ * n_sets == 0 succeeds with no output.  On-device batches are trusted but
+ * bounded as in bgv_verify_bits: a source that fails the span checks expands to
+ * the single index 0x7fffffff, which here rejects only that set
+ * (BGV_SET_INDEX_RANGE, set_valid = 0); padding bits are masked.
+ *
+ * When it pays: DESIGN.md section 3f, tools/bench_same_message_bits.py.        */
+typedef struct bgv_smb_batch {
+  uint32_t n_sets, n_groups;
+  const uint32_t* group_offsets; /* [n_groups + 1], as bgv_sm_batch */
+  const bgv_set_src* src;        /* [n_sets], as bgv_bits_batch */
+  const uint8_t* bits;           /* all bitfields, byte-packed */
+  uint32_t bits_len;
+  const uint32_t* pk_indices;    /* keys of explicit sets; bit 31 selects raw_pks */
+  uint32_t n_indices;
+  const uint8_t* raw_pks;        /* [n_raw][96], may be NULL */
+  uint32_t n_raw;
+  const uint8_t* msgs;           /* [n_groups][32] */
+  const uint8_t* sigs;           /* [n_sets][192] */
+  const uint32_t* sig_len;       /* [n_sets] */
+  const uint64_t* scalars;       /* [n_sets] non-zero, or NULL = drawn on the device */
+  uint32_t on_device;
+} bgv_smb_batch;
+/* Outputs as bgv_verify_same_message_agg.  bgv_bits_path_stats reports the call. */
+int bgv_verify_same_message_bits(bgv_ctx* ctx, const bgv_smb_batch* batch, uint8_t* set_valid, int32_t* set_code,
+                                 bgv_sm_stats* stats);
+/* The host-side contract check on its own (no device, no context), against the
+ * lengths of the lists (0: not set).  The arrays of an on-device batch are not
+ * read. */
+int bgv_smb_check(const bgv_smb_batch* batch, const uint32_t* list_len /* [BGV_MAX_INDEX_LISTS] */);
+/* test-only: the outputs of bgv_debug_same_message_agg plus path[n_sets]
+ * (1 = complement path).  Any output pointer may be NULL. */
+int bgv_debug_same_message_bits(bgv_ctx* ctx, const bgv_smb_batch* batch, uint8_t* set_valid, int32_t* set_code,
+                                bgv_sm_stats* stats, uint8_t* pk_set96, uint8_t* path, uint8_t* p_group96,
+                                uint8_t* s_group192, uint8_t* h_group192);
 
 /* Multi-GPU partials: run the batch up to, but excluding, the
  * final exponentiation and return this shard's Miller product (576 B, 12

@@ -1190,14 +1190,19 @@ struct bits_plan_out {
   uint32_t total = 0, max_job = 1;
   uint32_t gathered = 0, n_complement = 0;
 };
-static int bits_check_core(uint32_t n, uint32_t J, const uint32_t* jo, const bits_src* src, const bits_view& v,
-                           bits_plan_out* out, uint8_t* path) {
+// the job-offset half: the bgv_batch rules, and the largest job
+static int bits_check_jobs(uint32_t n, uint32_t J, const uint32_t* jo, bits_plan_out* out) {
   if (jo[0] != 0 || jo[J] != n) return fail(BGV_E_INVALID_ARG, "job_offsets must span [0, n_sets]");
   uint32_t max_job = 1;
   for (uint32_t j = 0; j < J; j++) {
     if (jo[j + 1] < jo[j]) return fail(BGV_E_INVALID_ARG, "job_offsets not monotone");
     if (jo[j + 1] - jo[j] > max_job) max_job = jo[j + 1] - jo[j];
   }
+  out->max_job = max_job;
+  return BGV_OK;
+}
+// the source half (the host plan): every set's source, its key count and its path
+static int bits_check_sources(uint32_t n, const bits_src* src, const bits_view& v, bits_plan_out* out, uint8_t* path) {
   uint64_t total = 0, gathered = 0;
   uint32_t n_complement = 0;
   for (uint32_t i = 0; i < n; i++) {
@@ -1231,10 +1236,26 @@ static int bits_check_core(uint32_t n, uint32_t J, const uint32_t* jo, const bit
   }
   if (total > 0xffffffffull) return fail(BGV_E_INVALID_ARG, "the batch's %llu keys do not fit 32 bits", (unsigned long long)total);
   out->total = (uint32_t)total;
-  out->max_job = max_job;
   out->gathered = (uint32_t)gathered;
   out->n_complement = n_complement;
   return BGV_OK;
+}
+static int bits_check_core(uint32_t n, uint32_t J, const uint32_t* jo, const bits_src* src, const bits_view& v,
+                           bits_plan_out* out, uint8_t* path) {
+  if (int r = bits_check_jobs(n, J, jo, out)) return r;
+  return bits_check_sources(n, src, v, out, path);
+}
+
+// a host-only view for the checks: of the lists only "is set", the length and
+// "has sums" (list_has_sums may be NULL: none)
+static void bits_host_view(bits_view& v, const uint32_t* list_len, const uint8_t* list_has_sums) {
+  static const uint32_t present = 0;  // a non-NULL stand-in: the check reads no list entry and no sum
+  memset(&v, 0, sizeof v);
+  for (uint32_t k = 0; k < BGV_MAX_INDEX_LISTS; k++) {
+    v.list[k] = list_len[k] ? &present : nullptr;
+    v.list_len[k] = list_len[k];
+    v.sums[k] = list_len[k] && list_has_sums && list_has_sums[k] ? &present : nullptr;
+  }
 }
 
 int bgv_bits_plan(const bgv_bits_batch* b, const uint32_t* list_len, const uint8_t* list_has_sums, uint8_t* path,
@@ -1243,14 +1264,8 @@ int bgv_bits_plan(const bgv_bits_batch* b, const uint32_t* list_len, const uint8
   if (int r = bits_check_args(b, true)) return r;
   if (!list_len) return fail(BGV_E_INVALID_ARG, "list_len is NULL");
   if (b->on_device) return BGV_OK;
-  static const uint32_t present = 0;  // a non-NULL stand-in: the check reads no list entry and no sum
   bits_view v;
-  memset(&v, 0, sizeof v);
-  for (uint32_t k = 0; k < BGV_MAX_INDEX_LISTS; k++) {
-    v.list[k] = list_len[k] ? &present : nullptr;
-    v.list_len[k] = list_len[k];
-    v.sums[k] = list_len[k] && list_has_sums && list_has_sums[k] ? &present : nullptr;
-  }
+  bits_host_view(v, list_len, list_has_sums);
   v.bits = b->bits; v.bits_len = b->bits_len; v.pk_indices = b->pk_indices; v.n_indices = b->n_indices;
   bits_plan_out po;
   if (int r = bits_check_core(b->n_sets, b->n_jobs, b->job_offsets, (const bits_src*)b->src, v, &po, path)) return r;
@@ -1259,6 +1274,70 @@ int bgv_bits_plan(const bgv_bits_batch* b, const uint32_t* list_len, const uint8
 }
 
 int bgv_bits_check(const bgv_bits_batch* b, const uint32_t* list_len) { return bgv_bits_plan(b, list_len, nullptr, nullptr, nullptr); }
+
+// The set-up every entry that expands bitfields shares: bits_args / bits_view
+// over the context's lists (and their sums, unless use_sums is false), the
+// offset buffer, the per-set windows when a list has sums, and the context's
+// record of the batch (bgv_bits_path_stats).  a.src, a.v.bits and
+// a.v.pk_indices are the caller's to fill; the tally of an on-device batch is
+// zeroed on `st`, the stream the expansion will run on.
+static int bits_setup(bgv_ctx* c, bits_args& a, uint32_t n, uint32_t bits_len, uint32_t n_indices, bool on_device, bool use_sums,
+                      hipStream_t st) {
+  memset(&a, 0, sizeof a);
+  a.n_sets = n;
+  bool any_sums = false;
+  for (uint32_t k = 0; k < BGV_MAX_INDEX_LISTS; k++) {
+    a.v.list[k] = c->idx_list[k]; a.v.list_len[k] = c->idx_list_n[k];
+    a.v.sums[k] = use_sums ? c->idx_sums[k] : nullptr;
+    any_sums = any_sums || a.v.sums[k];
+  }
+  a.v.bits_len = bits_len;
+  a.v.n_indices = n_indices;
+  // with sums resident: two tally words behind the scan's total (bgv_internal.h bits_args)
+  if (int r = ensure_or_release_lines(c, c->bits_off, (size_t)n + 3)) return r;
+  a.pk_off = c->bits_off.p;
+  c->bits_any_sums = any_sums;
+  c->bits_on_device = on_device;
+  c->bits_path = {};
+  c->bits_extra_chunks = 0;
+  c->bits_n = n;
+  if (any_sums) {
+    if (int r = ensure_or_release_lines(c, c->bits_win, n ? n : 1)) return r;
+    a.win = c->bits_win.p;
+    if (on_device) {
+      a.tally = a.pk_off + n + 1;
+      HIPCHK(hipMemsetAsync(a.tally, 0, 8, st));
+    }
+  }
+  return 0;
+}
+
+// the expansion launches on a given stream, in two halves: an on-device batch
+// reads the totals back between them
+static void bits_launch_count(hipStream_t st, const bits_args& a) {
+  launch_bits_count(st, a);
+  if (a.n_sets) launch_scan(st, a.pk_off, a.n_sets);
+}
+// `gathered`: the keys the expansion holds (the scan's total)
+static int bits_launch_expand(bgv_ctx* c, hipStream_t st, bits_args& a, uint32_t gathered) {
+  if (int r = ensure_or_release_lines(c, c->bits_idx, gathered ? gathered : 1)) return r;
+  a.pk_idx = c->bits_idx.p;
+  a.cap = gathered;
+  launch_bits_expand(st, a);
+  return 0;
+}
+// the totals of an on-device batch, after bits_launch_count on `st`: the host
+// learns the gathered keys (buffer and grid bound) and the participating keys
+static int bits_read_totals(bgv_ctx* c, hipStream_t st, const bits_args& a) {
+  uint32_t tot[2] = {0, 0};
+  if (a.n_sets) HIPCHK(hipMemcpyAsync(tot, a.pk_off + a.n_sets, c->bits_any_sums ? 8 : 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  c->pk_total = c->bits_any_sums ? tot[1] : tot[0];
+  c->bits_path.keys_expanded = c->pk_total;
+  c->bits_path.keys_gathered = tot[0];
+  c->bits_extra_chunks = c->bits_any_sums ? a.n_sets : 0u;  // the complement sets are counted on the device only
+  return 0;
+}
 
 // prepare() for a bits batch up to the expanded device view: staging and checks
 // (host batches), early hash maps, raw keys, the expansion.  Leaves d.pk_off /
@@ -1273,33 +1352,8 @@ static int bits_front(bgv_ctx* c, const bgv_bits_batch* b, dev_batch& d, bool ne
   d.span_log2 = 7;
   c->jo_host.resize((size_t)J + 1);
   bits_args a;
-  memset(&a, 0, sizeof a);
-  a.n_sets = n;
-  bool any_sums = false;
-  for (uint32_t k = 0; k < BGV_MAX_INDEX_LISTS; k++) {
-    a.v.list[k] = c->idx_list[k]; a.v.list_len[k] = c->idx_list_n[k];
-    a.v.sums[k] = use_sums ? c->idx_sums[k] : nullptr;
-    any_sums = any_sums || a.v.sums[k];
-  }
-  a.v.bits_len = b->bits_len;
-  a.v.n_indices = b->n_indices;
-  // with sums resident: two tally words behind the scan's total (bgv_internal.h bits_args)
-  if (int r = ensure_or_release_lines(c, c->bits_off, (size_t)n + 3)) return r;
-  a.pk_off = c->bits_off.p;
-  c->bits_any_sums = any_sums;
-  c->bits_on_device = b->on_device != 0;
-  c->bits_path = {};
-  c->bits_extra_chunks = 0;
-  c->bits_n = n;
-  if (any_sums) {
-    if (int r = ensure_or_release_lines(c, c->bits_win, n ? n : 1)) return r;
-    a.win = c->bits_win.p;
-    if (b->on_device) {
-      a.tally = a.pk_off + n + 1;
-      HIPCHK(hipMemsetAsync(a.tally, 0, 8, c->st));
-    }
-    d.win = c->bits_win.p;
-  }
+  if (int r = bits_setup(c, a, n, b->bits_len, b->n_indices, b->on_device != 0, use_sums, c->st)) return r;
+  d.win = a.win;
   c->bits_timed = need_sigs && (c->cfg.timing >= 0 ? c->cfg.timing != 0 : n >= 65536);
   if (!b->on_device) {
     const uint8_t* raw_dev = nullptr;
@@ -1343,13 +1397,9 @@ static int bits_front(bgv_ctx* c, const bgv_bits_batch* b, dev_batch& d, bool ne
     if (int r = ensure_or_release_lines(c, c->raw_conv, b->n_raw ? b->n_raw : 1)) return r;
     launch_raw_pks(c->st, raw_dev, c->raw_conv.p, b->n_raw);
     d.raw_pks = c->raw_conv.p;
-    if (int r = ensure_or_release_lines(c, c->bits_idx, total ? total : 1)) return r;
-    a.pk_idx = c->bits_idx.p;
-    a.cap = total;
     if (c->bits_timed) HIPCHK(hipEventRecord(c->ev_bits[0], c->st));
-    launch_bits_count(c->st, a);
-    if (n) launch_scan(c->st, a.pk_off, n);
-    launch_bits_expand(c->st, a);
+    bits_launch_count(c->st, a);
+    if (int r = bits_launch_expand(c, c->st, a, total)) return r;
     if (c->bits_timed) HIPCHK(hipEventRecord(c->ev_bits[1], c->st));
   } else {
     d.job_off = b->job_offsets;
@@ -1363,24 +1413,13 @@ static int bits_front(bgv_ctx* c, const bgv_bits_batch* b, dev_batch& d, bool ne
     launch_raw_pks(c->st, b->raw_pks, c->raw_conv.p, b->n_raw);
     d.raw_pks = c->raw_conv.p;
     if (c->bits_timed) HIPCHK(hipEventRecord(c->ev_bits[0], c->st));
-    launch_bits_count(c->st, a);
-    if (n) launch_scan(c->st, a.pk_off, n);
+    bits_launch_count(c->st, a);
     HIPCHK(hipGetLastError());
-    // the host needs the job offsets (stats) and the key total (buffer and grid bound)
+    // the host needs the job offsets (stats) and the key total (buffer and grid bound),
+    // with sums resident the gathered total and the participating total together
     HIPCHK(hipMemcpyAsync(c->jo_host.data(), b->job_offsets, c->jo_host.size() * 4, hipMemcpyDeviceToHost, c->st));
-    // ... with sums resident the gathered total and the participating total together
-    uint32_t tot[2] = {0, 0};
-    if (n) HIPCHK(hipMemcpyAsync(tot, a.pk_off + n, any_sums ? 8 : 4, hipMemcpyDeviceToHost, c->st));
-    HIPCHK(hipStreamSynchronize(c->st));
-    const uint32_t gathered = tot[0];
-    c->pk_total = any_sums ? tot[1] : tot[0];
-    c->bits_path.keys_expanded = c->pk_total;
-    c->bits_path.keys_gathered = gathered;
-    c->bits_extra_chunks = any_sums ? n : 0u;  // the complement sets are counted on the device only
-    if (int r = ensure_or_release_lines(c, c->bits_idx, gathered ? gathered : 1)) return r;
-    a.pk_idx = c->bits_idx.p;
-    a.cap = gathered;
-    launch_bits_expand(c->st, a);
+    if (int r = bits_read_totals(c, c->st, a)) return r;
+    if (int r = bits_launch_expand(c, c->st, a, c->bits_path.keys_gathered)) return r;
     if (c->bits_timed) HIPCHK(hipEventRecord(c->ev_bits[1], c->st));
   }
   HIPCHK(hipGetLastError());
@@ -1802,6 +1841,44 @@ int bgv_sma_check(const bgv_sma_batch* b) {
   return BGV_OK;
 }
 
+// the segments of a same-message batch: every group cut into runs of at most SM_SEG sets
+struct sma_segs {
+  std::vector<uint32_t> seg_off, seg_group, group_seg, iota;
+  uint32_t S = 0;
+};
+static void sma_cut_segments(const std::vector<uint32_t>& go, uint32_t n, sma_segs& sg) {
+  const uint32_t G = (uint32_t)go.size() - 1;
+  sg.group_seg.resize((size_t)G + 1);
+  sg.seg_off.reserve(n / SM_SEG + G + 1);
+  for (uint32_t g = 0; g < G; g++) {
+    sg.group_seg[g] = (uint32_t)sg.seg_off.size();
+    for (uint32_t i = go[g]; i < go[g + 1]; i += SM_SEG) { sg.seg_off.push_back(i); sg.seg_group.push_back(g); }
+  }
+  sg.S = (uint32_t)sg.seg_off.size();
+  sg.group_seg[G] = sg.S;
+  sg.seg_off.push_back(n);
+  sg.iota.resize((size_t)sg.S + 1);
+  for (uint32_t s = 0; s <= sg.S; s++) sg.iota[s] = s;
+}
+// device view of such a batch once its arrays are staged (or resident)
+struct sma_dev {
+  uint32_t n, G, S, n_raw;
+  const sma_segs* sg;
+  const uint32_t *d_seg_off, *d_seg_group, *d_group_seg, *d_iota, *d_po, *d_idx, *d_len;
+  const uint8_t *d_msgs, *d_sigs, *d_raw;
+  const uint64_t* d_scalars;
+  bool draw_scalars;          // the caller gave none: drawn on the device (d_scalars is then not read)
+  uint32_t chunk_bound;       // grid bound of the gather
+  // bgv_verify_same_message_bits: the per-set windows (contexts with sums, else
+  // NULL) and the expansion still to run on the pubkey stream
+  const pk_window* win;
+  bits_args* expand;
+  bool expand_count;  // count and scan too (host batches: their totals come from the host plan)
+  uint32_t gathered;  // keys the expansion holds
+};
+static int sma_back(bgv_ctx* c, sma_dev& k, std::chrono::steady_clock::time_point t0, uint8_t* set_valid, int32_t* set_code,
+                    bgv_sm_stats* stats, uint8_t* pk_set96, uint8_t* p_group96, uint8_t* s_group192, uint8_t* h_group192);
+
 static int sma_run(bgv_ctx* c, const bgv_sma_batch* b, uint8_t* set_valid, int32_t* set_code, bgv_sm_stats* stats,
                    uint8_t* pk_set96, uint8_t* p_group96, uint8_t* s_group192, uint8_t* h_group192) {
   if (!c) return fail(BGV_E_INVALID_ARG, "null ctx");
@@ -1830,33 +1907,28 @@ static int sma_run(bgv_ctx* c, const bgv_sma_batch* b, uint8_t* set_valid, int32
   const bool host = !b->on_device;
 
   // staging: the segment tables always, the batch arrays of a host batch
-  const uint32_t *d_seg_off = nullptr, *d_seg_group = nullptr, *d_group_seg = nullptr, *d_iota = nullptr;
-  const uint32_t *d_po = b->pk_offsets, *d_idx = b->pk_indices, *d_len = b->sig_len;
-  const uint8_t *d_msgs = b->msgs, *d_sigs = b->sigs, *d_raw = b->raw_pks;
-  const uint64_t* d_scalars = b->scalars;
-  std::vector<uint32_t> seg_off, seg_group, group_seg((size_t)G + 1);
-  seg_off.reserve(n / SM_SEG + G + 1);
-  for (uint32_t g = 0; g < G; g++) {
-    group_seg[g] = (uint32_t)seg_off.size();
-    for (uint32_t i = go[g]; i < go[g + 1]; i += SM_SEG) { seg_off.push_back(i); seg_group.push_back(g); }
-  }
-  const uint32_t S = (uint32_t)seg_off.size();
-  group_seg[G] = S;
-  seg_off.push_back(n);
-  std::vector<uint32_t> iota((size_t)S + 1);
-  for (uint32_t s = 0; s <= S; s++) iota[s] = s;
+  sma_dev k;
+  memset(&k, 0, sizeof k);
+  k.n = n; k.G = G; k.n_raw = b->n_raw;
+  k.d_po = b->pk_offsets; k.d_idx = b->pk_indices; k.d_len = b->sig_len;
+  k.d_msgs = b->msgs; k.d_sigs = b->sigs; k.d_raw = b->raw_pks; k.d_scalars = b->scalars;
+  k.draw_scalars = !b->scalars;
+  sma_segs sg;
+  sma_cut_segments(go, n, sg);
+  const uint32_t S = sg.S;
+  k.S = S; k.sg = &sg;
   stage_seg segs[11] = {
-      {seg_off.data(), ((size_t)S + 1) * 4, (const void**)&d_seg_off, 0},
-      {seg_group.data(), (size_t)S * 4, (const void**)&d_seg_group, 0},
-      {group_seg.data(), ((size_t)G + 1) * 4, (const void**)&d_group_seg, 0},
-      {iota.data(), ((size_t)S + 1) * 4, (const void**)&d_iota, 0},
-      {b->pk_offsets, ((size_t)n + 1) * 4, (const void**)&d_po, 0},
-      {b->pk_indices, (size_t)total * 4, (const void**)&d_idx, 0},
-      {b->msgs, (size_t)G * 32, (const void**)&d_msgs, 0},
-      {b->raw_pks, (size_t)b->n_raw * 96, (const void**)&d_raw, 0},
-      {b->scalars, b->scalars ? (size_t)n * 8 : 0, (const void**)&d_scalars, 0},
-      {b->sigs, (size_t)n * 192, (const void**)&d_sigs, 0},
-      {b->sig_len, (size_t)n * 4, (const void**)&d_len, 0},
+      {sg.seg_off.data(), ((size_t)S + 1) * 4, (const void**)&k.d_seg_off, 0},
+      {sg.seg_group.data(), (size_t)S * 4, (const void**)&k.d_seg_group, 0},
+      {sg.group_seg.data(), ((size_t)G + 1) * 4, (const void**)&k.d_group_seg, 0},
+      {sg.iota.data(), ((size_t)S + 1) * 4, (const void**)&k.d_iota, 0},
+      {b->pk_offsets, ((size_t)n + 1) * 4, (const void**)&k.d_po, 0},
+      {b->pk_indices, (size_t)total * 4, (const void**)&k.d_idx, 0},
+      {b->msgs, (size_t)G * 32, (const void**)&k.d_msgs, 0},
+      {b->raw_pks, (size_t)b->n_raw * 96, (const void**)&k.d_raw, 0},
+      {b->scalars, b->scalars ? (size_t)n * 8 : 0, (const void**)&k.d_scalars, 0},
+      {b->sigs, (size_t)n * 192, (const void**)&k.d_sigs, 0},
+      {b->sig_len, (size_t)n * 4, (const void**)&k.d_len, 0},
   };
   size_t bytes = 0;
   if (int r = stage_pack(c, segs, host ? 11 : 4, bytes)) return r;
@@ -1870,7 +1942,22 @@ static int sma_run(bgv_ctx* c, const bgv_sma_batch* b, uint8_t* set_valid, int32
     }
   }
   if (int r = stage_issue(c, bytes)) return r;
-  if (!b->scalars) {
+  k.chunk_bound = total / PK_CHUNK + n;  // as prepare() sets it: sum ceil(k_i / 32) <= total / 32 + n
+  return sma_back(c, k, t0, set_valid, set_code, stats, pk_set96, p_group96, s_group192, h_group192);
+}
+
+// The device half of a same-message call over aggregate keys, from the staged
+// (or resident) arrays on: shared by bgv_verify_same_message_agg and
+// bgv_verify_same_message_bits.
+static int sma_back(bgv_ctx* c, sma_dev& k, std::chrono::steady_clock::time_point t0, uint8_t* set_valid, int32_t* set_code,
+                    bgv_sm_stats* stats, uint8_t* pk_set96, uint8_t* p_group96, uint8_t* s_group192, uint8_t* h_group192) {
+  const uint32_t n = k.n, G = k.G, S = k.S, n_raw = k.n_raw;
+  const std::vector<uint32_t>&seg_off = k.sg->seg_off, &seg_group = k.sg->seg_group;
+  const uint32_t *d_seg_off = k.d_seg_off, *d_seg_group = k.d_seg_group, *d_group_seg = k.d_group_seg, *d_iota = k.d_iota;
+  const uint32_t *d_po = k.d_po, *d_idx = k.d_idx, *d_len = k.d_len;
+  const uint8_t *d_msgs = k.d_msgs, *d_sigs = k.d_sigs, *d_raw = k.d_raw;
+  const uint64_t* d_scalars = k.d_scalars;
+  if (k.draw_scalars) {
     uint32_t kn[11];
     random_bytes(kn, sizeof kn);
     if (int r = ensure_or_release_lines(c, c->scalars, n)) return r;
@@ -1878,15 +1965,16 @@ static int sma_run(bgv_ctx* c, const bgv_sma_batch* b, uint8_t* set_valid, int32
     HIPCHK(hipGetLastError());
     d_scalars = c->scalars.p;
   }
-  if (int r = ensure_or_release_lines(c, c->raw_conv, b->n_raw ? b->n_raw : 1)) return r;
-  launch_raw_pks(c->st, d_raw, c->raw_conv.p, b->n_raw);
+  if (int r = ensure_or_release_lines(c, c->raw_conv, n_raw ? n_raw : 1)) return r;
+  launch_raw_pks(c->st, d_raw, c->raw_conv.p, n_raw);
 
   // view A: the real sets, one job per segment (gather, signature decode, G2 sums)
   dev_batch dA;
   memset(&dA, 0, sizeof dA);
-  dA.n_sets = n; dA.n_jobs = S; dA.n_raw = b->n_raw; dA.table_n = c->table_n; dA.table = c->table;
+  dA.n_sets = n; dA.n_jobs = S; dA.n_raw = n_raw; dA.table_n = c->table_n; dA.table = c->table;
   dA.span_log2 = 6; dA.job_lanes = 36; dA.pairs_per_item = 1; dA.msm = 4; dA.clear_lanes = 9;
-  dA.chunk_bound = total / PK_CHUNK + n;  // as prepare() sets it: sum ceil(k_i / 32) <= total / 32 + n
+  dA.chunk_bound = k.chunk_bound;
+  dA.win = k.win;
   dA.defer_from = n;
   dA.job_off = d_seg_off; dA.pk_off = d_po; dA.pk_idx = d_idx; dA.raw_pks = c->raw_conv.p;
   dA.sigs = d_sigs; dA.sig_len = d_len; dA.scalars = d_scalars;
@@ -1900,7 +1988,7 @@ static int sma_run(bgv_ctx* c, const bgv_sma_batch* b, uint8_t* set_valid, int32
   HIPCHK(hipMemsetAsync(c->sm_zero.p, 0, (size_t)n * 4, c->st));
   sm_view v;
   memset(&v, 0, sizeof v);
-  v.n_sets = n; v.n_segs = S; v.n_groups = G; v.n_raw = b->n_raw; v.table_n = c->table_n;
+  v.n_sets = n; v.n_segs = S; v.n_groups = G; v.n_raw = n_raw; v.table_n = c->table_n;
   v.seg_off = d_seg_off; v.seg_group = d_seg_group; v.pk_idx = d_idx; v.raw_pks = c->raw_conv.p; v.table = c->table;
   v.scalars = d_scalars; v.sig_code = w.sig_code; v.sig_inf = w.sig_inf; v.skip = c->sm_skip.p; v.set_code = w.set_code;
   v.win = c->sm_win.p; v.p_seg = w.rpk_aff; v.seg_code = c->sm_seg_code.p; v.h_group = c->sm_hg.p; v.h_seg = w.h_aff;
@@ -1923,16 +2011,24 @@ static int sma_run(bgv_ctx* c, const bgv_sma_batch* b, uint8_t* set_valid, int32
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(c->ev_dep[ST_HASH], c->st_hash));
   }
+  // bitfield sets: the decode, which is the critical path, is launched before the key side, whose three
+  // expansion launches would otherwise stand in front of it on the host thread
+  const bool sig_first = k.expand != nullptr;
+  if (sig_first) launch_stage(c->st, ST_SIG, dA, w);
   {  // the keys of every set on the pubkey stream, beside the signature decode
     dev_batch dP = dA;
     dP.miller_coop = 36;  // launch_prep: the chunk set-up only, no Miller work items
+    if (k.expand) {  // bitfield sets: the expansion runs where its reader, the gather, runs
+      if (k.expand_count) bits_launch_count(c->st_pk, *k.expand);
+      if (int r2 = bits_launch_expand(c, c->st_pk, *k.expand, k.gathered)) return r2;  // into k.d_idx: reserved by the caller
+    }
     launch_prep(c->st_pk, dP, w);
     launch_stage(c->st_pk, ST_PK, dP, w);
     launch_sma_set_sum(c->st_pk, dP, w, c->sma_pk.p, c->sma_pk_code.p);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(c->ev_dep[ST_PK], c->st_pk));
   }
-  launch_stage(c->st, ST_SIG, dA, w);
+  if (!sig_first) launch_stage(c->st, ST_SIG, dA, w);
   HIPCHK(hipStreamWaitEvent(c->st, c->ev_dep[ST_PK], 0));
   launch_sma_classify(c->st, v);
   HIPCHK(hipGetLastError());
@@ -2067,6 +2163,161 @@ int bgv_verify_same_message_agg(bgv_ctx* c, const bgv_sma_batch* b, uint8_t* set
 int bgv_debug_same_message_agg(bgv_ctx* c, const bgv_sma_batch* b, uint8_t* set_valid, int32_t* set_code, bgv_sm_stats* stats,
                                uint8_t* pk_set96, uint8_t* p_group96, uint8_t* s_group192, uint8_t* h_group192) {
   return sma_run(c, b, set_valid, set_code, stats, pk_set96, p_group96, s_group192, h_group192);
+}
+
+// ---- same-message batches of committee sets -----------------------------------
+// bgv_verify_same_message_bits: the sets of bgv_verify_same_message_agg given as
+// bgv_verify_bits gives them.  The front is bits_front's (set-up, host plan,
+// expansion), the device half sma_back with the expansion buffers as pk_off /
+// pk_idx and the windows of a context with sums.  The expansion runs on st_pk in
+// front of the gather, its only reader: the signature decode on st and the
+// hashes on st_hash start without it.
+
+static int smb_check_args(const bgv_smb_batch* b) {
+  if (!b) return fail(BGV_E_INVALID_ARG, "batch is NULL");
+  if (b->n_sets == 0 && b->n_groups == 0) return BGV_OK;
+  if (b->n_groups > b->n_sets) return fail(BGV_E_INVALID_ARG, "n_groups %u > n_sets %u (a group is never empty)", b->n_groups, b->n_sets);
+  if (b->n_groups == 0) return fail(BGV_E_INVALID_ARG, "n_sets %u without a group", b->n_sets);
+  if (!b->group_offsets || !b->src || !b->msgs || !b->sigs || !b->sig_len) return fail(BGV_E_INVALID_ARG, "missing batch array");
+  if (b->bits_len && !b->bits) return fail(BGV_E_INVALID_ARG, "bits_len > 0 but bits is NULL");
+  if (b->n_indices && !b->pk_indices) return fail(BGV_E_INVALID_ARG, "n_indices > 0 but pk_indices is NULL");
+  if (b->n_raw && !b->raw_pks) return fail(BGV_E_INVALID_ARG, "n_raw > 0 but raw_pks is NULL");
+  return BGV_OK;
+}
+
+static int smb_check_groups(const bgv_smb_batch* b, const uint32_t* go) {
+  bgv_sma_batch a;
+  memset(&a, 0, sizeof a);
+  a.n_sets = b->n_sets; a.n_groups = b->n_groups;
+  return sma_check_groups(&a, go);
+}
+
+int bgv_smb_check(const bgv_smb_batch* b, const uint32_t* list_len) {
+  if (int r = smb_check_args(b)) return r;
+  if (!list_len) return fail(BGV_E_INVALID_ARG, "list_len is NULL");
+  if (b->on_device || b->n_sets == 0) return BGV_OK;
+  if (int r = smb_check_groups(b, b->group_offsets)) return r;
+  bits_view v;
+  bits_host_view(v, list_len, nullptr);
+  v.bits = b->bits; v.bits_len = b->bits_len; v.pk_indices = b->pk_indices; v.n_indices = b->n_indices;
+  bits_plan_out po;
+  if (int r = bits_check_sources(b->n_sets, (const bits_src*)b->src, v, &po, nullptr)) return r;
+  if (b->scalars)
+    for (uint32_t i = 0; i < b->n_sets; i++)
+      if (!b->scalars[i]) return fail(BGV_E_INVALID_ARG, "scalars[%u] is zero", i);
+  return BGV_OK;
+}
+
+static int smb_run(bgv_ctx* c, const bgv_smb_batch* b, uint8_t* set_valid, int32_t* set_code, bgv_sm_stats* stats,
+                   uint8_t* pk_set96, uint8_t* path, uint8_t* p_group96, uint8_t* s_group192, uint8_t* h_group192) {
+  if (!c) return fail(BGV_E_INVALID_ARG, "null ctx");
+  if (int r = smb_check_args(b)) return r;
+  if (stats) memset(stats, 0, sizeof *stats);
+  const uint32_t n = b->n_sets, G = b->n_groups;
+  if (n == 0) return BGV_OK;
+  if (!set_valid) return fail(BGV_E_INVALID_ARG, "set_valid is NULL");
+  c->partial_pending = false;
+  HIPCHK(hipSetDevice(c->device));
+  active_guard ag(c->device);
+  const auto t0 = std::chrono::steady_clock::now();
+  const bool host = !b->on_device;
+  // the group offsets come to the host first: the segments are cut from this copy
+  std::vector<uint32_t> go((size_t)G + 1);
+  if (host) {
+    memcpy(go.data(), b->group_offsets, go.size() * 4);
+  } else {
+    HIPCHK(hipMemcpyAsync(go.data(), b->group_offsets, go.size() * 4, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(hipStreamSynchronize(c->st));
+  }
+  if (int r = smb_check_groups(b, go.data())) return r;
+
+  bits_args a;
+  if (int r = bits_setup(c, a, n, b->bits_len, b->n_indices, !host, true, c->st_pk)) return r;
+  c->bits_timed = false;
+  a.src = (const bits_src*)b->src; a.v.bits = b->bits; a.v.pk_indices = b->pk_indices;
+
+  sma_dev k;
+  memset(&k, 0, sizeof k);
+  k.n = n; k.G = G; k.n_raw = b->n_raw;
+  k.d_len = b->sig_len; k.d_msgs = b->msgs; k.d_sigs = b->sigs; k.d_raw = b->raw_pks; k.d_scalars = b->scalars;
+  k.draw_scalars = !b->scalars;
+  sma_segs sg;
+  sma_cut_segments(go, n, sg);
+  const uint32_t S = sg.S;
+  k.S = S; k.sg = &sg;
+  // staging: the segment tables always, the batch arrays of a host batch
+  stage_seg segs[12] = {
+      {sg.seg_off.data(), ((size_t)S + 1) * 4, (const void**)&k.d_seg_off, 0},
+      {sg.seg_group.data(), (size_t)S * 4, (const void**)&k.d_seg_group, 0},
+      {sg.group_seg.data(), ((size_t)G + 1) * 4, (const void**)&k.d_group_seg, 0},
+      {sg.iota.data(), ((size_t)S + 1) * 4, (const void**)&k.d_iota, 0},
+      {b->src, (size_t)n * sizeof(bits_src), (const void**)&a.src, 0},
+      {b->bits, (size_t)b->bits_len, (const void**)&a.v.bits, 0},
+      {b->pk_indices, (size_t)b->n_indices * 4, (const void**)&a.v.pk_indices, 0},
+      {b->msgs, (size_t)G * 32, (const void**)&k.d_msgs, 0},
+      {b->raw_pks, (size_t)b->n_raw * 96, (const void**)&k.d_raw, 0},
+      {b->scalars, b->scalars ? (size_t)n * 8 : 0, (const void**)&k.d_scalars, 0},
+      {b->sigs, (size_t)n * 192, (const void**)&k.d_sigs, 0},
+      {b->sig_len, (size_t)n * 4, (const void**)&k.d_len, 0},
+  };
+  size_t bytes = 0;
+  if (int r = stage_pack(c, segs, host ? 12 : 4, bytes)) return r;
+  if (host) {
+    // the contract, on the pinned copy the device will see; the plan's totals
+    // size the expansion and the gather's grid without a read-back
+    bits_view hv = a.v;
+    hv.bits = c->pin_in + segs[5].off;
+    hv.pk_indices = (const uint32_t*)(c->pin_in + segs[6].off);
+    bits_plan_out po;
+    if (int r = bits_check_sources(n, (const bits_src*)(c->pin_in + segs[4].off), hv, &po, nullptr)) return r;
+    if (b->scalars) {
+      const uint64_t* sc = (const uint64_t*)(c->pin_in + segs[9].off);
+      for (uint32_t i = 0; i < n; i++)
+        if (!sc[i]) return fail(BGV_E_INVALID_ARG, "scalars[%u] is zero", i);
+    }
+    c->pk_total = po.total;
+    c->bits_path.sets_complement = po.n_complement;
+    c->bits_path.keys_expanded = po.total;
+    c->bits_path.keys_gathered = po.gathered;
+    c->bits_extra_chunks = po.n_complement;
+    if (int r = stage_issue(c, bytes)) return r;
+    k.expand_count = true;
+  } else {
+    if (int r = stage_issue(c, bytes)) return r;
+    // an on-device batch: count and scan now, the 8 bytes of totals come back
+    // before the buffers and the gather's grid are sized (as bgv_verify_bits does)
+    bits_launch_count(c->st_pk, a);
+    HIPCHK(hipGetLastError());
+    if (int r = bits_read_totals(c, c->st_pk, a)) return r;
+  }
+  k.gathered = c->bits_path.keys_gathered;
+  if (int r = ensure_or_release_lines(c, c->bits_idx, k.gathered ? k.gathered : 1)) return r;
+  k.expand = &a;
+  k.d_po = c->bits_off.p;
+  k.d_idx = c->bits_idx.p;
+  k.win = a.win;
+  // as bits_layout: sum ceil(k_i / 32) + windows <= gathered / 32 + n + windows
+  k.chunk_bound = k.gathered / PK_CHUNK + n + c->bits_extra_chunks;
+  if (int r = sma_back(c, k, t0, set_valid, set_code, stats, pk_set96, p_group96, s_group192, h_group192)) return r;
+  if (path) {
+    memset(path, 0, n);
+    if (a.win) {
+      std::vector<pk_window> win(n);
+      HIPCHK(hipMemcpyAsync(win.data(), a.win, (size_t)n * sizeof(pk_window), hipMemcpyDeviceToHost, c->st));
+      HIPCHK(hipStreamSynchronize(c->st));
+      for (uint32_t i = 0; i < n; i++) path[i] = win[i].hi ? 1 : 0;
+    }
+  }
+  return BGV_OK;
+}
+
+int bgv_verify_same_message_bits(bgv_ctx* c, const bgv_smb_batch* b, uint8_t* set_valid, int32_t* set_code, bgv_sm_stats* stats) {
+  return smb_run(c, b, set_valid, set_code, stats, nullptr, nullptr, nullptr, nullptr, nullptr);
+}
+
+int bgv_debug_same_message_bits(bgv_ctx* c, const bgv_smb_batch* b, uint8_t* set_valid, int32_t* set_code, bgv_sm_stats* stats,
+                                uint8_t* pk_set96, uint8_t* path, uint8_t* p_group96, uint8_t* s_group192, uint8_t* h_group192) {
+  return smb_run(c, b, set_valid, set_code, stats, pk_set96, path, p_group96, s_group192, h_group192);
 }
 
 // ---- multi-GPU partials ---------------------------------------------------

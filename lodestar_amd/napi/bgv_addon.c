@@ -23,13 +23,14 @@
  *   verifySameMessage(ctx, smBatch) -> Promise<smResult>, verifySameMessageSync(ctx, smBatch) -> smResult
  *                                                bgv_verify_same_message (see "same-message batches" below)
  *   verifySameMessageAgg(ctx, smaBatch) -> Promise<smResult>, verifySameMessageAggSync(ctx, smaBatch) -> smResult
+ *   verifySameMessageBits(ctx, smbBatch) -> Promise<smResult>, verifySameMessageBitsSync(ctx, smbBatch) -> smResult
  *                                                bgv_verify_same_message_agg: the sets' keys are aggregates
  *   setIndexList(ctx, id, Uint32Array)           bgv_index_list_set: a resident index list (an epoch's shuffling,
  *                                                a sync committee); an empty array drops it
  *   indexListLen(ctx, id) -> number              bgv_index_list_len
  *   setIndexListSums(ctx, id, bool)              bgv_index_list_sums: build (or drop) the list's resident prefix sums
  *   indexListHasSums(ctx, id) -> boolean         bgv_index_list_has_sums
- *   bitsPathStats(ctx) -> {setsComplement, keysExpanded, keysGathered}   bgv_bits_path_stats (the last verifyBits)
+ *   bitsPathStats(ctx) -> {setsComplement, keysExpanded, keysGathered}   bgv_bits_path_stats (the last verifyBits / verifySameMessageBits)
  *   verifyBits(ctx, bitsBatch) -> Promise<result>, verifyBitsSync(ctx, bitsBatch) -> result
  *                                                bgv_verify_bits: sets given as (list, window, participation bits)
  *                                                or as explicit index runs (see "committee bitfields" below)
@@ -567,16 +568,21 @@ static napi_value VerifySync(napi_env env, napi_callback_info info) {
  *
  * verifySameMessageAgg / verifySameMessageAggSync (bgv_verify_same_message_agg): the same, with
  * pkOffsets: Uint32Array (n_sets + 1 entries, copied too) and pkIndices holding pkOffsets[n_sets] keys. */
-enum { S_GRP, S_PKI, S_MSG, S_SIG, S_LEN, S_RAW, S_PKO, S_FIELDS };
-static const char* SM_FIELD[S_FIELDS] = {"groupOffsets", "pkIndices", "msgs", "sigs", "sigLen", "rawPks", "pkOffsets"};
-static const napi_typedarray_type SM_FIELD_T[S_FIELDS] = {napi_uint32_array, napi_uint32_array, napi_uint8_array, napi_uint8_array,
-                                                          napi_uint32_array, napi_uint8_array,  napi_uint32_array};
+enum { S_GRP, S_PKI, S_MSG, S_SIG, S_LEN, S_RAW, S_PKO, S_SRC, S_BITS, S_FIELDS }; /* S_SRC on: verifySameMessageBits only */
+static const char* SM_FIELD[S_FIELDS] = {"groupOffsets", "pkIndices", "msgs", "sigs", "sigLen", "rawPks", "pkOffsets", "src", "bits"};
+static const napi_typedarray_type SM_FIELD_T[S_FIELDS] = {napi_uint32_array, napi_uint32_array, napi_uint8_array,
+                                                          napi_uint8_array,  napi_uint32_array, napi_uint8_array,
+                                                          napi_uint32_array, napi_uint32_array, napi_uint8_array};
 
 typedef struct {
   addon_ctx* c;
   bgv_sm_batch b;
-  int agg;          /* the sets' keys are aggregates: `ba` is the batch, `b` keeps the counts */
+  int agg;          /* 1: the sets' keys are aggregates: `ba` is the batch, `b` keeps the counts;
+                       2: ... given as committee sets: `bb` is the batch (verifySameMessageBits) */
   bgv_sma_batch ba;
+  bgv_smb_batch bb;
+  uint32_t* src_copy;
+  bgv_bits_path path; /* agg == 2: the path counters of the call */
   uint32_t* pk_off;
   uint32_t* group_off;
   uint8_t* valid;
@@ -597,6 +603,7 @@ static void sm_free(napi_env env, sm_job* j) {
   if (j->ctx_ref) napi_delete_reference(env, j->ctx_ref);
   free(j->group_off);
   free(j->pk_off);
+  free(j->src_copy);
   free(j->valid);
   free(j->codes);
 }
@@ -605,7 +612,7 @@ static int sm_read_batch(napi_env env, napi_value obj, sm_job* j, int pin) {
   void* p[S_FIELDS] = {0};
   size_t n[S_FIELDS] = {0};
   napi_value v[S_FIELDS];
-  for (int k = 0; k < S_FIELDS; k++) {
+  for (int k = 0; k < S_SRC; k++) {
     bool has = false;
     if (k == S_PKO && !j->agg) continue;
     napi_has_named_property(env, obj, SM_FIELD[k], &has);
@@ -659,7 +666,7 @@ static int sm_read_batch(napi_env env, napi_value obj, sm_job* j, int pin) {
     return -1;
   }
   if (pin)
-    for (int k = 0; k < S_FIELDS; k++)
+    for (int k = 0; k < S_SRC; k++)
       if (p[k] && k != S_GRP && k != S_PKO) napi_create_reference(env, v[k], 1, &j->refs[k]);
   j->b.group_offsets = j->group_off;
   j->b.pk_indices = (const uint32_t*)p[S_PKI];
@@ -686,6 +693,87 @@ static int sm_read_batch(napi_env env, napi_value obj, sm_job* j, int pin) {
   return 0;
 }
 
+/* verifySameMessageBits(ctx, batch) -> Promise<result>, verifySameMessageBitsSync(ctx, batch) -> result
+ * (bgv_verify_same_message_bits).  batch = {groupOffsets, src: Uint32Array (4 per set, as verifyBits), bits:
+ * Uint8Array, pkIndices: Uint32Array (keys of the explicit sets), msgs (32 B per GROUP), sigs, sigLen, rawPks?}.
+ * result as verifySameMessageAgg plus pubkeysAggregated, the participating keys from the call's path counters
+ * (the caller holds no index lists to count them from).  Ownership as for verifyBits: groupOffsets and src are
+ * copied at call time, the other typed arrays are pinned until completion. */
+static int smb_read_batch(napi_env env, napi_value obj, sm_job* j, int pin) {
+  void* p[S_FIELDS] = {0};
+  size_t n[S_FIELDS] = {0};
+  napi_value v[S_FIELDS];
+  for (int k = 0; k < S_FIELDS; k++) {
+    bool has = false;
+    if (k == S_PKO) continue;
+    napi_has_named_property(env, obj, SM_FIELD[k], &has);
+    if (!has) {
+      if (k == S_RAW) continue;
+      napi_throw_type_error(env, NULL, "batch field missing");
+      return -1;
+    }
+    napi_get_named_property(env, obj, SM_FIELD[k], &v[k]);
+    if (typed(env, v[k], SM_FIELD_T[k], &p[k], &n[k])) {
+      napi_throw_type_error(env, NULL, "batch field has the wrong typed-array type");
+      return -1;
+    }
+  }
+  if (n[S_GRP] < 1 || n[S_SRC] % 4) {
+    napi_throw_range_error(env, NULL, "groupOffsets needs at least one entry, src four entries per set");
+    return -1;
+  }
+  const size_t n_sets = n[S_SRC] / 4;
+  if (n_sets > 0xffffffffull || n[S_BITS] > 0xffffffffull || n[S_PKI] > 0xffffffffull) {
+    napi_throw_range_error(env, NULL, "bits batch too large");
+    return -1;
+  }
+  memset(&j->b, 0, sizeof j->b);
+  j->b.n_groups = (uint32_t)(n[S_GRP] - 1);
+  j->b.n_sets = (uint32_t)n_sets;
+  j->group_off = (uint32_t*)malloc(4 * n[S_GRP]);
+  j->src_copy = (uint32_t*)malloc(n[S_SRC] ? 4 * n[S_SRC] : 4);
+  if (!j->group_off || !j->src_copy) {
+    napi_throw_error(env, NULL, "out of memory");
+    return -1;
+  }
+  memcpy(j->group_off, p[S_GRP], 4 * n[S_GRP]);
+  if (n[S_SRC]) memcpy(j->src_copy, p[S_SRC], 4 * n[S_SRC]);
+  if (j->group_off[j->b.n_groups] != n_sets) {
+    napi_throw_range_error(env, NULL, "groupOffsets must end at the set count of src");
+    return -1;
+  }
+  if (n[S_MSG] < 32ull * j->b.n_groups || n[S_SIG] < 192ull * n_sets || n[S_LEN] < n_sets) {
+    napi_throw_range_error(env, NULL, "msgs / sigs / sigLen shorter than the group or set count");
+    return -1;
+  }
+  j->valid = (uint8_t*)calloc(n_sets ? n_sets : 1, 1);
+  j->codes = (int32_t*)calloc(n_sets ? n_sets : 1, 4);
+  if (!j->valid || !j->codes) {
+    napi_throw_error(env, NULL, "out of memory");
+    return -1;
+  }
+  if (pin)
+    for (int k = 0; k < S_FIELDS; k++)
+      if (p[k] && k != S_GRP && k != S_SRC) napi_create_reference(env, v[k], 1, &j->refs[k]);
+  memset(&j->bb, 0, sizeof j->bb);
+  j->bb.n_sets = (uint32_t)n_sets;
+  j->bb.n_groups = j->b.n_groups;
+  j->bb.group_offsets = j->group_off;
+  j->bb.src = (const bgv_set_src*)j->src_copy;
+  j->bb.bits = (const uint8_t*)p[S_BITS];
+  j->bb.bits_len = (uint32_t)n[S_BITS];
+  j->bb.pk_indices = (const uint32_t*)p[S_PKI];
+  j->bb.n_indices = (uint32_t)n[S_PKI];
+  j->bb.raw_pks = (const uint8_t*)p[S_RAW];
+  j->bb.n_raw = (uint32_t)(n[S_RAW] / 96);
+  j->bb.msgs = (const uint8_t*)p[S_MSG];
+  j->bb.sigs = (const uint8_t*)p[S_SIG];
+  j->bb.sig_len = (const uint32_t*)p[S_LEN];
+  j->bb.scalars = NULL; /* drawn inside the library */
+  j->bb.on_device = 0;
+  return 0;
+}
+
 static void sm_run(sm_job* j) {
   pthread_mutex_lock(&j->c->mu);
   j->t_start_ms = now_ms();
@@ -693,8 +781,13 @@ static void sm_run(sm_job* j) {
     j->status = BGV_E_INVALID_ARG;
     snprintf(j->err, sizeof j->err, "QUEUE_ERROR_QUEUE_ABORTED");
   } else {
-    j->status = j->agg ? bgv_verify_same_message_agg(j->c->ctx, &j->ba, j->valid, j->codes, &j->stats)
-                       : bgv_verify_same_message(j->c->ctx, &j->b, j->valid, j->codes, &j->stats);
+    if (j->agg == 2) {
+      j->status = bgv_verify_same_message_bits(j->c->ctx, &j->bb, j->valid, j->codes, &j->stats);
+      if (j->status == BGV_OK) j->status = bgv_bits_path_stats(j->c->ctx, &j->path); /* under the same lock: this call's */
+    } else {
+      j->status = j->agg ? bgv_verify_same_message_agg(j->c->ctx, &j->ba, j->valid, j->codes, &j->stats)
+                         : bgv_verify_same_message(j->c->ctx, &j->b, j->valid, j->codes, &j->stats);
+    }
     if (j->status != BGV_OK) snprintf(j->err, sizeof j->err, "bgv error %d: %s", j->status, bgv_last_error());
   }
   j->t_end_ms = now_ms();
@@ -718,6 +811,10 @@ static napi_value sm_result(napi_env env, const sm_job* j) {
   for (size_t k = 0; k < sizeof u / sizeof u[0]; k++) {
     napi_create_uint32(env, u[k].val, &v);
     napi_set_named_property(env, o, u[k].name, v);
+  }
+  if (j->agg == 2) {
+    napi_create_uint32(env, j->path.keys_expanded, &v);
+    napi_set_named_property(env, o, "pubkeysAggregated", v);
   }
   napi_create_double(env, (double)j->stats.total_ms, &v);
   napi_set_named_property(env, o, "deviceMs", v);
@@ -761,7 +858,7 @@ static napi_value sm_async(napi_env env, napi_callback_info info, int agg) {
   sm_job* j = (sm_job*)calloc(1, sizeof *j);
   j->c = c;
   j->agg = agg;
-  if (sm_read_batch(env, a[1], j, 1)) {
+  if (agg == 2 ? smb_read_batch(env, a[1], j, 1) : sm_read_batch(env, a[1], j, 1)) {
     sm_free(env, j);
     free(j);
     return NULL;
@@ -769,8 +866,8 @@ static napi_value sm_async(napi_env env, napi_callback_info info, int agg) {
   napi_create_reference(env, a[0], 1, &j->ctx_ref); /* the context outlives its queued work */
   napi_value promise, name;
   NAPI_CALL(env, napi_create_promise(env, &j->deferred, &promise));
-  NAPI_CALL(env, napi_create_string_utf8(env, agg ? "bgv_verify_same_message_agg" : "bgv_verify_same_message", NAPI_AUTO_LENGTH,
-                                         &name));
+  NAPI_CALL(env, napi_create_string_utf8(env, agg == 2 ? "bgv_verify_same_message_bits" : agg ? "bgv_verify_same_message_agg" : "bgv_verify_same_message",
+                                         NAPI_AUTO_LENGTH, &name));
   NAPI_CALL(env, napi_create_async_work(env, NULL, name, sm_exec, sm_done, j, &j->work));
   NAPI_CALL(env, napi_queue_async_work(env, j->work));
   return promise;
@@ -787,7 +884,7 @@ static napi_value sm_sync(napi_env env, napi_callback_info info, int agg) {
   j.c = c;
   j.agg = agg;
   napi_value r = NULL;
-  if (!sm_read_batch(env, a[1], &j, 0)) {
+  if (!(agg == 2 ? smb_read_batch(env, a[1], &j, 0) : sm_read_batch(env, a[1], &j, 0))) {
     sm_run(&j);
     if (j.status != BGV_OK) napi_throw_error(env, NULL, j.err);
     else r = sm_result(env, &j);
@@ -800,6 +897,8 @@ static napi_value VerifySameMessage(napi_env env, napi_callback_info info) { ret
 static napi_value VerifySameMessageSync(napi_env env, napi_callback_info info) { return sm_sync(env, info, 0); }
 static napi_value VerifySameMessageAgg(napi_env env, napi_callback_info info) { return sm_async(env, info, 1); }
 static napi_value VerifySameMessageAggSync(napi_env env, napi_callback_info info) { return sm_sync(env, info, 1); }
+static napi_value VerifySameMessageBits(napi_env env, napi_callback_info info) { return sm_async(env, info, 2); }
+static napi_value VerifySameMessageBitsSync(napi_env env, napi_callback_info info) { return sm_sync(env, info, 2); }
 
 /* ------------------------------------------------------- committee bitfields
  * verifyBits(ctx, batch) -> Promise<result>, verifyBitsSync(ctx, batch) -> result (bgv_verify_bits).
@@ -1034,6 +1133,8 @@ static napi_value Init(napi_env env, napi_value exports) {
       {"verifySameMessageSync", NULL, VerifySameMessageSync, NULL, NULL, NULL, napi_enumerable, NULL},
       {"verifySameMessageAgg", NULL, VerifySameMessageAgg, NULL, NULL, NULL, napi_enumerable, NULL},
       {"verifySameMessageAggSync", NULL, VerifySameMessageAggSync, NULL, NULL, NULL, napi_enumerable, NULL},
+      {"verifySameMessageBits", NULL, VerifySameMessageBits, NULL, NULL, NULL, napi_enumerable, NULL},
+      {"verifySameMessageBitsSync", NULL, VerifySameMessageBitsSync, NULL, NULL, NULL, napi_enumerable, NULL},
       {"setIndexList", NULL, SetIndexList, NULL, NULL, NULL, napi_enumerable, NULL},
       {"indexListLen", NULL, IndexListLen, NULL, NULL, NULL, napi_enumerable, NULL},
       {"setIndexListSums", NULL, SetIndexListSums, NULL, NULL, NULL, napi_enumerable, NULL},

@@ -331,10 +331,20 @@ function encodeSameMessage(groups) {
 }
 
 // the caller-side checks of one verifyAggregateSetsSameMessage call: every set is
-// {publicKeys: [{index} | {raw} | validator index, ...], signature} with at least one key
+// {publicKeys: [{index} | {raw} | validator index, ...], signature} with at least one key,
+// or a committee set {committee: {list, offset, length}, bits, signature} (the checks of checkSets)
 function checkAggregateSameMessage(sets, message) {
   if (!message || message.length !== 32) throw Error("signingRoot must be 32 bytes");
   for (const s of sets) {
+    if (s && s.committee) {
+      const c = s.committee;
+      if (!s.bits || !(c.list >= 0 && c.list < MAX_INDEX_LISTS)) throw Error("committee set without a committee, bits or a valid list id");
+      if (!(c.offset >= 0) || !(c.length >= 0) || c.offset + c.length > 0xffffffff || s.bits.length !== ((c.length + 7) >> 3)) {
+        throw Error(`committee set: ${s.bits.length} bitfield bytes for ${c.length} members`);
+      }
+      if (!s.bits.some((b) => b !== 0)) throw Error("EMPTY_AGGREGATE_ARRAY");
+      continue;
+    }
     if (!s || !s.publicKeys || s.publicKeys.length === 0) throw Error("EMPTY_AGGREGATE_ARRAY");
     for (const pk of s.publicKeys) {
       if (pk === null || pk === undefined) throw Error("EMPTY_AGGREGATE_ARRAY");
@@ -377,6 +387,59 @@ function encodeSameMessageAgg(groups) {
     groupOffsets[gi + 1] = i;
   });
   return {groupOffsets, pkOffsets, pkIndices, msgs, sigs, sigLen, rawPks};
+}
+
+function hasCommitteeKeys(groups) {
+  return groups.some((g) => g.sets.some((s) => !!s.committee));
+}
+
+// groups [{message, sets}] -> the arrays of include/bgv.h bgv_smb_batch: a committee set
+// {committee: {list, offset, length}, bits, signature} becomes a list source over the
+// byte-packed bitfields, a set {publicKeys, signature} a BGV_SRC_EXPLICIT run of pkIndices
+function encodeSameMessageBits(groups) {
+  let n = 0, nKeys = 0, nRaw = 0, nBits = 0;
+  for (const g of groups) {
+    if (g.sets.length === 0) throw Error("Empty signature set");
+    n += g.sets.length;
+    for (const s of g.sets) {
+      if (s.committee) { nBits += s.bits.length; continue; }
+      if (s.publicKeys.length === 0) throw Error("EMPTY_AGGREGATE_ARRAY");
+      nKeys += s.publicKeys.length;
+      for (const pk of s.publicKeys) if (typeof pk !== "number" && pk.raw) nRaw++;
+    }
+  }
+  const groupOffsets = new Uint32Array(groups.length + 1);
+  const src = new Uint32Array(4 * n);
+  const bits = new Uint8Array(nBits);
+  const pkIndices = new Uint32Array(nKeys);
+  const rawPks = new Uint8Array(Math.max(nRaw, 1) * 96);
+  const msgs = new Uint8Array(Math.max(groups.length, 1) * 32);
+  const sigs = new Uint8Array(Math.max(n, 1) * 192);
+  const sigLen = new Uint32Array(Math.max(n, 1));
+  let i = 0, k = 0, r = 0, b = 0;
+  groups.forEach((g, gi) => {
+    msgs.set(g.message, 32 * gi);
+    for (const s of g.sets) {
+      if (s.committee) {
+        const c = s.committee;
+        if (s.bits.length !== ((c.length + 7) >> 3)) throw Error(`committee set: ${s.bits.length} bitfield bytes for ${c.length} members`);
+        src.set([c.list, c.offset, c.length, b], 4 * i);
+        bits.set(s.bits, b);
+        b += s.bits.length;
+      } else {
+        src.set([SRC_EXPLICIT, k, s.publicKeys.length, 0], 4 * i);
+        for (const pk of s.publicKeys) {
+          if (typeof pk === "number") pkIndices[k++] = pk >>> 0;
+          else if (pk.raw) { pkIndices[k++] = (RAW_BIT | r) >>> 0; rawPks.set(pk.raw, 96 * r++); } else pkIndices[k++] = pk.index >>> 0;
+        }
+      }
+      sigLen[i] = s.signature.length;
+      if (s.signature.length === 96 || s.signature.length === 192) sigs.set(s.signature, 192 * i);
+      i++;
+    }
+    groupOffsets[gi + 1] = i;
+  });
+  return {groupOffsets, src, bits, pkIndices, msgs, sigs, sigLen, rawPks};
 }
 
 // device work of a job in Montgomery Fp products (lodestar_amd/dist.py
@@ -709,11 +772,17 @@ class BlsGpuVerifier {
     try {
       const {groups, where} = mergeSameMessage(jobs);
       const {best} = this.idleContexts();
-      const batch = encodeSameMessageAgg(groups);
+      // the routing rule: a merged call that holds a committee set goes through
+      // bgv_verify_same_message_bits (the key count comes from the device); any
+      // other call takes exactly the path it took before
+      const bits = hasCommitteeKeys(groups);
+      const batch = bits ? encodeSameMessageBits(groups) : encodeSameMessageAgg(groups);
       this.smaDeviceCalls++;
       m.lodestar_bls_thread_pool_same_message_agg_sig_sets_started_total += n;
-      m.lodestar_bls_aggregated_pubkeys_total += batch.pkOffsets[n];
-      const res = await addon.verifySameMessageAgg(this.ctxs[best >= 0 ? best : 0], batch);
+      if (!bits) m.lodestar_bls_aggregated_pubkeys_total += batch.pkOffsets[n];
+      const ctx = this.ctxs[best >= 0 ? best : 0];
+      const res = await (bits ? addon.verifySameMessageBits(ctx, batch) : addon.verifySameMessageAgg(ctx, batch));
+      if (bits) m.lodestar_bls_aggregated_pubkeys_total += res.pubkeysAggregated;
       m.lodestar_bls_thread_pool_same_message_agg_retries_total += res.groupsRetried;
       m.lodestar_bls_thread_pool_time_seconds_sum += (res.workerEndMs - res.workerStartMs) / 1000;
       jobs.forEach((job, k) => job.resolve(Array.from(res.valid.subarray(where[k][0], where[k][1]), (v) => v === 1)));
@@ -1057,7 +1126,13 @@ class BlsGpuSingleThreadVerifier {
     if (this.closed) throw new QueueError();
     if (sets.length === 0) return [];
     checkAggregateSameMessage(sets, message);
-    const batch = encodeSameMessageAgg([{message, sets}]);
+    const groups = [{message, sets}];
+    if (hasCommitteeKeys(groups)) {  // the routing rule of runSameMessageAgg
+      const res = addon.verifySameMessageBitsSync(this.ctx, encodeSameMessageBits(groups));
+      this.metrics.lodestar_bls_aggregated_pubkeys_total += res.pubkeysAggregated;
+      return Array.from(res.valid, (v) => v === 1);
+    }
+    const batch = encodeSameMessageAgg(groups);
     this.metrics.lodestar_bls_aggregated_pubkeys_total += batch.pkOffsets[sets.length];
     const res = addon.verifySameMessageAggSync(this.ctx, batch);
     return Array.from(res.valid, (v) => v === 1);
@@ -1077,5 +1152,6 @@ class BlsGpuSingleThreadVerifier {
 module.exports = {
   addon, BlsGpuVerifier, BlsGpuSingleThreadVerifier, QueueError, sourceHash, checkBuildId, chunkifyMaximizeChunkSize, encodeJobs, checkSets, shardJobs, jobWork,
   encodeJobsBits, hasCommitteeSets, encodeSameMessage, mergeSameMessage, checkSameMessage, encodeSameMessageAgg, checkAggregateSameMessage,
+  encodeSameMessageBits, hasCommitteeKeys,
   MAX_BUFFERED_SIGS, MAX_BUFFER_WAIT_MS, MAX_JOBS_CAN_ACCEPT_WORK, SHARD_MIN_SETS, PRIORITY_CUS, RESERVED_CAP, CONTEXTS_PER_DEVICE,
 };

@@ -57,6 +57,7 @@ EXPORTS = [
     "bgv_bits_expand_ms",
     "bgv_index_list_sums", "bgv_index_list_has_sums", "bgv_bits_path_stats", "bgv_bits_plan", "bgv_debug_bits_keys",
     "bgv_debug_index_list_sums", "bgv_index_list_sums_ms",
+    "bgv_verify_same_message_bits", "bgv_smb_check", "bgv_debug_same_message_bits",
 ]
 MAX_INDEX_LISTS = 8
 SRC_EXPLICIT = 0xFFFFFFFF
@@ -168,6 +169,28 @@ class BgvBitsBatch(ctypes.Structure):
         ("n_sets", ctypes.c_uint32),
         ("n_jobs", ctypes.c_uint32),
         ("job_offsets", ctypes.c_void_p),
+        ("src", ctypes.c_void_p),
+        ("bits", ctypes.c_void_p),
+        ("bits_len", ctypes.c_uint32),
+        ("pk_indices", ctypes.c_void_p),
+        ("n_indices", ctypes.c_uint32),
+        ("raw_pks", ctypes.c_void_p),
+        ("n_raw", ctypes.c_uint32),
+        ("msgs", ctypes.c_void_p),
+        ("sigs", ctypes.c_void_p),
+        ("sig_len", ctypes.c_void_p),
+        ("scalars", ctypes.c_void_p),
+        ("on_device", ctypes.c_uint32),
+    ]
+
+
+class BgvSmbBatch(ctypes.Structure):
+    """bgv_smb_batch (include/bgv.h): sets grouped by message, their keys given
+    as committee bitfields over resident index lists or as explicit index runs."""
+    _fields_ = [
+        ("n_sets", ctypes.c_uint32),
+        ("n_groups", ctypes.c_uint32),
+        ("group_offsets", ctypes.c_void_p),
         ("src", ctypes.c_void_p),
         ("bits", ctypes.c_void_p),
         ("bits_len", ctypes.c_uint32),
@@ -341,6 +364,10 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
             "bgv_bits_plan": ([ctypes.POINTER(BgvBitsBatch), P, P, P, ctypes.POINTER(ctypes.c_uint64)], ctypes.c_int),
             "bgv_debug_bits_keys": ([P, ctypes.POINTER(BgvBitsBatch), P, P, P], ctypes.c_int),
             "bgv_debug_index_list_sums": ([P, u32, u32, u32, P], ctypes.c_int),
+            "bgv_verify_same_message_bits": ([P, ctypes.POINTER(BgvSmbBatch), P, P, ctypes.POINTER(BgvSmStats)], ctypes.c_int),
+            "bgv_smb_check": ([ctypes.POINTER(BgvSmbBatch), P], ctypes.c_int),
+            "bgv_debug_same_message_bits": ([P, ctypes.POINTER(BgvSmbBatch), P, P, ctypes.POINTER(BgvSmStats), P, P, P, P, P],
+                                            ctypes.c_int),
         }
         for name, (args, res) in sig.items():
             fn = getattr(lib, name)
@@ -437,6 +464,43 @@ def bits_check(arrays: dict, list_len, on_device: bool = False) -> tuple[int, st
     ll = np.zeros(MAX_INDEX_LISTS, np.uint32)
     ll[: len(list_len)] = np.asarray(list_len, np.uint32)
     st = lib.bgv_bits_check(ctypes.byref(b), ll.ctypes.data)
+    return st, ("" if st == BGV_OK else lib.bgv_last_error().decode())
+
+
+def make_smb_batch(arrays: dict, on_device: bool = False, sync_inputs: bool = True) -> BgvSmbBatch:
+    """arrays as verifier.encode_same_message_bits returns them: the groups of a
+    same-message batch, the sources of a bits batch; bits_len and n_indices
+    default to the arrays' sizes"""
+    b = BgvSmbBatch()
+    b.n_sets = int(arrays["n_sets"])
+    b.n_groups = int(arrays["n_groups"])
+    b.group_offsets = _ptr(arrays["group_offsets"])
+    b.src = _ptr(arrays["src"])
+    b.bits = _ptr(arrays.get("bits"))
+    b.bits_len = int(arrays["bits_len"]) if "bits_len" in arrays else _count(arrays.get("bits"))
+    b.pk_indices = _ptr(arrays.get("pk_indices"))
+    b.n_indices = int(arrays["n_indices"]) if "n_indices" in arrays else _count(arrays.get("pk_indices"))
+    b.raw_pks = _ptr(arrays.get("raw_pks"))
+    b.n_raw = int(arrays.get("n_raw", 0))
+    b.msgs = _ptr(arrays.get("msgs"))
+    b.sigs = _ptr(arrays.get("sigs"))
+    b.sig_len = _ptr(arrays.get("sig_len"))
+    b.scalars = _ptr(arrays.get("scalars"))
+    b.on_device = 1 if on_device else 0
+    if on_device and sync_inputs:
+        _sync_producers(arrays)
+    return b
+
+
+def smb_check(arrays: dict, list_len, on_device: bool = False) -> tuple[int, str]:
+    """bgv_smb_check: the host-side contract of bgv_verify_same_message_bits,
+    without a device.  list_len: the lengths of the index lists (0: not set).
+    Returns (status, bgv_last_error() text); the text is empty for BGV_OK."""
+    lib = load_library()
+    b = make_smb_batch(arrays, on_device, sync_inputs=False)
+    ll = np.zeros(MAX_INDEX_LISTS, np.uint32)
+    ll[: len(list_len)] = np.asarray(list_len, np.uint32)
+    st = lib.bgv_smb_check(ctypes.byref(b), ll.ctypes.data)
     return st, ("" if st == BGV_OK else lib.bgv_last_error().decode())
 
 
@@ -651,6 +715,38 @@ class Device:
         return {"set_valid": ok[:n].astype(bool), "set_code": sc[:n], "pk_set": ps[:n], "p_group": pg[:G],
                 "s_group": sg[:G], "h_group": hg[:G], "stats": self.last_sm_stats.as_dict()}
 
+    make_smb_batch = staticmethod(make_smb_batch)
+
+    def verify_same_message_bits(self, arrays: dict, on_device: bool = False, sync_inputs: bool = True):
+        """bgv_verify_same_message_bits: (set_valid bool[n_sets], set_code int32[n_sets]);
+        the counters of the call are left in last_sm_stats, its key counts in bits_path_stats()"""
+        b = make_smb_batch(arrays, on_device, sync_inputs)
+        ok = np.zeros(max(b.n_sets, 1), dtype=np.uint8)
+        sc = np.zeros(max(b.n_sets, 1), dtype=np.int32)
+        self.last_sm_stats = BgvSmStats()
+        self._check(self.lib.bgv_verify_same_message_bits(self.h, ctypes.byref(b), ok.ctypes.data, sc.ctypes.data,
+                                                          ctypes.byref(self.last_sm_stats)))
+        return ok[: b.n_sets].astype(bool), sc[: b.n_sets]
+
+    def debug_same_message_bits(self, arrays: dict, on_device: bool = False) -> dict:
+        """bgv_debug_same_message_bits (test only): the outputs of debug_same_message_agg
+        plus path uint8[n_sets] (1: complement path)"""
+        b = make_smb_batch(arrays, on_device)
+        n, G = b.n_sets, b.n_groups
+        ok = np.zeros(max(n, 1), dtype=np.uint8)
+        sc = np.zeros(max(n, 1), dtype=np.int32)
+        ps = np.zeros((max(n, 1), 96), np.uint8)
+        path = np.zeros(max(n, 1), np.uint8)
+        pg = np.zeros((max(G, 1), 96), np.uint8)
+        sg = np.zeros((max(G, 1), 192), np.uint8)
+        hg = np.zeros((max(G, 1), 192), np.uint8)
+        self.last_sm_stats = BgvSmStats()
+        self._check(self.lib.bgv_debug_same_message_bits(self.h, ctypes.byref(b), ok.ctypes.data, sc.ctypes.data,
+                                                         ctypes.byref(self.last_sm_stats), ps.ctypes.data, path.ctypes.data,
+                                                         pg.ctypes.data, sg.ctypes.data, hg.ctypes.data))
+        return {"set_valid": ok[:n].astype(bool), "set_code": sc[:n], "pk_set": ps[:n], "path": path[:n], "p_group": pg[:G],
+                "s_group": sg[:G], "h_group": hg[:G], "stats": self.last_sm_stats.as_dict()}
+
     # ------------------------------------------- committee bitfields (bgv_verify_bits)
     def index_list_set(self, list_id: int, indices) -> None:
         """bgv_index_list_set: replace resident index list list_id (an empty one drops it)"""
@@ -678,7 +774,8 @@ class Device:
         return bool(has.value)
 
     def bits_path_stats(self) -> dict:
-        """bgv_bits_path_stats: {sets_complement, keys_expanded, keys_gathered} of the last verify_bits"""
+        """bgv_bits_path_stats: {sets_complement, keys_expanded, keys_gathered} of the last
+        verify_bits or verify_same_message_bits"""
         out = BgvBitsPath()
         self._check(self.lib.bgv_bits_path_stats(self.h, ctypes.byref(out)))
         return out.as_dict()

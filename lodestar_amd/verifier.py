@@ -130,6 +130,16 @@ class CommitteeRef:
     length: int
 
 
+@dataclass(frozen=True)
+class CommitteeKeys:
+    """The keys of one set of verify_aggregate_sets_same_message given as a
+    committee and its participation bits, in place of a pubkey list: the members
+    of ``committee`` whose bit is set (ceil(length / 8) bytes, SSZ bit order)."""
+
+    committee: CommitteeRef
+    bits: bytes
+
+
 @dataclass
 class VerifySignatureOpts:
     batchable: bool = False
@@ -626,6 +636,15 @@ def check_aggregate_same_message(sets, message: bytes) -> None:
     if len(message) != 32:
         raise BlsError("signingRoot must be 32 bytes")
     for pks, _sig in sets:
+        if isinstance(pks, CommitteeKeys):  # the checks of a committee set in check_sets
+            c = pks.committee
+            if c is None or pks.bits is None or not (0 <= c.list_id < native.MAX_INDEX_LISTS):
+                raise BlsError("committee set without a committee, bits or a valid list id")
+            if c.offset < 0 or c.length < 0 or c.offset + c.length > 0xFFFFFFFF or len(pks.bits) != (c.length + 7) // 8:
+                raise BlsError(f"committee set: {len(pks.bits)} bitfield bytes for {c.length} members")
+            if not any(pks.bits):
+                raise BlsError("EMPTY_AGGREGATE_ARRAY")
+            continue
         if pks is None or len(pks) == 0:
             raise BlsError("EMPTY_AGGREGATE_ARRAY")
         for pk in pks:
@@ -695,12 +714,98 @@ def encode_same_message_agg(groups, scalars: np.ndarray | None = None) -> dict:
     }
 
 
+def has_committee_keys(groups) -> bool:
+    return any(isinstance(pks, CommitteeKeys) for _m, sets in groups for pks, _sig in sets)
+
+
+def encode_same_message_bits(groups, scalars: np.ndarray | None = None) -> dict:
+    """Flatten groups [(message, [(keys, signature), ...]), ...] into the arrays
+    of bgv_smb_batch (include/bgv.h): `keys` is a CommitteeKeys (a list source
+    over the packed bitfields) or a pubkey list as encode_same_message_agg takes
+    it (a BGV_SRC_EXPLICIT run of pk_indices)."""
+    n = sum(len(g[1]) for g in groups)
+    G = len(groups)
+    off = [0]
+    idx: list[int] = []
+    raw: list[bytes] = []
+    raw_pos: dict[bytes, int] = {}
+    bits = bytearray()
+    src = np.zeros(max(n, 1), dtype=native.SET_SRC_DTYPE)
+    msgs = np.zeros((max(G, 1), 32), dtype=np.uint8)
+    sigs = np.zeros((max(n, 1), 192), dtype=np.uint8)
+    sig_len = np.zeros(max(n, 1), dtype=np.uint32)
+    i = 0
+    for g, (message, sets) in enumerate(groups):
+        if len(sets) == 0:
+            raise BlsError("Empty signature set", 10)
+        if len(message) != 32:
+            raise BlsError("signingRoot must be 32 bytes")
+        msgs[g] = np.frombuffer(bytes(message), dtype=np.uint8)
+        for pks, sig in sets:
+            if isinstance(pks, CommitteeKeys):
+                c = pks.committee
+                if len(pks.bits) != (c.length + 7) // 8:
+                    raise BlsError(f"committee set: {len(pks.bits)} bitfield bytes for {c.length} members")
+                src[i] = (c.list_id, c.offset, c.length, len(bits))
+                bits += pks.bits
+            else:
+                if len(pks) == 0:
+                    raise BlsError("EMPTY_AGGREGATE_ARRAY")
+                src[i] = (native.SRC_EXPLICIT, len(idx), len(pks), 0)
+                for pk in _as_pubkeys(pks):
+                    if pk.index is not None:
+                        idx.append(pk.index)
+                    else:
+                        r = pk.raw if len(pk.raw) == 96 else _decompress_raw48(pk.raw)
+                        if r not in raw_pos:
+                            raw_pos[r] = len(raw)
+                            raw.append(r)
+                        idx.append(0x80000000 | raw_pos[r])
+            sl = len(sig)
+            sig_len[i] = sl
+            if sl in (96, 192):
+                sigs[i, :sl] = np.frombuffer(bytes(sig), dtype=np.uint8)
+            i += 1
+        off.append(i)
+    return {
+        "n_sets": n,
+        "n_groups": G,
+        "group_offsets": np.array(off, dtype=np.uint32),
+        "src": src,
+        "bits": np.frombuffer(bytes(bits), dtype=np.uint8).copy() if bits else np.zeros(1, np.uint8),
+        "bits_len": len(bits),
+        "pk_indices": np.array(idx if idx else [0], dtype=np.uint32),
+        "n_indices": len(idx),
+        "raw_pks": np.frombuffer(b"".join(raw), dtype=np.uint8).copy() if raw else None,
+        "n_raw": len(raw),
+        "msgs": msgs,
+        "sigs": sigs,
+        "sig_len": sig_len,
+        "scalars": scalars,
+    }
+
+
 def run_same_message_agg_calls(device, calls, scalars_for=None, metrics: dict | None = None) -> list:
-    """One device call (Device.verify_same_message_agg) for the merged calls
-    (merge_same_message: one group per call, equal messages share one);
-    returns list[bool] per call."""
+    """One device call for the merged calls (merge_same_message: one group per
+    call, equal messages share one); returns list[bool] per call.  The routing
+    rule: a merged call that holds a committee set goes through
+    Device.verify_same_message_bits (encode_same_message_bits arrays; the key
+    count comes from the device's path counters); any other call takes exactly
+    the path it took before (encode_same_message_agg, Device.verify_same_message_agg)."""
     groups, where = merge_same_message(calls)
     n = sum(len(g[1]) for g in groups)
+    if has_committee_keys(groups):
+        arrays = encode_same_message_bits(groups, scalars_for(n) if scalars_for else None)
+        ok, _codes = device.verify_same_message_bits(arrays)
+        if metrics is not None:
+            st = getattr(device, "last_sm_stats", None)
+            metrics["same_message_agg_sets_started"] = metrics.get("same_message_agg_sets_started", 0) + n
+            metrics["same_message_agg_retries"] = (metrics.get("same_message_agg_retries", 0)
+                                                   + (int(st.groups_retried) if st is not None else 0))
+            metrics["aggregated_pubkeys_total"] = (metrics.get("aggregated_pubkeys_total", 0)
+                                                   + int(device.bits_path_stats()["keys_expanded"]))
+        ok = [bool(x) for x in ok]
+        return [ok[w] for w in where]
     arrays = encode_same_message_agg(groups, scalars_for(n) if scalars_for else None)
     ok, _codes = device.verify_same_message_agg(arrays)
     if metrics is not None:
@@ -844,7 +949,10 @@ class BlsGpuVerifier:
         committee and data); one boolean per set, False for a rejected set.
         Batchable calls wait in a buffer of their own, apart from the single-key
         one, and are merged into one device call
-        (bgv_verify_same_message_agg), one group per call."""
+        (bgv_verify_same_message_agg), one group per call.  A set's `pubkeys`
+        may be a CommitteeKeys (a committee of a resident index list and its
+        participation bits): a merged call that holds one goes through
+        bgv_verify_same_message_bits (run_same_message_agg_calls)."""
         opts = opts or VerifySignatureOpts()
         sets = list(sets)
         if not sets:

@@ -154,6 +154,11 @@ struct bgv_ctx {
   uint32_t bits_extra_chunks = 0;     // window chunks of the last bits batch (an upper bound for on-device batches)
   hipEvent_t ev_bits[2] = {};         // around the expansion kernels (timed runs)
   bool bits_timed = false;
+  // message classes of a bulk batch (bgv_cfg.hash_dedup, bgv_dedup.hip)
+  dbuf<uint32_t> msg_rep, msg_uniq, msg_tab, msg_cnt;
+  msg_classes mc = {};                // the batch's view of them (work_alloc); n_sets == 0: no class pass
+  bgv_hash_path hash_path = {};       // bgv_hash_stats
+  bool hash_pending = false;          // hash_path.hashes is still the device's n_uniq: fetched with the results
   // microbench scratch
   dbuf<fp_t> mb_fp;
   dbuf<uint64_t> mb_u64;
@@ -199,7 +204,7 @@ void bgv_cfg_default(bgv_cfg* cfg) {
   memset(cfg, 0, sizeof *cfg);
   cfg->struct_size = sizeof *cfg;
   cfg->split = cfg->miller = cfg->msm = cfg->prefold = cfg->lines = cfg->defer_pct = cfg->timing = cfg->clear_lanes = -1;
-  cfg->miller_kv = -1;
+  cfg->miller_kv = cfg->hash_dedup = -1;
   cfg->job_lanes = cfg->pairs = cfg->cu_split = 0;
 }
 
@@ -228,6 +233,7 @@ int bgv_open_cfg(int device, const bgv_cfg* cfg, bgv_ctx** out) {
     if (!tri_ok(k.prefold)) return fail(BGV_E_INVALID_ARG, "bgv_cfg.prefold %d", k.prefold);
     if (!tri_ok(k.lines)) return fail(BGV_E_INVALID_ARG, "bgv_cfg.lines %d", k.lines);
     if (!tri_ok(k.timing)) return fail(BGV_E_INVALID_ARG, "bgv_cfg.timing %d", k.timing);
+    if (!tri_ok(k.hash_dedup)) return fail(BGV_E_INVALID_ARG, "bgv_cfg.hash_dedup %d", k.hash_dedup);
     if (k.cu_split < -64 || k.cu_split > 64) return fail(BGV_E_INVALID_ARG, "bgv_cfg.cu_split %d (|N| <= 64 CUs)", k.cu_split);
     // two pairs per item exist only in the one-lane loop
     if (k.pairs >= 2 && k.miller != -1 && k.miller != 1)
@@ -328,6 +334,7 @@ int bgv_close(bgv_ctx* c) {
   for (auto& l : c->idx_sums)
     if (l) (void)hipFree(l);
   c->bits_off.release(); c->bits_idx.release(); c->bits_win.release();
+  c->msg_rep.release(); c->msg_uniq.release(); c->msg_tab.release(); c->msg_cnt.release();
   if (c->pin_in) (void)hipHostFree(c->pin_in);
   if (c->pin_out) (void)hipHostFree(c->pin_out);
   if (c->table) (void)hipFree(c->table);
@@ -819,6 +826,21 @@ static int prepare_layout(bgv_ctx* c, dev_batch& d, const uint64_t* scalars, boo
 
 static int work_alloc_once(bgv_ctx* c, const dev_batch& d, dev_work& w);
 
+// Message classes (bgv_cfg.hash_dedup): the bulk layout only.  A latency-mode
+// batch keeps its early two-lane maps and cooperative clearing: its hash heads
+// the critical path and is a wave or less per SIMD, where 64 hashes take as
+// long as 1,024 (DESIGN.md sections 3c, 3g).  Auto (-1) means OFF, callers opt
+// in with 1: on the C4 segment with every root distinct the pass costs nothing
+// alone (35.9 against 36.0 ms, inside the spread) but 2.3 ms per batch with
+// three batches in flight (35.1 against 32.8 ms, spread 1.0 ms), where its
+// set-up kernels queue behind the other batches' waves; with half of the roots
+// repeated it gains 1.4 ms alone and 0.75 ms in flight, with three quarters
+// 4.5 and 3.4 ms.
+// The table's slot count is a uint32_t power of two >= 2 n_sets.
+static bool hash_dedup_on(const bgv_cfg& k, const dev_batch& d) {
+  return !d.split && k.hash_dedup == 1 && d.n_sets > 0 && d.n_sets <= (1u << 30);
+}
+
 // a kept line buffer the batch does not use gives way under memory pressure
 static int work_alloc(bgv_ctx* c, const dev_batch& d, dev_work& w) {
   int r = work_alloc_once(c, d, w);
@@ -873,6 +895,19 @@ static int work_alloc_once(bgv_ctx* c, const dev_batch& d, dev_work& w) {
     c->lines.release();
     c->lines_idle = 0;
   }
+  // message classes (bgv_dedup.hip): sized with the batch's other buffers, never inside a run
+  c->mc = {};
+  if (hash_dedup_on(c->cfg, d)) {
+    size_t slots = 64;
+    while (slots < 2 * ns) slots *= 2;
+    if ((r = c->msg_rep.ensure(ns)) || (r = c->msg_uniq.ensure(ns)) || (r = c->msg_tab.ensure(slots)) || (r = c->msg_cnt.ensure(1)))
+      return r;
+    c->mc.n_sets = n;
+    c->mc.mask = (uint32_t)(slots - 1);
+    c->mc.msgs = d.msgs;
+    c->mc.table = c->msg_tab.p; c->mc.rep = c->msg_rep.p; c->mc.uniq = c->msg_uniq.p; c->mc.n_uniq = c->msg_cnt.p;
+    c->mc.h_aff = w.h_aff;
+  }
   w.msm_bucket = nullptr; w.msm_mask = nullptr; w.msm_win = nullptr;
   if (d.msm == 2) {
     if ((r = c->msm_bucket.ensure(nj * 16 * 15)) || (r = c->msm_mask.ensure(nj * 16)) || (r = c->msm_win.ensure(nj * 16))) return r;
@@ -915,6 +950,12 @@ static int run_stages(bgv_ctx* c, const dev_batch& d, const dev_work& w, int fro
   // then runs into the Miller phase, and the step lost 0.2-3.8 ms in every
   // order tried (profiles/r05m_bulk_stage_order.txt)
   const bool early_hash = fork && d.split && from <= ST_HASH && to > ST_HASH;
+  const bool hashes = from <= ST_HASH && to > ST_HASH;
+  const bool classes = hashes && c->mc.n_sets == d.n_sets && hash_dedup_on(c->cfg, d);
+  if (hashes) {
+    c->hash_path = {d.n_sets, d.n_sets, classes ? 1u : 0u};
+    c->hash_pending = classes;  // hashes = n_uniq, home with the results (finish_results, bgv_partial)
+  }
   auto launch_one = [&](int s) -> int {
     hipStream_t st = c->st;
     // fixed-argument lines: right behind the hash on its stream, before the
@@ -938,7 +979,8 @@ static int run_stages(bgv_ctx* c, const dev_batch& d, const dev_work& w, int fro
       if (fork) HIPCHK(hipStreamWaitEvent(st, c->ev_grp, 0));
       launch_sig_fixup(st, d, w);
     }
-    launch_stage(st, s, d, w);
+    if (s == ST_HASH && classes) launch_hash_classes(st, c->mc);  // bgv_dedup.hip: the representatives, then the copies
+    else launch_stage(st, s, d, w);
     HIPCHK(hipGetLastError());
     if (timed) HIPCHK(hipEventRecord(c->ev_end[s], st));
     else if (fork && (s == ST_PK_SCALE || s == ST_HASH || s == ST_MILLER)) HIPCHK(hipEventRecord(c->ev_dep[s], st));
@@ -970,6 +1012,17 @@ static int run_stages(bgv_ctx* c, const dev_batch& d, const dev_work& w, int fro
   }
   if (from <= ST_PK) {
     launch_prep(c->st, d, w);
+    HIPCHK(hipGetLastError());
+  }
+  // the message classes are index-only set-up too: beside launch_prep, on an
+  // otherwise idle GPU and in front of everything the hash stream runs.  The
+  // slot key is fresh per call (also when the caller injects the scalars):
+  // peers choose roots, and a fixed mix would let them build long probe chains
+  if (classes) {
+    random_bytes(&c->mc.key, sizeof c->mc.key);
+    HIPCHK(hipMemsetAsync(c->mc.table, 0xff, ((size_t)c->mc.mask + 1) * 4, c->st));
+    HIPCHK(hipMemsetAsync(c->mc.n_uniq, 0, 4, c->st));
+    launch_msg_dedup(c->st, c->mc);
     HIPCHK(hipGetLastError());
   }
   if (fork) {
@@ -1005,10 +1058,16 @@ static int finish_results(bgv_ctx* c, const dev_batch& d, const dev_work& w, int
   if (d.n_jobs) HIPCHK(hipMemcpyAsync(c->pin_out + jr_off, w.job_result, (size_t)d.n_jobs * 4, hipMemcpyDeviceToHost, c->st));
   if (want_sc) HIPCHK(hipMemcpyAsync(c->pin_out + sc_off, w.set_code, (size_t)d.n_sets * 4, hipMemcpyDeviceToHost, c->st));
   HIPCHK(hipMemcpyAsync(c->pin_out, w.flags, 4, hipMemcpyDeviceToHost, c->st));
+  const bool want_uniq = c->hash_pending;  // the class count of this run rides along (written before ev_prep on c->st)
+  if (want_uniq) HIPCHK(hipMemcpyAsync(c->pin_out + 64, c->mc.n_uniq, 4, hipMemcpyDeviceToHost, c->st));
   HIPCHK(hipStreamSynchronize(c->st));
   c->staged_pending = false;
   uint32_t flag = 0;
   memcpy(&flag, c->pin_out, 4);
+  if (want_uniq) {
+    memcpy(&c->hash_path.hashes, c->pin_out + 64, 4);
+    c->hash_pending = false;
+  }
   if (d.n_jobs) memcpy(job_result, c->pin_out + jr_off, (size_t)d.n_jobs * 4);
   if (want_sc) memcpy(set_code, c->pin_out + sc_off, (size_t)d.n_sets * 4);
   if (stats) {
@@ -1448,6 +1507,26 @@ int bgv_bits_path_stats(bgv_ctx* c, bgv_bits_path* out) {
   return BGV_OK;
 }
 
+// the same-message entries hash per group on their own (their retries may pass
+// through run_stages): bgv_hash_stats reports zeros after them
+static void hash_path_clear(bgv_ctx* c) {
+  if (!c) return;
+  c->hash_path = {};
+  c->hash_pending = false;
+}
+
+int bgv_hash_stats(bgv_ctx* c, bgv_hash_path* out) {
+  if (!c || !out) return fail(BGV_E_INVALID_ARG, "null argument");
+  if (c->hash_pending) {  // a call that failed between its launches and its results
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipMemcpyAsync(&c->hash_path.hashes, c->mc.n_uniq, 4, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(hipStreamSynchronize(c->st));
+    c->hash_pending = false;
+  }
+  *out = c->hash_path;
+  return BGV_OK;
+}
+
 int bgv_verify_bits(bgv_ctx* c, const bgv_bits_batch* b, int32_t* job_result, int32_t* set_code, bgv_stats* stats) {
   if (!c || !b || (!job_result && b->n_jobs)) return fail(BGV_E_INVALID_ARG, "null argument");
   c->partial_pending = false;
@@ -1777,12 +1856,16 @@ static int sm_run(bgv_ctx* c, const bgv_sm_batch* b, uint8_t* set_valid, int32_t
 }
 
 int bgv_verify_same_message(bgv_ctx* c, const bgv_sm_batch* b, uint8_t* set_valid, int32_t* set_code, bgv_sm_stats* stats) {
-  return sm_run(c, b, set_valid, set_code, stats, nullptr, nullptr, nullptr);
+  const int r_ = sm_run(c, b, set_valid, set_code, stats, nullptr, nullptr, nullptr);
+  hash_path_clear(c);  // these entries report bgv_sm_stats.hashes
+  return r_;
 }
 
 int bgv_debug_same_message(bgv_ctx* c, const bgv_sm_batch* b, uint8_t* set_valid, int32_t* set_code, bgv_sm_stats* stats,
                            uint8_t* p_group96, uint8_t* s_group192, uint8_t* h_group192) {
-  return sm_run(c, b, set_valid, set_code, stats, p_group96, s_group192, h_group192);
+  const int r_ = sm_run(c, b, set_valid, set_code, stats, p_group96, s_group192, h_group192);
+  hash_path_clear(c);  // these entries report bgv_sm_stats.hashes
+  return r_;
 }
 
 // ---- same-message batches of aggregate sets ----------------------------------
@@ -2157,12 +2240,16 @@ static int sma_back(bgv_ctx* c, sma_dev& k, std::chrono::steady_clock::time_poin
 }
 
 int bgv_verify_same_message_agg(bgv_ctx* c, const bgv_sma_batch* b, uint8_t* set_valid, int32_t* set_code, bgv_sm_stats* stats) {
-  return sma_run(c, b, set_valid, set_code, stats, nullptr, nullptr, nullptr, nullptr);
+  const int r_ = sma_run(c, b, set_valid, set_code, stats, nullptr, nullptr, nullptr, nullptr);
+  hash_path_clear(c);  // these entries report bgv_sm_stats.hashes
+  return r_;
 }
 
 int bgv_debug_same_message_agg(bgv_ctx* c, const bgv_sma_batch* b, uint8_t* set_valid, int32_t* set_code, bgv_sm_stats* stats,
                                uint8_t* pk_set96, uint8_t* p_group96, uint8_t* s_group192, uint8_t* h_group192) {
-  return sma_run(c, b, set_valid, set_code, stats, pk_set96, p_group96, s_group192, h_group192);
+  const int r_ = sma_run(c, b, set_valid, set_code, stats, pk_set96, p_group96, s_group192, h_group192);
+  hash_path_clear(c);  // these entries report bgv_sm_stats.hashes
+  return r_;
 }
 
 // ---- same-message batches of committee sets -----------------------------------
@@ -2312,12 +2399,16 @@ static int smb_run(bgv_ctx* c, const bgv_smb_batch* b, uint8_t* set_valid, int32
 }
 
 int bgv_verify_same_message_bits(bgv_ctx* c, const bgv_smb_batch* b, uint8_t* set_valid, int32_t* set_code, bgv_sm_stats* stats) {
-  return smb_run(c, b, set_valid, set_code, stats, nullptr, nullptr, nullptr, nullptr, nullptr);
+  const int r_ = smb_run(c, b, set_valid, set_code, stats, nullptr, nullptr, nullptr, nullptr, nullptr);
+  hash_path_clear(c);  // these entries report bgv_sm_stats.hashes
+  return r_;
 }
 
 int bgv_debug_same_message_bits(bgv_ctx* c, const bgv_smb_batch* b, uint8_t* set_valid, int32_t* set_code, bgv_sm_stats* stats,
                                 uint8_t* pk_set96, uint8_t* path, uint8_t* p_group96, uint8_t* s_group192, uint8_t* h_group192) {
-  return smb_run(c, b, set_valid, set_code, stats, pk_set96, path, p_group96, s_group192, h_group192);
+  const int r_ = smb_run(c, b, set_valid, set_code, stats, pk_set96, path, p_group96, s_group192, h_group192);
+  hash_path_clear(c);  // these entries report bgv_sm_stats.hashes
+  return r_;
 }
 
 // ---- multi-GPU partials ---------------------------------------------------
@@ -2362,7 +2453,9 @@ int bgv_partial(bgv_ctx* c, const bgv_batch* b, uint8_t* miller576, int32_t* set
   std::vector<int32_t> jc(d.n_jobs ? d.n_jobs : 1);
   if (d.n_jobs) HIPCHK(hipMemcpyAsync(jc.data(), w.job_code, (size_t)d.n_jobs * 4, hipMemcpyDeviceToHost, c->st));
   if (set_code && d.n_sets) HIPCHK(hipMemcpyAsync(set_code, w.set_code, (size_t)d.n_sets * 4, hipMemcpyDeviceToHost, c->st));
+  if (c->hash_pending) HIPCHK(hipMemcpyAsync(&c->hash_path.hashes, c->mc.n_uniq, 4, hipMemcpyDeviceToHost, c->st));
   HIPCHK(hipStreamSynchronize(c->st));
+  c->hash_pending = false;
   c->staged_pending = false;
   fp12_plain_to_bytes(miller576, f);
   int32_t ok = 1;

@@ -265,4 +265,23 @@ void launch_sums_export(hipStream_t st, const g1j* sums, uint8_t* out96, uint32_
 // exclusive scan of a[0..n) in place, total at a[n] (bgv_kernels.hip k_scan)
 void launch_scan(hipStream_t st, uint32_t* a, uint32_t n);
 
+// ---- message classes of a bulk batch (bgv_cfg.hash_dedup, bgv_dedup.hip) -----
+// Sets with equal signing roots form a class; its representative is hashed and
+// the other members copy H(m).  Kept out of dev_batch / dev_work: those are
+// kernel arguments of every other kernel.
+constexpr uint32_t MSG_EMPTY = 0xffffffffu;  // a free slot of the table (hipMemsetAsync 0xff)
+struct msg_classes {
+  uint32_t n_sets;
+  uint32_t mask;        // slots of the table - 1; the table holds a power of two >= 2 n_sets slots
+  uint64_t key;         // per-call key of the slot mix (getrandom)
+  const uint8_t* msgs;  // [n_sets][32]
+  uint32_t* table;      // [mask + 1] MSG_EMPTY, or the set that claimed the slot
+  uint32_t* rep;        // [n_sets] representative of every set (rep[rep[i]] == rep[i])
+  uint32_t* uniq;       // [n_sets] the representatives, compacted, in no particular order
+  uint32_t* n_uniq;     // their count (zeroed per call)
+  g2a* h_aff;           // dev_work.h_aff
+};
+void launch_msg_dedup(hipStream_t st, const msg_classes& c);     // index-only set-up, beside launch_prep
+void launch_hash_classes(hipStream_t st, const msg_classes& c);  // ST_HASH of the bulk layout: k_hash_reps, k_hash_spread
+
 }  // namespace bgv

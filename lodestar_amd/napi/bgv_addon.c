@@ -5,9 +5,10 @@
  *   abiVersion() -> number                      bgv_abi_version
  *   buildId() -> string                         bgv_build_id
  *   codeName(code) -> "BLST_..."                 bgv_set_code_name
- *   open(device, cuSplit = 0) -> ctx (external)  bgv_open_cfg  (multithread/index.ts:120); cuSplit N > 0:
+ *   open(device, cuSplit = 0, cfg?) -> ctx (external)  bgv_open_cfg  (multithread/index.ts:120); cuSplit N > 0:
  *                                                a priority context on N reserved CUs (verifyOnMainThread),
- *                                                N < 0: a bulk context that leaves them free (bgv_cfg.cu_split)
+ *                                                N < 0: a bulk context that leaves them free (bgv_cfg.cu_split);
+ *                                                cfg (tests and A/B tools): {split, hashDedup} as in bgv_cfg
  *   close(ctx)                                   bgv_close     (multithread/index.ts:193-214)
  *   pubkeysSet(ctx, first, Uint8Array, format)   bgv_pubkeys_set (pubkeyCache.ts:56-77)
  *   pubkeysCount(ctx) -> number
@@ -30,6 +31,7 @@
  *   indexListLen(ctx, id) -> number              bgv_index_list_len
  *   setIndexListSums(ctx, id, bool)              bgv_index_list_sums: build (or drop) the list's resident prefix sums
  *   indexListHasSums(ctx, id) -> boolean         bgv_index_list_has_sums
+ *   hashStats(ctx) -> {sets, hashes, dedup}      bgv_hash_stats (the last verify / verifyBits / partial, for the sync paths)
  *   bitsPathStats(ctx) -> {setsComplement, keysExpanded, keysGathered}   bgv_bits_path_stats (the last verifyBits / verifySameMessageBits)
  *   verifyBits(ctx, bitsBatch) -> Promise<result>, verifyBitsSync(ctx, bitsBatch) -> result
  *                                                bgv_verify_bits: sets given as (list, window, participation bits)
@@ -41,7 +43,9 @@
  * result = {results: Int32Array (bgv_job_result per job: 1 valid, 0 invalid,
  * -code rejected), batchRetries, batchSigsSuccess, pubkeysAggregated,
  * deviceMs, workerStartMs, workerEndMs}: the BlsWorkResult fields
- * (multithread/types.ts:26-38) the pool's metrics are fed from.  For
+ * (multithread/types.ts:26-38) the pool's metrics are fed from; verify,
+ * verifyBits and partial add hashes, the call's hash_to_G2 evaluations
+ * (bgv_hash_stats, read while the context is still locked).  For
  * partial() `results` is provisional: -code for a job rejected by a parse /
  * subgroup / pubkey error (final), 1 for every other job (valid iff the
  * combined check passes).  Contexts on different devices run their queued
@@ -151,8 +155,8 @@ static napi_value CodeName(napi_env env, napi_callback_info info) {
 }
 
 static napi_value Open(napi_env env, napi_callback_info info) {
-  size_t argc = 2;
-  napi_value a[2];
+  size_t argc = 3;
+  napi_value a[3];
   NAPI_CALL(env, napi_get_cb_info(env, info, &argc, a, NULL, NULL));
   int32_t dev = 0, cu_split = 0;
   if (argc >= 1) NAPI_CALL(env, napi_get_value_int32(env, a[0], &dev));
@@ -160,6 +164,34 @@ static napi_value Open(napi_env env, napi_callback_info info) {
   bgv_cfg cfg;
   bgv_cfg_default(&cfg);
   cfg.cu_split = cu_split;
+  if (argc >= 3) { /* pipeline overrides (tests, A/B tools): any other key is refused */
+    napi_valuetype t;
+    NAPI_CALL(env, napi_typeof(env, a[2], &t));
+    if (t == napi_object) {
+      napi_value keys, key, val;
+      uint32_t nk = 0;
+      NAPI_CALL(env, napi_get_property_names(env, a[2], &keys));
+      NAPI_CALL(env, napi_get_array_length(env, keys, &nk));
+      for (uint32_t k = 0; k < nk; k++) {
+        char name[32];
+        size_t len = 0;
+        int32_t x = 0;
+        NAPI_CALL(env, napi_get_element(env, keys, k, &key));
+        NAPI_CALL(env, napi_get_value_string_utf8(env, key, name, sizeof name, &len));
+        NAPI_CALL(env, napi_get_property(env, a[2], key, &val));
+        NAPI_CALL(env, napi_get_value_int32(env, val, &x));
+        if (!strcmp(name, "split")) cfg.split = x;
+        else if (!strcmp(name, "hashDedup")) cfg.hash_dedup = x;
+        else {
+          napi_throw_type_error(env, NULL, "open: cfg takes split and hashDedup");
+          return NULL;
+        }
+      }
+    } else if (t != napi_undefined && t != napi_null) {
+      napi_throw_type_error(env, NULL, "open: cfg must be an object");
+      return NULL;
+    }
+  }
   bgv_ctx* ctx = NULL;
   const int st = bgv_open_cfg(dev, &cfg, &ctx);
   if (st != BGV_OK) return throw_bgv(env, st);
@@ -284,6 +316,7 @@ typedef struct {
   uint32_t* pk_off;
   int32_t* job_result;
   bgv_stats stats;
+  bgv_hash_path hash_path; /* K_VERIFY, K_BITS, K_PARTIAL: read under the context's lock */
   double t_start_ms, t_end_ms;
   int status;
   char err[512];
@@ -395,6 +428,9 @@ static void run_verify(verify_job* j) {
       case K_BITS: j->status = bgv_verify_bits(j->c->ctx, &j->bb, j->job_result, NULL, &j->stats); break;
       default: j->status = bgv_verify(j->c->ctx, &j->b, j->job_result, NULL, &j->stats); break;
     }
+    /* under the same lock: this call's evaluations, not a later call's */
+    if (j->status == BGV_OK && (j->kind == K_VERIFY || j->kind == K_BITS || j->kind == K_PARTIAL))
+      j->status = bgv_hash_stats(j->c->ctx, &j->hash_path);
     if (j->status != BGV_OK) snprintf(j->err, sizeof j->err, "bgv error %d: %s", j->status, bgv_last_error());
   }
   j->t_end_ms = now_ms();
@@ -420,6 +456,10 @@ static napi_value result_object(napi_env env, const verify_job* j) {
   napi_set_named_property(env, o, "workerStartMs", v);
   napi_create_double(env, j->t_end_ms, &v);
   napi_set_named_property(env, o, "workerEndMs", v);
+  if (j->kind == K_VERIFY || j->kind == K_BITS || j->kind == K_PARTIAL) {
+    napi_create_uint32(env, j->hash_path.hashes, &v);
+    napi_set_named_property(env, o, "hashes", v);
+  }
   if (j->kind == K_PARTIAL) {
     void* dst = NULL;
     napi_value ab;
@@ -1092,6 +1132,29 @@ static napi_value IndexListHasSums(napi_env env, napi_callback_info info) {
   return r;
 }
 
+/* hashStats(ctx): bgv_hash_stats of the context's last ordinary batch (the sync paths read it after the call) */
+static napi_value HashStats(napi_env env, napi_callback_info info) {
+  size_t argc = 1;
+  napi_value a[1];
+  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, a, NULL, NULL));
+  addon_ctx* c = get_ctx(env, a[0]);
+  if (!c) return NULL;
+  bgv_hash_path p;
+  pthread_mutex_lock(&c->mu);
+  const int st = bgv_hash_stats(c->ctx, &p);
+  pthread_mutex_unlock(&c->mu);
+  if (st != BGV_OK) return throw_bgv(env, st);
+  napi_value r, v;
+  NAPI_CALL(env, napi_create_object(env, &r));
+  NAPI_CALL(env, napi_create_uint32(env, p.sets, &v));
+  NAPI_CALL(env, napi_set_named_property(env, r, "sets", v));
+  NAPI_CALL(env, napi_create_uint32(env, p.hashes, &v));
+  NAPI_CALL(env, napi_set_named_property(env, r, "hashes", v));
+  NAPI_CALL(env, napi_create_uint32(env, p.dedup, &v));
+  NAPI_CALL(env, napi_set_named_property(env, r, "dedup", v));
+  return r;
+}
+
 static napi_value BitsPathStats(napi_env env, napi_callback_info info) {
   size_t argc = 1;
   napi_value a[1];
@@ -1140,6 +1203,7 @@ static napi_value Init(napi_env env, napi_value exports) {
       {"setIndexListSums", NULL, SetIndexListSums, NULL, NULL, NULL, napi_enumerable, NULL},
       {"indexListHasSums", NULL, IndexListHasSums, NULL, NULL, NULL, napi_enumerable, NULL},
       {"bitsPathStats", NULL, BitsPathStats, NULL, NULL, NULL, napi_enumerable, NULL},
+      {"hashStats", NULL, HashStats, NULL, NULL, NULL, napi_enumerable, NULL},
       {"verifyBits", NULL, VerifyBits, NULL, NULL, NULL, napi_enumerable, NULL},
       {"verifyBitsSync", NULL, VerifyBitsSync, NULL, NULL, NULL, napi_enumerable, NULL},
   };

@@ -150,6 +150,15 @@ function checkSets(sets) {
   }
 }
 
+// hash_to_G2 per device batch (bgv_hash_stats): the sets that needed H(m) and the evaluations the device made
+// (fewer where a bulk-layout batch repeats signing roots).  Added on first use, so the metrics object keeps its
+// shape until a batch reports them.
+function recordHashes(m, sets, res) {
+  if (typeof res.hashes !== "number") return;
+  m.hashToG2Sets = (m.hashToG2Sets || 0) + sets;
+  m.hashToG2Evaluated = (m.hashToG2Evaluated || 0) + res.hashes;
+}
+
 function aggregatedPubkeysCount(sets) {
   let n = 0;
   for (const s of sets) {
@@ -1014,6 +1023,7 @@ class BlsGpuVerifier {
     return {
       results, batchRetries: valid ? 0 : 1, batchSigsSuccess: sigsOk,
       pubkeysAggregated: parts.reduce((a, p) => a + p.pubkeysAggregated, 0),
+      hashes: parts.reduce((a, p) => a + p.hashes, 0), // per shard: a root on two shards is hashed on both
       deviceMs: Math.max(...parts.map((p) => p.deviceMs)),
       workerStartMs: Math.min(...parts.map((p) => p.workerStartMs)),
       workerEndMs: Math.max(...finals.map((p) => p.workerEndMs)),
@@ -1036,6 +1046,7 @@ class BlsGpuVerifier {
     m.lodestar_bls_thread_pool_error_jobs_signature_sets_count += err;
     m.lodestar_bls_thread_pool_batch_retries_total += res.batchRetries;
     m.lodestar_bls_thread_pool_batch_sigs_success_total += res.batchSigsSuccess;
+    recordHashes(m, ok + err, res);
   }
 
   // gauges sampled at scrape time (index.ts:135-139)

@@ -1114,6 +1114,21 @@ class BlsGpuVerifier:
         self.metrics["batch_sigs_success"] += int(st.batch_sigs_success)
         self.metrics["device_time_s"] += seconds
 
+    def _record_hashes(self, hs: list[dict | None]):
+        """hash_to_G2 per device batch (bgv_hash_stats of each context that ran a part of it): the sets that
+        needed H(m) and the evaluations made, fewer where a bulk-layout batch repeats signing roots.  Both keys
+        appear with the first batch that reports them; sharded batches add up their shards."""
+        for h in hs:
+            if h:
+                self.metrics["hash_to_g2_sets"] = self.metrics.get("hash_to_g2_sets", 0) + int(h["sets"])
+                self.metrics["hash_to_g2_evaluated"] = self.metrics.get("hash_to_g2_evaluated", 0) + int(h["hashes"])
+
+    @staticmethod
+    def _hash_stats(dev) -> dict | None:
+        """read under the context's lock, right after its call (a device stand-in without the getter reports nothing)"""
+        get = getattr(dev, "hash_stats", None)
+        return get() if get is not None else None
+
     def _warm_priority(self):
         """sizes the priority context's work buffers for a full job (128 sets)
         at construction, so a verifyOnMainThread call never frees and regrows
@@ -1153,6 +1168,7 @@ class BlsGpuVerifier:
                 t1 = time.perf_counter()
                 jr, _ = (self.prio.verify_bits if use_bits else self.prio.verify)(arrays, want_set_codes=False)
                 self._record(self.prio.last_stats, time.perf_counter() - t1)
+                self._record_hashes([self._hash_stats(self.prio)])
         except Exception as e:  # noqa: BLE001 -- a device error rejects the call
             return e
         finally:
@@ -1214,6 +1230,7 @@ class BlsGpuVerifier:
                     t0 = time.perf_counter()
                     jr, _ = (self.devices[d].verify_bits if use_bits else self.devices[d].verify)(arrays, want_set_codes=False)
                     self._record(self.devices[d].last_stats, time.perf_counter() - t0)
+                    self._record_hashes([self._hash_stats(self.devices[d])])
             except Exception as e:  # noqa: BLE001 -- a device error rejects the package (index.ts:386-393)
                 return [e] * len(jobs)
             return [self._verdict(r) for r in jr.tolist()]
@@ -1225,16 +1242,19 @@ class BlsGpuVerifier:
         try:
             t0 = time.perf_counter()
             parts: list = [None] * len(live)
+            hashed: list = [None] * len(live)
 
             def run_partial(k):
                 d, ids = live[k]
                 try:
                     sub = [jobs[i] for i in ids]
                     parts[k] = self.devices[d].partial(encode_jobs(sub, self._scalars(sum(len(j) for j in sub))))
+                    hashed[k] = self._hash_stats(self.devices[d])
                 except Exception as e:  # noqa: BLE001
                     parts[k] = e
 
             self._parallel(run_partial, len(live))
+            self._record_hashes(hashed)
             failed = [k for k in range(len(live)) if isinstance(parts[k], Exception)]
             for k in failed:  # a device error rejects that shard's jobs
                 for i in live[k][1]:

@@ -14,6 +14,7 @@
 #include <stdlib.h>
 #include <atomic>
 #include <chrono>
+#include <optional>
 #include <vector>
 #include <string>
 
@@ -1596,19 +1597,43 @@ int bgv_debug_bits_keys(bgv_ctx* c, const bgv_bits_batch* b, uint8_t* pk_agg96, 
 }
 
 // ---- same-message batches ---------------------------------------------------
-// IBlsVerifier.verifySignatureSetsSameMessage: see include/bgv.h.  Layout:
-//   st      : sig decode + subgroup -> classify -> G2 bucket MSM per segment
-//             (k_msm_digit / k_msm_job over the real sets, job = segment)
+// Three entries over one pipeline (include/bgv.h; DESIGN.md section 3c holds
+// the table of what differs between them):
+//   bgv_verify_same_message      a set has one key
+//     (IBlsVerifier.verifySignatureSetsSameMessage)
+//   bgv_verify_same_message_agg  a set's key is an aggregate, PK_i = sum_j pk_{i,j}
+//   bgv_verify_same_message_bits the aggregate's members given as bgv_verify_bits
+//                                gives them
+// A front (sm_run, sma_run, smb_run) checks its batch, cuts the segments, stages
+// its arrays and fills an sm_dev; sm_back is the device half.  Layout:
+//   st      : sig decode + subgroup -> [set sums] classify -> G2 bucket MSM per
+//             segment (k_msm_digit / k_msm_job over the real sets, job = segment)
 //             -> [pk, hash] apply -> Miller, folds, final exponentiations on
 //             the VIRTUAL batch (one set = one job = one segment)
-//   st_pk   : [classify] weighted G1 sum per segment (bgv_same_msg.hip)
-//   st_hash : one hash per group (the latency-mode hash kernels)
+//   st_pk   : aggregate keys: [expansion of bitfield sets ->] chunk set-up ->
+//             gather (k_pk_chunk) -> per-set fold (k_sma_set_sum) beside the
+//             signature decode; then [classify] the weighted G1 sum per segment
+//             (bgv_same_msg.hip)
+//   st_hash : one hash per group (the latency-mode hash kernels); aggregate
+//             keys: then [apply] the (P_seg, H(m)) pairs beside the
+//             (-G1, S_seg) ones
 // then, only when the whole-batch check failed, the surviving sets of the
-// failing segments as one-set jobs of the ordinary pipeline.
+// failing segments as one-set jobs of the ordinary pipeline (an aggregate key
+// enters as a raw key).
 
-// contract of a batch; `go` is the copy of the group offsets the device will see
-static int sm_check_offsets(const bgv_sm_batch* b, const uint32_t* go) {
-  const uint32_t n = b->n_sets, G = b->n_groups;
+// the rules every same-message batch shares; what passes has n_sets == 0 (and
+// no group: nothing more to check) or 1 <= n_groups <= n_sets
+template <class B>
+static int sm_check_counts(const B* b) {
+  if (!b) return fail(BGV_E_INVALID_ARG, "batch is NULL");
+  if (b->n_sets == 0 && b->n_groups == 0) return BGV_OK;
+  if (b->n_groups > b->n_sets) return fail(BGV_E_INVALID_ARG, "n_groups %u > n_sets %u (a group is never empty)", b->n_groups, b->n_sets);
+  if (b->n_groups == 0) return fail(BGV_E_INVALID_ARG, "n_sets %u without a group", b->n_sets);
+  return BGV_OK;
+}
+
+// `go`: the copy of the group offsets the segments are cut from
+static int sm_check_groups(uint32_t n, uint32_t G, const uint32_t* go) {
   if (go[0] != 0 || go[G] != n) return fail(BGV_E_INVALID_ARG, "group_offsets must span [0, n_sets]");
   for (uint32_t g = 0; g < G; g++) {
     if (go[g + 1] < go[g]) return fail(BGV_E_INVALID_ARG, "group_offsets not monotone");
@@ -1617,86 +1642,175 @@ static int sm_check_offsets(const bgv_sm_batch* b, const uint32_t* go) {
   return BGV_OK;
 }
 
+// caller-given scalars (NULL: none given, drawn on the device)
+static int scalars_nonzero(const uint64_t* sc, uint32_t n) {
+  if (sc)
+    for (uint32_t i = 0; i < n; i++)
+      if (!sc[i]) return fail(BGV_E_INVALID_ARG, "scalars[%u] is zero", i);
+  return BGV_OK;
+}
+
 static int sm_check_args(const bgv_sm_batch* b) {
-  if (!b) return fail(BGV_E_INVALID_ARG, "batch is NULL");
-  if (b->n_sets == 0 && b->n_groups == 0) return BGV_OK;
-  if (b->n_groups > b->n_sets) return fail(BGV_E_INVALID_ARG, "n_groups %u > n_sets %u (a group is never empty)", b->n_groups, b->n_sets);
-  if (b->n_groups == 0) return fail(BGV_E_INVALID_ARG, "n_sets %u without a group", b->n_sets);
+  if (int r = sm_check_counts(b)) return r;
+  if (b->n_sets == 0) return BGV_OK;
   if (!b->group_offsets || !b->pk_indices || !b->msgs || !b->sigs || !b->sig_len) return fail(BGV_E_INVALID_ARG, "missing batch array");
   if (b->n_raw && !b->raw_pks) return fail(BGV_E_INVALID_ARG, "n_raw > 0 but raw_pks is NULL");
+  return BGV_OK;
+}
+
+static int sm_check_args(const bgv_sma_batch* b) {
+  if (int r = sm_check_counts(b)) return r;
+  if (b->n_sets == 0) return BGV_OK;
+  if (!b->group_offsets || !b->pk_offsets || !b->pk_indices || !b->msgs || !b->sigs || !b->sig_len)
+    return fail(BGV_E_INVALID_ARG, "missing batch array");
+  if (b->n_raw && !b->raw_pks) return fail(BGV_E_INVALID_ARG, "n_raw > 0 but raw_pks is NULL");
+  return BGV_OK;
+}
+
+static int sm_check_args(const bgv_smb_batch* b) {
+  if (int r = sm_check_counts(b)) return r;
+  if (b->n_sets == 0) return BGV_OK;
+  if (!b->group_offsets || !b->src || !b->msgs || !b->sigs || !b->sig_len) return fail(BGV_E_INVALID_ARG, "missing batch array");
+  if (b->bits_len && !b->bits) return fail(BGV_E_INVALID_ARG, "bits_len > 0 but bits is NULL");
+  if (b->n_indices && !b->pk_indices) return fail(BGV_E_INVALID_ARG, "n_indices > 0 but pk_indices is NULL");
+  if (b->n_raw && !b->raw_pks) return fail(BGV_E_INVALID_ARG, "n_raw > 0 but raw_pks is NULL");
+  return BGV_OK;
+}
+
+// `po`: the copy of the key offsets the device will see; total: the length of pk_indices that is staged
+static int sma_check_keys(const bgv_sma_batch* b, const uint32_t* po, uint32_t total) {
+  const uint32_t n = b->n_sets;
+  if (po[0] != 0 || po[n] != total) return fail(BGV_E_INVALID_ARG, "pk_offsets must span [0, total]");
+  for (uint32_t i = 0; i < n; i++)
+    if (po[i + 1] < po[i]) return fail(BGV_E_INVALID_ARG, "pk_offsets not monotone");
+  for (uint32_t i = 0; i < n; i++)
+    if (po[i + 1] == po[i]) return fail(BGV_E_EMPTY_SET, "EMPTY_AGGREGATE_ARRAY (set %u)", i);
   return BGV_OK;
 }
 
 int bgv_sm_check(const bgv_sm_batch* b) {
   if (int r = sm_check_args(b)) return r;
   if (b->on_device || b->n_sets == 0) return BGV_OK;
-  if (int r = sm_check_offsets(b, b->group_offsets)) return r;
-  if (b->scalars)
-    for (uint32_t i = 0; i < b->n_sets; i++)
-      if (!b->scalars[i]) return fail(BGV_E_INVALID_ARG, "scalars[%u] is zero", i);
-  return BGV_OK;
+  if (int r = sm_check_groups(b->n_sets, b->n_groups, b->group_offsets)) return r;
+  return scalars_nonzero(b->scalars, b->n_sets);
 }
 
-static int sm_run(bgv_ctx* c, const bgv_sm_batch* b, uint8_t* set_valid, int32_t* set_code, bgv_sm_stats* stats,
-                  uint8_t* p_group96, uint8_t* s_group192, uint8_t* h_group192) {
+int bgv_sma_check(const bgv_sma_batch* b) {
+  if (int r = sm_check_args(b)) return r;
+  if (b->on_device || b->n_sets == 0) return BGV_OK;
+  if (int r = sm_check_groups(b->n_sets, b->n_groups, b->group_offsets)) return r;
+  if (int r = sma_check_keys(b, b->pk_offsets, b->pk_offsets[b->n_sets])) return r;
+  return scalars_nonzero(b->scalars, b->n_sets);
+}
+
+int bgv_smb_check(const bgv_smb_batch* b, const uint32_t* list_len) {
+  if (int r = sm_check_args(b)) return r;
+  if (!list_len) return fail(BGV_E_INVALID_ARG, "list_len is NULL");
+  if (b->on_device || b->n_sets == 0) return BGV_OK;
+  if (int r = sm_check_groups(b->n_sets, b->n_groups, b->group_offsets)) return r;
+  bits_view v;
+  bits_host_view(v, list_len, nullptr);
+  v.bits = b->bits; v.bits_len = b->bits_len; v.pk_indices = b->pk_indices; v.n_indices = b->n_indices;
+  bits_plan_out po;
+  if (int r = bits_check_sources(b->n_sets, (const bits_src*)b->src, v, &po, nullptr)) return r;
+  return scalars_nonzero(b->scalars, b->n_sets);
+}
+
+// the segments of a same-message batch: every group cut into runs of at most SM_SEG sets
+struct sm_segs {
+  std::vector<uint32_t> seg_off, seg_group, group_seg, iota;
+  uint32_t S = 0;
+};
+static void sm_cut_segments(const std::vector<uint32_t>& go, uint32_t n, sm_segs& sg) {
+  const uint32_t G = (uint32_t)go.size() - 1;
+  sg.group_seg.resize((size_t)G + 1);
+  sg.seg_off.reserve(n / SM_SEG + G + 1);
+  for (uint32_t g = 0; g < G; g++) {
+    sg.group_seg[g] = (uint32_t)sg.seg_off.size();
+    for (uint32_t i = go[g]; i < go[g + 1]; i += SM_SEG) { sg.seg_off.push_back(i); sg.seg_group.push_back(g); }
+  }
+  sg.S = (uint32_t)sg.seg_off.size();
+  sg.group_seg[G] = sg.S;
+  sg.seg_off.push_back(n);
+  sg.iota.resize((size_t)sg.S + 1);
+  for (uint32_t s = 0; s <= sg.S; s++) sg.iota[s] = s;
+}
+
+// A same-message call between its front and sm_back: the segments, and the
+// device view of the batch once its arrays are staged (or resident).  sm_open
+// fills what every entry has; a front adds the segment tables and its key side.
+struct sm_dev {
+  uint32_t n = 0, G = 0, n_raw = 0;  // n == 0 after sm_open: an empty batch, the call is done
+  std::optional<active_guard> busy;
+  std::chrono::steady_clock::time_point t0;
+  sm_segs sg;
+  const uint32_t *d_seg_off = nullptr, *d_seg_group = nullptr, *d_group_seg = nullptr, *d_iota = nullptr;
+  const uint32_t *d_po = nullptr, *d_idx = nullptr, *d_len = nullptr;
+  const uint8_t *d_msgs = nullptr, *d_sigs = nullptr, *d_raw = nullptr;
+  const uint64_t* d_scalars = nullptr;
+  bool draw_scalars = false;  // the caller gave none: drawn on the device (d_scalars is then not read)
+  // The key side.  One key per set: d_idx[i] names it, d_po and win stay NULL and
+  // chunk_bound n, nothing is gathered.  Aggregates: d_po / d_idx are the lists
+  // the gather on the pubkey stream sums into PK_i.
+  bool agg = false;
+  uint32_t chunk_bound = 0;  // grid bound of the gather
+  // bgv_verify_same_message_bits: the per-set windows (contexts with sums, else
+  // NULL) and the expansion still to run on the pubkey stream
+  const pk_window* win = nullptr;
+  bits_args* expand = nullptr;
+  bool expand_count = false;  // count and scan too (host batches: their totals come from the host plan)
+  uint32_t gathered = 0;      // keys the expansion holds
+};
+
+// the opening of every front; k.n stays 0 for an empty batch
+template <class B>
+static int sm_open(bgv_ctx* c, const B* b, uint8_t* set_valid, bgv_sm_stats* stats, sm_dev& k) {
   if (!c) return fail(BGV_E_INVALID_ARG, "null ctx");
   if (int r = sm_check_args(b)) return r;
   if (stats) memset(stats, 0, sizeof *stats);
-  const uint32_t n = b->n_sets, G = b->n_groups;
-  if (n == 0) return BGV_OK;
+  if (b->n_sets == 0) return BGV_OK;
   if (!set_valid) return fail(BGV_E_INVALID_ARG, "set_valid is NULL");
   c->partial_pending = false;
   HIPCHK(hipSetDevice(c->device));
-  active_guard ag(c->device);
-  const auto t0 = std::chrono::steady_clock::now();
-  // the group offsets come to the host first: the segments are cut from this copy
-  std::vector<uint32_t> go((size_t)G + 1);
-  if (b->on_device) {
-    HIPCHK(hipMemcpyAsync(go.data(), b->group_offsets, go.size() * 4, hipMemcpyDeviceToHost, c->st));
+  k.busy.emplace(c->device);
+  k.t0 = std::chrono::steady_clock::now();
+  k.n = b->n_sets; k.G = b->n_groups; k.n_raw = b->n_raw;
+  k.d_len = b->sig_len; k.d_msgs = b->msgs; k.d_sigs = b->sigs; k.d_raw = b->raw_pks; k.d_scalars = b->scalars;
+  k.draw_scalars = !b->scalars;
+  k.chunk_bound = k.n;
+  return BGV_OK;
+}
+
+// The group offsets come to the host first: the segments are cut from this
+// copy.  An on-device batch may bring one more word (d_word -> *h_word) with
+// the same wait.
+static int sm_groups(bgv_ctx* c, sm_dev& k, const uint32_t* group_offsets, bool on_device, const uint32_t* d_word = nullptr,
+                     uint32_t* h_word = nullptr) {
+  std::vector<uint32_t> go((size_t)k.G + 1);
+  if (on_device) {
+    HIPCHK(hipMemcpyAsync(go.data(), group_offsets, go.size() * 4, hipMemcpyDeviceToHost, c->st));
+    if (d_word) HIPCHK(hipMemcpyAsync(h_word, d_word, 4, hipMemcpyDeviceToHost, c->st));
     HIPCHK(hipStreamSynchronize(c->st));
   } else {
-    memcpy(go.data(), b->group_offsets, go.size() * 4);
+    memcpy(go.data(), group_offsets, go.size() * 4);
   }
-  if (int r = sm_check_offsets(b, go.data())) return r;
-  std::vector<uint32_t> seg_off, seg_group, group_seg((size_t)G + 1);
-  seg_off.reserve(n / SM_SEG + G + 1);
-  for (uint32_t g = 0; g < G; g++) {
-    group_seg[g] = (uint32_t)seg_off.size();
-    for (uint32_t i = go[g]; i < go[g + 1]; i += SM_SEG) { seg_off.push_back(i); seg_group.push_back(g); }
-  }
-  const uint32_t S = (uint32_t)seg_off.size();
-  group_seg[G] = S;
-  seg_off.push_back(n);
-  std::vector<uint32_t> iota((size_t)S + 1);
-  for (uint32_t s = 0; s <= S; s++) iota[s] = s;
+  if (int r = sm_check_groups(k.n, k.G, go.data())) return r;
+  sm_cut_segments(go, k.n, k.sg);
+  return BGV_OK;
+}
 
-  // staging: the segment tables always, the batch arrays of a host batch
-  const uint32_t *d_seg_off = nullptr, *d_seg_group = nullptr, *d_group_seg = nullptr, *d_iota = nullptr;
-  const uint32_t *d_idx = b->pk_indices, *d_len = b->sig_len;
-  const uint8_t *d_msgs = b->msgs, *d_sigs = b->sigs, *d_raw = b->raw_pks;
-  const uint64_t* d_scalars = b->scalars;
-  const bool host = !b->on_device;
-  stage_seg segs[10] = {
-      {seg_off.data(), ((size_t)S + 1) * 4, (const void**)&d_seg_off, 0},
-      {seg_group.data(), (size_t)S * 4, (const void**)&d_seg_group, 0},
-      {group_seg.data(), ((size_t)G + 1) * 4, (const void**)&d_group_seg, 0},
-      {iota.data(), ((size_t)S + 1) * 4, (const void**)&d_iota, 0},
-      {b->pk_indices, (size_t)n * 4, (const void**)&d_idx, 0},
-      {b->msgs, (size_t)G * 32, (const void**)&d_msgs, 0},
-      {b->raw_pks, (size_t)b->n_raw * 96, (const void**)&d_raw, 0},
-      {b->scalars, b->scalars ? (size_t)n * 8 : 0, (const void**)&d_scalars, 0},
-      {b->sigs, (size_t)n * 192, (const void**)&d_sigs, 0},
-      {b->sig_len, (size_t)n * 4, (const void**)&d_len, 0},
-  };
-  size_t bytes = 0;
-  if (int r = stage_pack(c, segs, host ? 10 : 4, bytes)) return r;
-  if (host && b->scalars) {  // checked on the pinned copy
-    const uint64_t* sc = (const uint64_t*)(c->pin_in + segs[7].off);
-    for (uint32_t i = 0; i < n; i++)
-      if (!sc[i]) return fail(BGV_E_INVALID_ARG, "scalars[%u] is zero", i);
-  }
-  if (int r = stage_issue(c, bytes)) return r;
-  if (!b->scalars) {
+// The device half of a same-message call, from the staged (or resident) arrays
+// on.  k.agg picks the key side, where the pairs of the virtual batch run and
+// what the retry takes as a set's key; everything else is one path.
+static int sm_back(bgv_ctx* c, sm_dev& k, uint8_t* set_valid, int32_t* set_code, bgv_sm_stats* stats, uint8_t* pk_set96,
+                   uint8_t* p_group96, uint8_t* s_group192, uint8_t* h_group192) {
+  const uint32_t n = k.n, G = k.G, S = k.sg.S, n_raw = k.n_raw;
+  const std::vector<uint32_t>&seg_off = k.sg.seg_off, &seg_group = k.sg.seg_group;
+  const uint32_t *d_seg_off = k.d_seg_off, *d_seg_group = k.d_seg_group, *d_group_seg = k.d_group_seg, *d_iota = k.d_iota;
+  const uint32_t *d_po = k.d_po, *d_idx = k.d_idx, *d_len = k.d_len;
+  const uint8_t *d_msgs = k.d_msgs, *d_sigs = k.d_sigs, *d_raw = k.d_raw;
+  const uint64_t* d_scalars = k.d_scalars;
+  if (k.draw_scalars) {
     uint32_t kn[11];
     random_bytes(kn, sizeof kn);
     if (int r = ensure_or_release_lines(c, c->scalars, n)) return r;
@@ -1704,36 +1818,40 @@ static int sm_run(bgv_ctx* c, const bgv_sm_batch* b, uint8_t* set_valid, int32_t
     HIPCHK(hipGetLastError());
     d_scalars = c->scalars.p;
   }
-  if (int r = ensure_or_release_lines(c, c->raw_conv, b->n_raw ? b->n_raw : 1)) return r;
-  launch_raw_pks(c->st, d_raw, c->raw_conv.p, b->n_raw);
+  if (int r = ensure_or_release_lines(c, c->raw_conv, n_raw ? n_raw : 1)) return r;
+  launch_raw_pks(c->st, d_raw, c->raw_conv.p, n_raw);
 
-  // view A: the real sets, one job per segment (signature decode, G2 sums)
+  // view A: the real sets, one job per segment ([gather,] signature decode, G2 sums)
   dev_batch dA;
   memset(&dA, 0, sizeof dA);
-  dA.n_sets = n; dA.n_jobs = S; dA.n_raw = b->n_raw; dA.table_n = c->table_n; dA.table = c->table;
-  dA.span_log2 = 6; dA.chunk_bound = n; dA.job_lanes = 36; dA.pairs_per_item = 1; dA.msm = 4; dA.clear_lanes = 9;
+  dA.n_sets = n; dA.n_jobs = S; dA.n_raw = n_raw; dA.table_n = c->table_n; dA.table = c->table;
+  dA.span_log2 = 6; dA.job_lanes = 36; dA.pairs_per_item = 1; dA.msm = 4; dA.clear_lanes = 9;
+  dA.chunk_bound = k.chunk_bound;
+  dA.win = k.win;
   dA.defer_from = n;
-  dA.job_off = d_seg_off; dA.pk_idx = d_idx; dA.raw_pks = c->raw_conv.p;
+  dA.job_off = d_seg_off; dA.pk_off = d_po; dA.pk_idx = d_idx; dA.raw_pks = c->raw_conv.p;
   dA.sigs = d_sigs; dA.sig_len = d_len; dA.scalars = d_scalars;
   dev_work w;
   if (int r = work_alloc(c, dA, w)) return r;
   int r = 0;
   if ((r = c->sm_skip.ensure(n)) || (r = c->sm_zero.ensure(n)) || (r = c->sm_seg_code.ensure(S)) ||
-      (r = c->sm_win.ensure((size_t)S * 16)) || (r = c->sm_hg.ensure(G)) || (r = c->q_part.ensure(2 * (size_t)G)))
+      (r = c->sm_win.ensure((size_t)S * 16)) || (r = c->sm_hg.ensure(G)) || (r = c->q_part.ensure(2 * (size_t)G)) ||
+      (k.agg && ((r = c->sma_pk.ensure(n)) || (r = c->sma_pk_code.ensure(n)))))
     return r;
   HIPCHK(hipMemsetAsync(c->sm_zero.p, 0, (size_t)n * 4, c->st));
   sm_view v;
   memset(&v, 0, sizeof v);
-  v.n_sets = n; v.n_segs = S; v.n_groups = G; v.n_raw = b->n_raw; v.table_n = c->table_n;
+  v.n_sets = n; v.n_segs = S; v.n_groups = G; v.n_raw = n_raw; v.table_n = c->table_n;
   v.seg_off = d_seg_off; v.seg_group = d_seg_group; v.pk_idx = d_idx; v.raw_pks = c->raw_conv.p; v.table = c->table;
   v.scalars = d_scalars; v.sig_code = w.sig_code; v.sig_inf = w.sig_inf; v.skip = c->sm_skip.p; v.set_code = w.set_code;
   v.win = c->sm_win.p; v.p_seg = w.rpk_aff; v.seg_code = c->sm_seg_code.p; v.h_group = c->sm_hg.p; v.h_seg = w.h_aff;
   v.pk_code_v = w.pk_code; v.job_code_v = w.job_code; v.s_seg = w.s_aff; v.s_inf = w.s_inf;
+  if (k.agg) { v.pk_set = c->sma_pk.p; v.pk_set_code = c->sma_pk_code.p; }
 
-  // one hash per group on the hash stream (latency-mode kernels: two lanes per map)
   HIPCHK(hipEventRecord(c->ev_fork, c->st));
   HIPCHK(hipStreamWaitEvent(c->st_hash, c->ev_fork, 0));
-  {
+  HIPCHK(hipStreamWaitEvent(c->st_pk, c->ev_fork, 0));
+  {  // one hash per group on the hash stream (latency-mode kernels: two lanes per map)
     dev_batch dH;
     memset(&dH, 0, sizeof dH);
     dH.n_sets = G; dH.n_jobs = G; dH.split = 1; dH.msgs = d_msgs;
@@ -1746,12 +1864,35 @@ static int sm_run(bgv_ctx* c, const bgv_sm_batch* b, uint8_t* set_valid, int32_t
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(c->ev_dep[ST_HASH], c->st_hash));
   }
-  launch_stage(c->st, ST_SIG, dA, w);
-  launch_sm_classify(c->st, v);
+  // bitfield sets: the decode, which is the critical path, is launched before the key side, whose three
+  // expansion launches would otherwise stand in front of it on the host thread (DESIGN.md section 3f)
+  const bool sig_first = k.expand != nullptr;
+  if (sig_first) launch_stage(c->st, ST_SIG, dA, w);
+  if (k.agg) {  // the keys of every set on the pubkey stream, beside the signature decode
+    dev_batch dP = dA;
+    dP.miller_coop = 36;  // launch_prep: the chunk set-up only, no Miller work items
+    if (k.expand) {  // bitfield sets: the expansion runs where its reader, the gather, runs
+      if (k.expand_count) bits_launch_count(c->st_pk, *k.expand);
+      if (int r2 = bits_launch_expand(c, c->st_pk, *k.expand, k.gathered)) return r2;  // into k.d_idx: reserved by the caller
+    }
+    launch_prep(c->st_pk, dP, w);
+    launch_stage(c->st_pk, ST_PK, dP, w);
+    launch_sma_set_sum(c->st_pk, dP, w, c->sma_pk.p, c->sma_pk_code.p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(c->ev_dep[ST_PK], c->st_pk));
+  }
+  if (!sig_first) launch_stage(c->st, ST_SIG, dA, w);
+  if (k.agg) {
+    HIPCHK(hipStreamWaitEvent(c->st, c->ev_dep[ST_PK], 0));
+    launch_sma_classify(c->st, v);
+  } else {
+    launch_sm_classify(c->st, v);
+  }
   HIPCHK(hipGetLastError());
   HIPCHK(hipEventRecord(c->ev_sigdec, c->st));
   HIPCHK(hipStreamWaitEvent(c->st_pk, c->ev_sigdec, 0));
-  launch_sm_g1_sum(c->st_pk, v);
+  if (k.agg) launch_sma_g1_sum(c->st_pk, v);
+  else launch_sm_g1_sum(c->st_pk, v);
   HIPCHK(hipGetLastError());
   HIPCHK(hipEventRecord(c->ev_dep[ST_PK_SCALE], c->st_pk));
   {
@@ -1774,7 +1915,21 @@ static int sm_run(bgv_ctx* c, const bgv_sm_batch* b, uint8_t* set_valid, int32_t
   dB.n_sets = S; dB.n_jobs = S; dB.pairs_per_item = 1; dB.job_lanes = 36;
   dB.miller_coop = S < 2000 ? 36u : (S < 6000 ? 18u : 6u);
   dB.job_off = d_iota;
-  for (int s = ST_MILLER; s <= ST_JOB_FINAL; s++) launch_stage(c->st, s, dB, w);
+  int first = ST_MILLER;  // one key per set: every stage of the virtual batch in order on st
+  if (k.agg) {
+    // the (P_seg, H(m)) pairs on the hash stream beside the (-G1, S_seg) pairs, as
+    // run_stages places them: a few thousand lanes each, one after the other they
+    // would both be on the critical path
+    HIPCHK(hipEventRecord(c->ev_prep, c->st));
+    HIPCHK(hipStreamWaitEvent(c->st_hash, c->ev_prep, 0));
+    launch_stage(c->st_hash, ST_MILLER, dB, w);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(c->ev_dep[ST_MILLER], c->st_hash));
+    launch_stage(c->st, ST_MILLER_JOBS, dB, w);
+    HIPCHK(hipStreamWaitEvent(c->st, c->ev_dep[ST_MILLER], 0));
+    first = ST_F_TREE;
+  }
+  for (int s = first; s <= ST_JOB_FINAL; s++) launch_stage(c->st, s, dB, w);
   HIPCHK(hipGetLastError());
 
   // first-pass results
@@ -1784,398 +1939,23 @@ static int sm_run(bgv_ctx* c, const bgv_sm_batch* b, uint8_t* set_valid, int32_t
   HIPCHK(hipMemcpyAsync(c->pin_out + o_jr, w.job_result, (size_t)S * 4, hipMemcpyDeviceToHost, c->st));
   HIPCHK(hipMemcpyAsync(c->pin_out + o_sc, w.set_code, (size_t)n * 4, hipMemcpyDeviceToHost, c->st));
   HIPCHK(hipMemcpyAsync(c->pin_out + o_sk, c->sm_skip.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->st));
-  if (p_group96 || s_group192 || h_group192) {
-    if ((r = c->sm_pg.ensure(G)) || (r = c->sm_sg.ensure(G)) || (r = c->dbg_out.ensure((size_t)G * 480))) return r;
-    launch_sm_group_sums(c->st, v, d_group_seg, c->sm_pg.p, c->sm_sg.p);
-    uint8_t* o = c->dbg_out.p;
-    launch_export_g1a(c->st, c->sm_pg.p, o, G);
-    launch_export_g2a(c->st, c->sm_sg.p, o + (size_t)G * 96, G);
-    launch_export_g2a(c->st, c->sm_hg.p, o + (size_t)G * 288, G);
-    HIPCHK(hipGetLastError());
-    if (p_group96) HIPCHK(hipMemcpyAsync(p_group96, o, (size_t)G * 96, hipMemcpyDeviceToHost, c->st));
-    if (s_group192) HIPCHK(hipMemcpyAsync(s_group192, o + (size_t)G * 96, (size_t)G * 192, hipMemcpyDeviceToHost, c->st));
-    if (h_group192) HIPCHK(hipMemcpyAsync(h_group192, o + (size_t)G * 288, (size_t)G * 192, hipMemcpyDeviceToHost, c->st));
-  }
-  HIPCHK(hipStreamSynchronize(c->st));
-  c->staged_pending = false;
-  const int32_t* jr = (const int32_t*)(c->pin_out + o_jr);
-  const int32_t* sc = (const int32_t*)(c->pin_out + o_sc);
-  const uint32_t* sk = (const uint32_t*)(c->pin_out + o_sk);
-  std::vector<uint32_t> list, list_group;
-  uint32_t pairs = 0, groups_retried = 0, last_group = 0xffffffffu;
-  for (uint32_t s = 0; s < S; s++) {
-    const bool ok = jr[s] == 1, retry = jr[s] == 0 || jr[s] == -C_SEG_RETRY;
-    if (jr[s] >= 0) pairs += 2;
-    if (retry && seg_group[s] != last_group) { groups_retried++; last_group = seg_group[s]; }
-    for (uint32_t i = seg_off[s]; i < seg_off[s + 1]; i++) {
-      set_valid[i] = (!sk[i] && ok) ? 1 : 0;
-      if (set_code) set_code[i] = sc[i];
-      if (retry && !sk[i]) { list.push_back(i); list_group.push_back(seg_group[s]); }
-    }
-  }
-  const uint32_t nr = (uint32_t)list.size();
-  if (nr) {
-    // the rare path: the surviving sets of the failing segments, each on its own
-    const size_t a = 256;
-    auto up = [&](size_t x) { return (x + a - 1) & ~(a - 1); };
-    const size_t o_iota = 0, o_idx = up(((size_t)nr + 1) * 4), o_len = o_idx + up((size_t)nr * 4), o_scal = o_len + up((size_t)nr * 4),
-                 o_msg = o_scal + up((size_t)nr * 8), o_sig = o_msg + up((size_t)nr * 32), total = o_sig + up((size_t)nr * 192);
-    if ((r = c->sm_retry.ensure(total)) || (r = c->sm_list.ensure(2 * (size_t)nr))) return r;
-    HIPCHK(hipMemcpyAsync(c->sm_list.p, list.data(), (size_t)nr * 4, hipMemcpyHostToDevice, c->st));
-    HIPCHK(hipMemcpyAsync(c->sm_list.p + nr, list_group.data(), (size_t)nr * 4, hipMemcpyHostToDevice, c->st));
-    uint8_t* base = c->sm_retry.p;
-    sm_retry q;
-    q.n = nr; q.list = c->sm_list.p; q.list_group = c->sm_list.p + nr;
-    q.pk_idx = d_idx; q.msgs = d_msgs; q.sigs = d_sigs; q.sig_len = d_len; q.scalars = d_scalars;
-    q.o_iota = (uint32_t*)(base + o_iota); q.o_idx = (uint32_t*)(base + o_idx); q.o_len = (uint32_t*)(base + o_len);
-    q.o_scalars = (uint64_t*)(base + o_scal); q.o_msgs = base + o_msg; q.o_sigs = base + o_sig;
-    launch_sm_retry_gather(c->st, q);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(c->st));  // prepare() starts the hash maps on another stream
-    bgv_batch bb;
-    memset(&bb, 0, sizeof bb);
-    bb.n_sets = nr; bb.n_jobs = nr; bb.job_offsets = q.o_iota; bb.pk_offsets = q.o_iota; bb.pk_indices = q.o_idx;
-    bb.raw_pks = d_raw; bb.n_raw = b->n_raw; bb.msgs = q.o_msgs; bb.sigs = q.o_sigs; bb.sig_len = q.o_len;
-    bb.scalars = q.o_scalars; bb.on_device = 1;
-    dev_batch d2;
-    if ((r = prepare(c, &bb, d2, true))) return r;
-    dev_work w2;
-    if ((r = work_alloc(c, d2, w2))) return r;
-    if ((r = run_stages(c, d2, w2, 0, ST_COUNT))) return r;
-    std::vector<int32_t> jr2(nr);
-    if ((r = finish_results(c, d2, w2, jr2.data(), nullptr, nullptr))) return r;
-    for (uint32_t k = 0; k < nr; k++) set_valid[list[k]] = jr2[k] == 1 ? 1 : 0;
-  }
-  if (stats) {
-    stats->n_sets = n; stats->n_groups = G; stats->n_segments = S;
-    stats->hashes = G; stats->pairs = pairs;
-    stats->groups_retried = groups_retried; stats->sets_retried = nr;
-    stats->total_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  }
-  return BGV_OK;
-}
-
-int bgv_verify_same_message(bgv_ctx* c, const bgv_sm_batch* b, uint8_t* set_valid, int32_t* set_code, bgv_sm_stats* stats) {
-  const int r_ = sm_run(c, b, set_valid, set_code, stats, nullptr, nullptr, nullptr);
-  hash_path_clear(c);  // these entries report bgv_sm_stats.hashes
-  return r_;
-}
-
-int bgv_debug_same_message(bgv_ctx* c, const bgv_sm_batch* b, uint8_t* set_valid, int32_t* set_code, bgv_sm_stats* stats,
-                           uint8_t* p_group96, uint8_t* s_group192, uint8_t* h_group192) {
-  const int r_ = sm_run(c, b, set_valid, set_code, stats, p_group96, s_group192, h_group192);
-  hash_path_clear(c);  // these entries report bgv_sm_stats.hashes
-  return r_;
-}
-
-// ---- same-message batches of aggregate sets ----------------------------------
-// bgv_verify_same_message_agg: sm_run with a set's key an aggregate.  Layout:
-//   st_pk   : chunk set-up -> gather (k_pk_chunk) -> per-set fold (k_sma_set_sum)
-//             beside the signature decode, then [classify] the weighted sum
-//             over the folded keys (k_sma_g1_digit / k_sm_g1_fold)
-//   st      : sig decode + subgroup -> [set sums] classify -> G2 sums ->
-//             [pk, hash] apply -> the (-G1, S_seg) pairs -> [set pairs] folds
-//             and final exponentiations of the virtual batch, as in sm_run
-//   st_hash : one hash per group, then [apply] the (P_seg, H(m)) pairs beside
-//             the (-G1, S_seg) ones
-// The retry takes the surviving sets of failing segments with PK_i as a raw key.
-
-static int sma_check_args(const bgv_sma_batch* b) {
-  if (!b) return fail(BGV_E_INVALID_ARG, "batch is NULL");
-  if (b->n_sets == 0 && b->n_groups == 0) return BGV_OK;
-  if (b->n_groups > b->n_sets) return fail(BGV_E_INVALID_ARG, "n_groups %u > n_sets %u (a group is never empty)", b->n_groups, b->n_sets);
-  if (b->n_groups == 0) return fail(BGV_E_INVALID_ARG, "n_sets %u without a group", b->n_sets);
-  if (!b->group_offsets || !b->pk_offsets || !b->pk_indices || !b->msgs || !b->sigs || !b->sig_len)
-    return fail(BGV_E_INVALID_ARG, "missing batch array");
-  if (b->n_raw && !b->raw_pks) return fail(BGV_E_INVALID_ARG, "n_raw > 0 but raw_pks is NULL");
-  return BGV_OK;
-}
-
-// `go`: the copy of the group offsets the segments are cut from
-static int sma_check_groups(const bgv_sma_batch* b, const uint32_t* go) {
-  const uint32_t n = b->n_sets, G = b->n_groups;
-  if (go[0] != 0 || go[G] != n) return fail(BGV_E_INVALID_ARG, "group_offsets must span [0, n_sets]");
-  for (uint32_t g = 0; g < G; g++) {
-    if (go[g + 1] < go[g]) return fail(BGV_E_INVALID_ARG, "group_offsets not monotone");
-    if (go[g + 1] == go[g]) return fail(BGV_E_INVALID_ARG, "group %u is empty", g);
-  }
-  return BGV_OK;
-}
-
-// `po`: the copy of the key offsets the device will see; total: the length of pk_indices that is staged
-static int sma_check_keys(const bgv_sma_batch* b, const uint32_t* po, uint32_t total) {
-  const uint32_t n = b->n_sets;
-  if (po[0] != 0 || po[n] != total) return fail(BGV_E_INVALID_ARG, "pk_offsets must span [0, total]");
-  for (uint32_t i = 0; i < n; i++)
-    if (po[i + 1] < po[i]) return fail(BGV_E_INVALID_ARG, "pk_offsets not monotone");
-  for (uint32_t i = 0; i < n; i++)
-    if (po[i + 1] == po[i]) return fail(BGV_E_EMPTY_SET, "EMPTY_AGGREGATE_ARRAY (set %u)", i);
-  return BGV_OK;
-}
-
-int bgv_sma_check(const bgv_sma_batch* b) {
-  if (int r = sma_check_args(b)) return r;
-  if (b->on_device || b->n_sets == 0) return BGV_OK;
-  if (int r = sma_check_groups(b, b->group_offsets)) return r;
-  if (int r = sma_check_keys(b, b->pk_offsets, b->pk_offsets[b->n_sets])) return r;
-  if (b->scalars)
-    for (uint32_t i = 0; i < b->n_sets; i++)
-      if (!b->scalars[i]) return fail(BGV_E_INVALID_ARG, "scalars[%u] is zero", i);
-  return BGV_OK;
-}
-
-// the segments of a same-message batch: every group cut into runs of at most SM_SEG sets
-struct sma_segs {
-  std::vector<uint32_t> seg_off, seg_group, group_seg, iota;
-  uint32_t S = 0;
-};
-static void sma_cut_segments(const std::vector<uint32_t>& go, uint32_t n, sma_segs& sg) {
-  const uint32_t G = (uint32_t)go.size() - 1;
-  sg.group_seg.resize((size_t)G + 1);
-  sg.seg_off.reserve(n / SM_SEG + G + 1);
-  for (uint32_t g = 0; g < G; g++) {
-    sg.group_seg[g] = (uint32_t)sg.seg_off.size();
-    for (uint32_t i = go[g]; i < go[g + 1]; i += SM_SEG) { sg.seg_off.push_back(i); sg.seg_group.push_back(g); }
-  }
-  sg.S = (uint32_t)sg.seg_off.size();
-  sg.group_seg[G] = sg.S;
-  sg.seg_off.push_back(n);
-  sg.iota.resize((size_t)sg.S + 1);
-  for (uint32_t s = 0; s <= sg.S; s++) sg.iota[s] = s;
-}
-// device view of such a batch once its arrays are staged (or resident)
-struct sma_dev {
-  uint32_t n, G, S, n_raw;
-  const sma_segs* sg;
-  const uint32_t *d_seg_off, *d_seg_group, *d_group_seg, *d_iota, *d_po, *d_idx, *d_len;
-  const uint8_t *d_msgs, *d_sigs, *d_raw;
-  const uint64_t* d_scalars;
-  bool draw_scalars;          // the caller gave none: drawn on the device (d_scalars is then not read)
-  uint32_t chunk_bound;       // grid bound of the gather
-  // bgv_verify_same_message_bits: the per-set windows (contexts with sums, else
-  // NULL) and the expansion still to run on the pubkey stream
-  const pk_window* win;
-  bits_args* expand;
-  bool expand_count;  // count and scan too (host batches: their totals come from the host plan)
-  uint32_t gathered;  // keys the expansion holds
-};
-static int sma_back(bgv_ctx* c, sma_dev& k, std::chrono::steady_clock::time_point t0, uint8_t* set_valid, int32_t* set_code,
-                    bgv_sm_stats* stats, uint8_t* pk_set96, uint8_t* p_group96, uint8_t* s_group192, uint8_t* h_group192);
-
-static int sma_run(bgv_ctx* c, const bgv_sma_batch* b, uint8_t* set_valid, int32_t* set_code, bgv_sm_stats* stats,
-                   uint8_t* pk_set96, uint8_t* p_group96, uint8_t* s_group192, uint8_t* h_group192) {
-  if (!c) return fail(BGV_E_INVALID_ARG, "null ctx");
-  if (int r = sma_check_args(b)) return r;
-  if (stats) memset(stats, 0, sizeof *stats);
-  const uint32_t n = b->n_sets, G = b->n_groups;
-  if (n == 0) return BGV_OK;
-  if (!set_valid) return fail(BGV_E_INVALID_ARG, "set_valid is NULL");
-  c->partial_pending = false;
-  HIPCHK(hipSetDevice(c->device));
-  active_guard ag(c->device);
-  const auto t0 = std::chrono::steady_clock::now();
-  // the group offsets and the key total come to the host first: the segments
-  // and the gather's grid bound are cut from these copies
-  std::vector<uint32_t> go((size_t)G + 1);
-  uint32_t total = 0;
-  if (b->on_device) {
-    HIPCHK(hipMemcpyAsync(go.data(), b->group_offsets, go.size() * 4, hipMemcpyDeviceToHost, c->st));
-    HIPCHK(hipMemcpyAsync(&total, b->pk_offsets + n, 4, hipMemcpyDeviceToHost, c->st));
-    HIPCHK(hipStreamSynchronize(c->st));
-  } else {
-    memcpy(go.data(), b->group_offsets, go.size() * 4);
-    total = b->pk_offsets[n];  // sizes the pk_indices copy; re-checked on the pinned copy
-  }
-  if (int r = sma_check_groups(b, go.data())) return r;
-  const bool host = !b->on_device;
-
-  // staging: the segment tables always, the batch arrays of a host batch
-  sma_dev k;
-  memset(&k, 0, sizeof k);
-  k.n = n; k.G = G; k.n_raw = b->n_raw;
-  k.d_po = b->pk_offsets; k.d_idx = b->pk_indices; k.d_len = b->sig_len;
-  k.d_msgs = b->msgs; k.d_sigs = b->sigs; k.d_raw = b->raw_pks; k.d_scalars = b->scalars;
-  k.draw_scalars = !b->scalars;
-  sma_segs sg;
-  sma_cut_segments(go, n, sg);
-  const uint32_t S = sg.S;
-  k.S = S; k.sg = &sg;
-  stage_seg segs[11] = {
-      {sg.seg_off.data(), ((size_t)S + 1) * 4, (const void**)&k.d_seg_off, 0},
-      {sg.seg_group.data(), (size_t)S * 4, (const void**)&k.d_seg_group, 0},
-      {sg.group_seg.data(), ((size_t)G + 1) * 4, (const void**)&k.d_group_seg, 0},
-      {sg.iota.data(), ((size_t)S + 1) * 4, (const void**)&k.d_iota, 0},
-      {b->pk_offsets, ((size_t)n + 1) * 4, (const void**)&k.d_po, 0},
-      {b->pk_indices, (size_t)total * 4, (const void**)&k.d_idx, 0},
-      {b->msgs, (size_t)G * 32, (const void**)&k.d_msgs, 0},
-      {b->raw_pks, (size_t)b->n_raw * 96, (const void**)&k.d_raw, 0},
-      {b->scalars, b->scalars ? (size_t)n * 8 : 0, (const void**)&k.d_scalars, 0},
-      {b->sigs, (size_t)n * 192, (const void**)&k.d_sigs, 0},
-      {b->sig_len, (size_t)n * 4, (const void**)&k.d_len, 0},
-  };
-  size_t bytes = 0;
-  if (int r = stage_pack(c, segs, host ? 11 : 4, bytes)) return r;
-  if (host) {  // the contract, on the pinned copy the device will see
-    const uint32_t* po = (const uint32_t*)(c->pin_in + segs[4].off);
-    if (int r = sma_check_keys(b, po, total)) return r;
-    if (b->scalars) {
-      const uint64_t* sc = (const uint64_t*)(c->pin_in + segs[8].off);
-      for (uint32_t i = 0; i < n; i++)
-        if (!sc[i]) return fail(BGV_E_INVALID_ARG, "scalars[%u] is zero", i);
-    }
-  }
-  if (int r = stage_issue(c, bytes)) return r;
-  k.chunk_bound = total / PK_CHUNK + n;  // as prepare() sets it: sum ceil(k_i / 32) <= total / 32 + n
-  return sma_back(c, k, t0, set_valid, set_code, stats, pk_set96, p_group96, s_group192, h_group192);
-}
-
-// The device half of a same-message call over aggregate keys, from the staged
-// (or resident) arrays on: shared by bgv_verify_same_message_agg and
-// bgv_verify_same_message_bits.
-static int sma_back(bgv_ctx* c, sma_dev& k, std::chrono::steady_clock::time_point t0, uint8_t* set_valid, int32_t* set_code,
-                    bgv_sm_stats* stats, uint8_t* pk_set96, uint8_t* p_group96, uint8_t* s_group192, uint8_t* h_group192) {
-  const uint32_t n = k.n, G = k.G, S = k.S, n_raw = k.n_raw;
-  const std::vector<uint32_t>&seg_off = k.sg->seg_off, &seg_group = k.sg->seg_group;
-  const uint32_t *d_seg_off = k.d_seg_off, *d_seg_group = k.d_seg_group, *d_group_seg = k.d_group_seg, *d_iota = k.d_iota;
-  const uint32_t *d_po = k.d_po, *d_idx = k.d_idx, *d_len = k.d_len;
-  const uint8_t *d_msgs = k.d_msgs, *d_sigs = k.d_sigs, *d_raw = k.d_raw;
-  const uint64_t* d_scalars = k.d_scalars;
-  if (k.draw_scalars) {
-    uint32_t kn[11];
-    random_bytes(kn, sizeof kn);
-    if (int r = ensure_or_release_lines(c, c->scalars, n)) return r;
-    launch_gen_scalars(c->st, kn, kn + 8, c->scalars.p, n);
-    HIPCHK(hipGetLastError());
-    d_scalars = c->scalars.p;
-  }
-  if (int r = ensure_or_release_lines(c, c->raw_conv, n_raw ? n_raw : 1)) return r;
-  launch_raw_pks(c->st, d_raw, c->raw_conv.p, n_raw);
-
-  // view A: the real sets, one job per segment (gather, signature decode, G2 sums)
-  dev_batch dA;
-  memset(&dA, 0, sizeof dA);
-  dA.n_sets = n; dA.n_jobs = S; dA.n_raw = n_raw; dA.table_n = c->table_n; dA.table = c->table;
-  dA.span_log2 = 6; dA.job_lanes = 36; dA.pairs_per_item = 1; dA.msm = 4; dA.clear_lanes = 9;
-  dA.chunk_bound = k.chunk_bound;
-  dA.win = k.win;
-  dA.defer_from = n;
-  dA.job_off = d_seg_off; dA.pk_off = d_po; dA.pk_idx = d_idx; dA.raw_pks = c->raw_conv.p;
-  dA.sigs = d_sigs; dA.sig_len = d_len; dA.scalars = d_scalars;
-  dev_work w;
-  if (int r = work_alloc(c, dA, w)) return r;
-  int r = 0;
-  if ((r = c->sm_skip.ensure(n)) || (r = c->sm_zero.ensure(n)) || (r = c->sm_seg_code.ensure(S)) ||
-      (r = c->sm_win.ensure((size_t)S * 16)) || (r = c->sm_hg.ensure(G)) || (r = c->q_part.ensure(2 * (size_t)G)) ||
-      (r = c->sma_pk.ensure(n)) || (r = c->sma_pk_code.ensure(n)))
-    return r;
-  HIPCHK(hipMemsetAsync(c->sm_zero.p, 0, (size_t)n * 4, c->st));
-  sm_view v;
-  memset(&v, 0, sizeof v);
-  v.n_sets = n; v.n_segs = S; v.n_groups = G; v.n_raw = n_raw; v.table_n = c->table_n;
-  v.seg_off = d_seg_off; v.seg_group = d_seg_group; v.pk_idx = d_idx; v.raw_pks = c->raw_conv.p; v.table = c->table;
-  v.scalars = d_scalars; v.sig_code = w.sig_code; v.sig_inf = w.sig_inf; v.skip = c->sm_skip.p; v.set_code = w.set_code;
-  v.win = c->sm_win.p; v.p_seg = w.rpk_aff; v.seg_code = c->sm_seg_code.p; v.h_group = c->sm_hg.p; v.h_seg = w.h_aff;
-  v.pk_code_v = w.pk_code; v.job_code_v = w.job_code; v.s_seg = w.s_aff; v.s_inf = w.s_inf;
-  v.pk_set = c->sma_pk.p; v.pk_set_code = c->sma_pk_code.p;
-
-  HIPCHK(hipEventRecord(c->ev_fork, c->st));
-  HIPCHK(hipStreamWaitEvent(c->st_hash, c->ev_fork, 0));
-  HIPCHK(hipStreamWaitEvent(c->st_pk, c->ev_fork, 0));
-  {  // one hash per group on the hash stream (latency-mode kernels: two lanes per map)
-    dev_batch dH;
-    memset(&dH, 0, sizeof dH);
-    dH.n_sets = G; dH.n_jobs = G; dH.split = 1; dH.msgs = d_msgs;
-    dH.clear_lanes = G < 9000 ? 9u : (G < 16500 ? 3u : 1u);
-    dev_work wH;
-    memset(&wH, 0, sizeof wH);
-    wH.q_part = c->q_part.p;
-    wH.h_aff = c->sm_hg.p;
-    launch_stage(c->st_hash, ST_HASH, dH, wH);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(c->ev_dep[ST_HASH], c->st_hash));
-  }
-  // bitfield sets: the decode, which is the critical path, is launched before the key side, whose three
-  // expansion launches would otherwise stand in front of it on the host thread (DESIGN.md section 3f)
-  const bool sig_first = k.expand != nullptr;
-  if (sig_first) launch_stage(c->st, ST_SIG, dA, w);
-  {  // the keys of every set on the pubkey stream, beside the signature decode
-    dev_batch dP = dA;
-    dP.miller_coop = 36;  // launch_prep: the chunk set-up only, no Miller work items
-    if (k.expand) {  // bitfield sets: the expansion runs where its reader, the gather, runs
-      if (k.expand_count) bits_launch_count(c->st_pk, *k.expand);
-      if (int r2 = bits_launch_expand(c, c->st_pk, *k.expand, k.gathered)) return r2;  // into k.d_idx: reserved by the caller
-    }
-    launch_prep(c->st_pk, dP, w);
-    launch_stage(c->st_pk, ST_PK, dP, w);
-    launch_sma_set_sum(c->st_pk, dP, w, c->sma_pk.p, c->sma_pk_code.p);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(c->ev_dep[ST_PK], c->st_pk));
-  }
-  if (!sig_first) launch_stage(c->st, ST_SIG, dA, w);
-  HIPCHK(hipStreamWaitEvent(c->st, c->ev_dep[ST_PK], 0));
-  launch_sma_classify(c->st, v);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(c->ev_sigdec, c->st));
-  HIPCHK(hipStreamWaitEvent(c->st_pk, c->ev_sigdec, 0));
-  launch_sma_g1_sum(c->st_pk, v);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(c->ev_dep[ST_PK_SCALE], c->st_pk));
-  {
-    // the per-job MSM sums what `skip` leaves in and rejects nothing (sm_run)
-    dev_work wz = w;
-    wz.sig_code = c->sm_zero.p;
-    wz.pk_code = c->sm_zero.p;
-    wz.sig_inf = c->sm_skip.p;
-    launch_stage(c->st, ST_SIG_SCALE, dA, wz);
-    launch_stage(c->st, ST_S_TREE, dA, wz);
-    HIPCHK(hipGetLastError());
-  }
-  HIPCHK(hipStreamWaitEvent(c->st, c->ev_dep[ST_PK_SCALE], 0));
-  HIPCHK(hipStreamWaitEvent(c->st, c->ev_dep[ST_HASH], 0));
-  launch_sm_apply(c->st, v);
-  // view B: the virtual batch, segment s = set s = job s
-  dev_batch dB;
-  memset(&dB, 0, sizeof dB);
-  dB.n_sets = S; dB.n_jobs = S; dB.pairs_per_item = 1; dB.job_lanes = 36;
-  dB.miller_coop = S < 2000 ? 36u : (S < 6000 ? 18u : 6u);
-  dB.job_off = d_iota;
-  // the (P_seg, H(m)) pairs on the hash stream beside the (-G1, S_seg) pairs, as
-  // run_stages places them: a few thousand lanes each, one after the other they
-  // would both be on the critical path
-  HIPCHK(hipEventRecord(c->ev_prep, c->st));
-  HIPCHK(hipStreamWaitEvent(c->st_hash, c->ev_prep, 0));
-  launch_stage(c->st_hash, ST_MILLER, dB, w);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(c->ev_dep[ST_MILLER], c->st_hash));
-  launch_stage(c->st, ST_MILLER_JOBS, dB, w);
-  HIPCHK(hipStreamWaitEvent(c->st, c->ev_dep[ST_MILLER], 0));
-  for (int s = ST_F_TREE; s <= ST_JOB_FINAL; s++) launch_stage(c->st, s, dB, w);
-  HIPCHK(hipGetLastError());
-
-  // first-pass results
-  const size_t o_jr = 256, o_sc = o_jr + (((size_t)S * 4 + 255) & ~size_t(255)), o_sk = o_sc + (((size_t)n * 4 + 255) & ~size_t(255));
-  if ((r = pinned_reserve(c->pin_out, c->pin_out_cap, o_sk + (size_t)n * 4))) return r;
-  HIPCHK(hipMemcpyAsync(c->pin_out, w.flags, 4, hipMemcpyDeviceToHost, c->st));
-  HIPCHK(hipMemcpyAsync(c->pin_out + o_jr, w.job_result, (size_t)S * 4, hipMemcpyDeviceToHost, c->st));
-  HIPCHK(hipMemcpyAsync(c->pin_out + o_sc, w.set_code, (size_t)n * 4, hipMemcpyDeviceToHost, c->st));
-  HIPCHK(hipMemcpyAsync(c->pin_out + o_sk, c->sm_skip.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->st));
-  if (pk_set96 || p_group96 || s_group192 || h_group192) {
+  if (pk_set96 || p_group96 || s_group192 || h_group192) {  // the debug entries; pk_set96: aggregate keys only
     const size_t o_set = (size_t)G * 480;
-    if ((r = c->sm_pg.ensure(G)) || (r = c->sm_sg.ensure(G)) || (r = c->sma_aff.ensure(n)) ||
-        (r = c->dbg_out.ensure(o_set + (size_t)n * 96)))
+    if ((r = c->sm_pg.ensure(G)) || (r = c->sm_sg.ensure(G)) || (k.agg && (r = c->sma_aff.ensure(n))) ||
+        (r = c->dbg_out.ensure(o_set + (k.agg ? (size_t)n * 96 : 0))))
       return r;
     launch_sm_group_sums(c->st, v, d_group_seg, c->sm_pg.p, c->sm_sg.p);
-    launch_sma_pk_aff(c->st, c->sma_pk.p, c->sma_aff.p, n);
+    if (k.agg) launch_sma_pk_aff(c->st, c->sma_pk.p, c->sma_aff.p, n);
     uint8_t* o = c->dbg_out.p;
     launch_export_g1a(c->st, c->sm_pg.p, o, G);
     launch_export_g2a(c->st, c->sm_sg.p, o + (size_t)G * 96, G);
     launch_export_g2a(c->st, c->sm_hg.p, o + (size_t)G * 288, G);
-    launch_export_g1a(c->st, c->sma_aff.p, o + o_set, n);
+    if (k.agg) launch_export_g1a(c->st, c->sma_aff.p, o + o_set, n);
     HIPCHK(hipGetLastError());
     if (p_group96) HIPCHK(hipMemcpyAsync(p_group96, o, (size_t)G * 96, hipMemcpyDeviceToHost, c->st));
     if (s_group192) HIPCHK(hipMemcpyAsync(s_group192, o + (size_t)G * 96, (size_t)G * 192, hipMemcpyDeviceToHost, c->st));
     if (h_group192) HIPCHK(hipMemcpyAsync(h_group192, o + (size_t)G * 288, (size_t)G * 192, hipMemcpyDeviceToHost, c->st));
-    if (pk_set96) HIPCHK(hipMemcpyAsync(pk_set96, o + o_set, (size_t)n * 96, hipMemcpyDeviceToHost, c->st));
+    if (k.agg && pk_set96) HIPCHK(hipMemcpyAsync(pk_set96, o + o_set, (size_t)n * 96, hipMemcpyDeviceToHost, c->st));
   }
   HIPCHK(hipStreamSynchronize(c->st));
   c->staged_pending = false;
@@ -2197,29 +1977,35 @@ static int sma_back(bgv_ctx* c, sma_dev& k, std::chrono::steady_clock::time_poin
   const uint32_t nr = (uint32_t)list.size();
   if (nr) {
     // the rare path: the surviving sets of the failing segments, each on its
-    // own against its aggregated key, which enters as row k of a raw-key table
+    // own.  An aggregated key enters as row j of a raw-key table (o_pk).
     const size_t a = 256;
     auto up = [&](size_t x) { return (x + a - 1) & ~(a - 1); };
     const size_t o_iota = 0, o_idx = up(((size_t)nr + 1) * 4), o_len = o_idx + up((size_t)nr * 4), o_scal = o_len + up((size_t)nr * 4),
                  o_msg = o_scal + up((size_t)nr * 8), o_sig = o_msg + up((size_t)nr * 32), o_pk = o_sig + up((size_t)nr * 192),
-                 total_r = o_pk + up((size_t)nr * 96);
-    if ((r = c->sm_retry.ensure(total_r)) || (r = c->sm_list.ensure(2 * (size_t)nr)) || (r = c->sma_aff.ensure(nr))) return r;
+                 total_r = k.agg ? o_pk + up((size_t)nr * 96) : o_pk;
+    if ((r = c->sm_retry.ensure(total_r)) || (r = c->sm_list.ensure(2 * (size_t)nr)) || (k.agg && (r = c->sma_aff.ensure(nr)))) return r;
     HIPCHK(hipMemcpyAsync(c->sm_list.p, list.data(), (size_t)nr * 4, hipMemcpyHostToDevice, c->st));
     HIPCHK(hipMemcpyAsync(c->sm_list.p + nr, list_group.data(), (size_t)nr * 4, hipMemcpyHostToDevice, c->st));
     uint8_t* base = c->sm_retry.p;
     sm_retry q;
     q.n = nr; q.list = c->sm_list.p; q.list_group = c->sm_list.p + nr;
-    q.pk_idx = nullptr; q.msgs = d_msgs; q.sigs = d_sigs; q.sig_len = d_len; q.scalars = d_scalars;
+    q.pk_idx = k.agg ? nullptr : d_idx; q.msgs = d_msgs; q.sigs = d_sigs; q.sig_len = d_len; q.scalars = d_scalars;
     q.o_iota = (uint32_t*)(base + o_iota); q.o_idx = (uint32_t*)(base + o_idx); q.o_len = (uint32_t*)(base + o_len);
     q.o_scalars = (uint64_t*)(base + o_scal); q.o_msgs = base + o_msg; q.o_sigs = base + o_sig;
-    launch_sma_retry_gather(c->st, q, c->sma_pk.p, c->sma_aff.p);
-    launch_export_g1a(c->st, c->sma_aff.p, base + o_pk, nr);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(c->st));  // prepare() starts the hash maps on another stream
     bgv_batch bb;
     memset(&bb, 0, sizeof bb);
+    if (k.agg) {
+      launch_sma_retry_gather(c->st, q, c->sma_pk.p, c->sma_aff.p);
+      launch_export_g1a(c->st, c->sma_aff.p, base + o_pk, nr);
+      bb.raw_pks = base + o_pk; bb.n_raw = nr;
+    } else {
+      launch_sm_retry_gather(c->st, q);
+      bb.raw_pks = d_raw; bb.n_raw = n_raw;
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(c->st));  // prepare() starts the hash maps on another stream
     bb.n_sets = nr; bb.n_jobs = nr; bb.job_offsets = q.o_iota; bb.pk_offsets = q.o_iota; bb.pk_indices = q.o_idx;
-    bb.raw_pks = base + o_pk; bb.n_raw = nr; bb.msgs = q.o_msgs; bb.sigs = q.o_sigs; bb.sig_len = q.o_len;
+    bb.msgs = q.o_msgs; bb.sigs = q.o_sigs; bb.sig_len = q.o_len;
     bb.scalars = q.o_scalars; bb.on_device = 1;
     dev_batch d2;
     if ((r = prepare(c, &bb, d2, true))) return r;
@@ -2228,116 +2014,110 @@ static int sma_back(bgv_ctx* c, sma_dev& k, std::chrono::steady_clock::time_poin
     if ((r = run_stages(c, d2, w2, 0, ST_COUNT))) return r;
     std::vector<int32_t> jr2(nr);
     if ((r = finish_results(c, d2, w2, jr2.data(), nullptr, nullptr))) return r;
-    for (uint32_t k = 0; k < nr; k++) set_valid[list[k]] = jr2[k] == 1 ? 1 : 0;
+    for (uint32_t j = 0; j < nr; j++) set_valid[list[j]] = jr2[j] == 1 ? 1 : 0;
   }
   if (stats) {
     stats->n_sets = n; stats->n_groups = G; stats->n_segments = S;
     stats->hashes = G; stats->pairs = pairs;
     stats->groups_retried = groups_retried; stats->sets_retried = nr;
-    stats->total_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    stats->total_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - k.t0).count();
   }
   return BGV_OK;
 }
 
-int bgv_verify_same_message_agg(bgv_ctx* c, const bgv_sma_batch* b, uint8_t* set_valid, int32_t* set_code, bgv_sm_stats* stats) {
-  const int r_ = sma_run(c, b, set_valid, set_code, stats, nullptr, nullptr, nullptr, nullptr);
-  hash_path_clear(c);  // these entries report bgv_sm_stats.hashes
-  return r_;
+static int sm_run(bgv_ctx* c, const bgv_sm_batch* b, uint8_t* set_valid, int32_t* set_code, bgv_sm_stats* stats,
+                  uint8_t* p_group96, uint8_t* s_group192, uint8_t* h_group192) {
+  sm_dev k;
+  if (int r = sm_open(c, b, set_valid, stats, k)) return r;
+  if (!k.n) return BGV_OK;
+  if (int r = sm_groups(c, k, b->group_offsets, b->on_device)) return r;
+  const uint32_t n = k.n, G = k.G, S = k.sg.S;
+  const bool host = !b->on_device;
+  k.d_idx = b->pk_indices;
+  // staging: the segment tables always, the batch arrays of a host batch
+  stage_seg segs[10] = {
+      {k.sg.seg_off.data(), ((size_t)S + 1) * 4, (const void**)&k.d_seg_off, 0},
+      {k.sg.seg_group.data(), (size_t)S * 4, (const void**)&k.d_seg_group, 0},
+      {k.sg.group_seg.data(), ((size_t)G + 1) * 4, (const void**)&k.d_group_seg, 0},
+      {k.sg.iota.data(), ((size_t)S + 1) * 4, (const void**)&k.d_iota, 0},
+      {b->pk_indices, (size_t)n * 4, (const void**)&k.d_idx, 0},
+      {b->msgs, (size_t)G * 32, (const void**)&k.d_msgs, 0},
+      {b->raw_pks, (size_t)b->n_raw * 96, (const void**)&k.d_raw, 0},
+      {b->scalars, b->scalars ? (size_t)n * 8 : 0, (const void**)&k.d_scalars, 0},
+      {b->sigs, (size_t)n * 192, (const void**)&k.d_sigs, 0},
+      {b->sig_len, (size_t)n * 4, (const void**)&k.d_len, 0},
+  };
+  size_t bytes = 0;
+  if (int r = stage_pack(c, segs, host ? 10 : 4, bytes)) return r;
+  if (host && b->scalars)  // checked on the pinned copy
+    if (int r = scalars_nonzero((const uint64_t*)(c->pin_in + segs[7].off), n)) return r;
+  if (int r = stage_issue(c, bytes)) return r;
+  return sm_back(c, k, set_valid, set_code, stats, nullptr, p_group96, s_group192, h_group192);
 }
 
-int bgv_debug_same_message_agg(bgv_ctx* c, const bgv_sma_batch* b, uint8_t* set_valid, int32_t* set_code, bgv_sm_stats* stats,
-                               uint8_t* pk_set96, uint8_t* p_group96, uint8_t* s_group192, uint8_t* h_group192) {
-  const int r_ = sma_run(c, b, set_valid, set_code, stats, pk_set96, p_group96, s_group192, h_group192);
-  hash_path_clear(c);  // these entries report bgv_sm_stats.hashes
-  return r_;
+static int sma_run(bgv_ctx* c, const bgv_sma_batch* b, uint8_t* set_valid, int32_t* set_code, bgv_sm_stats* stats,
+                   uint8_t* pk_set96, uint8_t* p_group96, uint8_t* s_group192, uint8_t* h_group192) {
+  sm_dev k;
+  if (int r = sm_open(c, b, set_valid, stats, k)) return r;
+  if (!k.n) return BGV_OK;
+  const uint32_t n = k.n, G = k.G;
+  const bool host = !b->on_device;
+  // the key total comes with the group offsets: the gather's grid bound is cut from it
+  uint32_t total = host ? b->pk_offsets[n] : 0;  // host: sizes the pk_indices copy; re-checked on the pinned copy
+  if (int r = sm_groups(c, k, b->group_offsets, b->on_device, b->pk_offsets + n, &total)) return r;
+  const uint32_t S = k.sg.S;
+  k.agg = true;
+  k.d_po = b->pk_offsets; k.d_idx = b->pk_indices;
+  // staging: the segment tables always, the batch arrays of a host batch
+  stage_seg segs[11] = {
+      {k.sg.seg_off.data(), ((size_t)S + 1) * 4, (const void**)&k.d_seg_off, 0},
+      {k.sg.seg_group.data(), (size_t)S * 4, (const void**)&k.d_seg_group, 0},
+      {k.sg.group_seg.data(), ((size_t)G + 1) * 4, (const void**)&k.d_group_seg, 0},
+      {k.sg.iota.data(), ((size_t)S + 1) * 4, (const void**)&k.d_iota, 0},
+      {b->pk_offsets, ((size_t)n + 1) * 4, (const void**)&k.d_po, 0},
+      {b->pk_indices, (size_t)total * 4, (const void**)&k.d_idx, 0},
+      {b->msgs, (size_t)G * 32, (const void**)&k.d_msgs, 0},
+      {b->raw_pks, (size_t)b->n_raw * 96, (const void**)&k.d_raw, 0},
+      {b->scalars, b->scalars ? (size_t)n * 8 : 0, (const void**)&k.d_scalars, 0},
+      {b->sigs, (size_t)n * 192, (const void**)&k.d_sigs, 0},
+      {b->sig_len, (size_t)n * 4, (const void**)&k.d_len, 0},
+  };
+  size_t bytes = 0;
+  if (int r = stage_pack(c, segs, host ? 11 : 4, bytes)) return r;
+  if (host) {  // the contract, on the pinned copy the device will see
+    if (int r = sma_check_keys(b, (const uint32_t*)(c->pin_in + segs[4].off), total)) return r;
+    if (b->scalars)
+      if (int r = scalars_nonzero((const uint64_t*)(c->pin_in + segs[8].off), n)) return r;
+  }
+  if (int r = stage_issue(c, bytes)) return r;
+  k.chunk_bound = total / PK_CHUNK + n;  // as prepare() sets it: sum ceil(k_i / 32) <= total / 32 + n
+  return sm_back(c, k, set_valid, set_code, stats, pk_set96, p_group96, s_group192, h_group192);
 }
 
-// ---- same-message batches of committee sets -----------------------------------
-// bgv_verify_same_message_bits: the sets of bgv_verify_same_message_agg given as
-// bgv_verify_bits gives them.  The front is bits_front's (set-up, host plan,
-// expansion), the device half sma_back with the expansion buffers as pk_off /
-// pk_idx and the windows of a context with sums.  The expansion runs on st_pk in
-// front of the gather, its only reader: the signature decode on st and the
-// hashes on st_hash start without it.
-
-static int smb_check_args(const bgv_smb_batch* b) {
-  if (!b) return fail(BGV_E_INVALID_ARG, "batch is NULL");
-  if (b->n_sets == 0 && b->n_groups == 0) return BGV_OK;
-  if (b->n_groups > b->n_sets) return fail(BGV_E_INVALID_ARG, "n_groups %u > n_sets %u (a group is never empty)", b->n_groups, b->n_sets);
-  if (b->n_groups == 0) return fail(BGV_E_INVALID_ARG, "n_sets %u without a group", b->n_sets);
-  if (!b->group_offsets || !b->src || !b->msgs || !b->sigs || !b->sig_len) return fail(BGV_E_INVALID_ARG, "missing batch array");
-  if (b->bits_len && !b->bits) return fail(BGV_E_INVALID_ARG, "bits_len > 0 but bits is NULL");
-  if (b->n_indices && !b->pk_indices) return fail(BGV_E_INVALID_ARG, "n_indices > 0 but pk_indices is NULL");
-  if (b->n_raw && !b->raw_pks) return fail(BGV_E_INVALID_ARG, "n_raw > 0 but raw_pks is NULL");
-  return BGV_OK;
-}
-
-static int smb_check_groups(const bgv_smb_batch* b, const uint32_t* go) {
-  bgv_sma_batch a;
-  memset(&a, 0, sizeof a);
-  a.n_sets = b->n_sets; a.n_groups = b->n_groups;
-  return sma_check_groups(&a, go);
-}
-
-int bgv_smb_check(const bgv_smb_batch* b, const uint32_t* list_len) {
-  if (int r = smb_check_args(b)) return r;
-  if (!list_len) return fail(BGV_E_INVALID_ARG, "list_len is NULL");
-  if (b->on_device || b->n_sets == 0) return BGV_OK;
-  if (int r = smb_check_groups(b, b->group_offsets)) return r;
-  bits_view v;
-  bits_host_view(v, list_len, nullptr);
-  v.bits = b->bits; v.bits_len = b->bits_len; v.pk_indices = b->pk_indices; v.n_indices = b->n_indices;
-  bits_plan_out po;
-  if (int r = bits_check_sources(b->n_sets, (const bits_src*)b->src, v, &po, nullptr)) return r;
-  if (b->scalars)
-    for (uint32_t i = 0; i < b->n_sets; i++)
-      if (!b->scalars[i]) return fail(BGV_E_INVALID_ARG, "scalars[%u] is zero", i);
-  return BGV_OK;
-}
-
+// The front of bitfield sets is bits_front's (set-up, host plan, expansion), with
+// the expansion buffers as d_po / d_idx and the windows of a context with sums.
+// The expansion runs on st_pk in front of the gather, its only reader: the
+// signature decode on st and the hashes on st_hash start without it.
 static int smb_run(bgv_ctx* c, const bgv_smb_batch* b, uint8_t* set_valid, int32_t* set_code, bgv_sm_stats* stats,
                    uint8_t* pk_set96, uint8_t* path, uint8_t* p_group96, uint8_t* s_group192, uint8_t* h_group192) {
-  if (!c) return fail(BGV_E_INVALID_ARG, "null ctx");
-  if (int r = smb_check_args(b)) return r;
-  if (stats) memset(stats, 0, sizeof *stats);
-  const uint32_t n = b->n_sets, G = b->n_groups;
-  if (n == 0) return BGV_OK;
-  if (!set_valid) return fail(BGV_E_INVALID_ARG, "set_valid is NULL");
-  c->partial_pending = false;
-  HIPCHK(hipSetDevice(c->device));
-  active_guard ag(c->device);
-  const auto t0 = std::chrono::steady_clock::now();
+  sm_dev k;
+  if (int r = sm_open(c, b, set_valid, stats, k)) return r;
+  if (!k.n) return BGV_OK;
+  if (int r = sm_groups(c, k, b->group_offsets, b->on_device)) return r;
+  const uint32_t n = k.n, G = k.G, S = k.sg.S;
   const bool host = !b->on_device;
-  // the group offsets come to the host first: the segments are cut from this copy
-  std::vector<uint32_t> go((size_t)G + 1);
-  if (host) {
-    memcpy(go.data(), b->group_offsets, go.size() * 4);
-  } else {
-    HIPCHK(hipMemcpyAsync(go.data(), b->group_offsets, go.size() * 4, hipMemcpyDeviceToHost, c->st));
-    HIPCHK(hipStreamSynchronize(c->st));
-  }
-  if (int r = smb_check_groups(b, go.data())) return r;
 
   bits_args a;
   if (int r = bits_setup(c, a, n, b->bits_len, b->n_indices, !host, true, c->st_pk)) return r;
   c->bits_timed = false;
   a.src = (const bits_src*)b->src; a.v.bits = b->bits; a.v.pk_indices = b->pk_indices;
 
-  sma_dev k;
-  memset(&k, 0, sizeof k);
-  k.n = n; k.G = G; k.n_raw = b->n_raw;
-  k.d_len = b->sig_len; k.d_msgs = b->msgs; k.d_sigs = b->sigs; k.d_raw = b->raw_pks; k.d_scalars = b->scalars;
-  k.draw_scalars = !b->scalars;
-  sma_segs sg;
-  sma_cut_segments(go, n, sg);
-  const uint32_t S = sg.S;
-  k.S = S; k.sg = &sg;
   // staging: the segment tables always, the batch arrays of a host batch
   stage_seg segs[12] = {
-      {sg.seg_off.data(), ((size_t)S + 1) * 4, (const void**)&k.d_seg_off, 0},
-      {sg.seg_group.data(), (size_t)S * 4, (const void**)&k.d_seg_group, 0},
-      {sg.group_seg.data(), ((size_t)G + 1) * 4, (const void**)&k.d_group_seg, 0},
-      {sg.iota.data(), ((size_t)S + 1) * 4, (const void**)&k.d_iota, 0},
+      {k.sg.seg_off.data(), ((size_t)S + 1) * 4, (const void**)&k.d_seg_off, 0},
+      {k.sg.seg_group.data(), (size_t)S * 4, (const void**)&k.d_seg_group, 0},
+      {k.sg.group_seg.data(), ((size_t)G + 1) * 4, (const void**)&k.d_group_seg, 0},
+      {k.sg.iota.data(), ((size_t)S + 1) * 4, (const void**)&k.d_iota, 0},
       {b->src, (size_t)n * sizeof(bits_src), (const void**)&a.src, 0},
       {b->bits, (size_t)b->bits_len, (const void**)&a.v.bits, 0},
       {b->pk_indices, (size_t)b->n_indices * 4, (const void**)&a.v.pk_indices, 0},
@@ -2357,11 +2137,8 @@ static int smb_run(bgv_ctx* c, const bgv_smb_batch* b, uint8_t* set_valid, int32
     hv.pk_indices = (const uint32_t*)(c->pin_in + segs[6].off);
     bits_plan_out po;
     if (int r = bits_check_sources(n, (const bits_src*)(c->pin_in + segs[4].off), hv, &po, nullptr)) return r;
-    if (b->scalars) {
-      const uint64_t* sc = (const uint64_t*)(c->pin_in + segs[9].off);
-      for (uint32_t i = 0; i < n; i++)
-        if (!sc[i]) return fail(BGV_E_INVALID_ARG, "scalars[%u] is zero", i);
-    }
+    if (b->scalars)
+      if (int r = scalars_nonzero((const uint64_t*)(c->pin_in + segs[9].off), n)) return r;
     c->pk_total = po.total;
     c->bits_path.sets_complement = po.n_complement;
     c->bits_path.keys_expanded = po.total;
@@ -2379,13 +2156,14 @@ static int smb_run(bgv_ctx* c, const bgv_smb_batch* b, uint8_t* set_valid, int32
   }
   k.gathered = c->bits_path.keys_gathered;
   if (int r = ensure_or_release_lines(c, c->bits_idx, k.gathered ? k.gathered : 1)) return r;
+  k.agg = true;
   k.expand = &a;
   k.d_po = c->bits_off.p;
   k.d_idx = c->bits_idx.p;
   k.win = a.win;
   // as bits_layout: sum ceil(k_i / 32) + windows <= gathered / 32 + n + windows
   k.chunk_bound = k.gathered / PK_CHUNK + n + c->bits_extra_chunks;
-  if (int r = sma_back(c, k, t0, set_valid, set_code, stats, pk_set96, p_group96, s_group192, h_group192)) return r;
+  if (int r = sm_back(c, k, set_valid, set_code, stats, pk_set96, p_group96, s_group192, h_group192)) return r;
   if (path) {
     memset(path, 0, n);
     if (a.win) {
@@ -2398,17 +2176,37 @@ static int smb_run(bgv_ctx* c, const bgv_smb_batch* b, uint8_t* set_valid, int32
   return BGV_OK;
 }
 
+// run, then: these entries report bgv_sm_stats.hashes (hash_path_clear)
+static int sm_done(bgv_ctx* c, int r) {
+  hash_path_clear(c);
+  return r;
+}
+
+int bgv_verify_same_message(bgv_ctx* c, const bgv_sm_batch* b, uint8_t* set_valid, int32_t* set_code, bgv_sm_stats* stats) {
+  return sm_done(c, sm_run(c, b, set_valid, set_code, stats, nullptr, nullptr, nullptr));
+}
+
+int bgv_debug_same_message(bgv_ctx* c, const bgv_sm_batch* b, uint8_t* set_valid, int32_t* set_code, bgv_sm_stats* stats,
+                           uint8_t* p_group96, uint8_t* s_group192, uint8_t* h_group192) {
+  return sm_done(c, sm_run(c, b, set_valid, set_code, stats, p_group96, s_group192, h_group192));
+}
+
+int bgv_verify_same_message_agg(bgv_ctx* c, const bgv_sma_batch* b, uint8_t* set_valid, int32_t* set_code, bgv_sm_stats* stats) {
+  return sm_done(c, sma_run(c, b, set_valid, set_code, stats, nullptr, nullptr, nullptr, nullptr));
+}
+
+int bgv_debug_same_message_agg(bgv_ctx* c, const bgv_sma_batch* b, uint8_t* set_valid, int32_t* set_code, bgv_sm_stats* stats,
+                               uint8_t* pk_set96, uint8_t* p_group96, uint8_t* s_group192, uint8_t* h_group192) {
+  return sm_done(c, sma_run(c, b, set_valid, set_code, stats, pk_set96, p_group96, s_group192, h_group192));
+}
+
 int bgv_verify_same_message_bits(bgv_ctx* c, const bgv_smb_batch* b, uint8_t* set_valid, int32_t* set_code, bgv_sm_stats* stats) {
-  const int r_ = smb_run(c, b, set_valid, set_code, stats, nullptr, nullptr, nullptr, nullptr, nullptr);
-  hash_path_clear(c);  // these entries report bgv_sm_stats.hashes
-  return r_;
+  return sm_done(c, smb_run(c, b, set_valid, set_code, stats, nullptr, nullptr, nullptr, nullptr, nullptr));
 }
 
 int bgv_debug_same_message_bits(bgv_ctx* c, const bgv_smb_batch* b, uint8_t* set_valid, int32_t* set_code, bgv_sm_stats* stats,
                                 uint8_t* pk_set96, uint8_t* path, uint8_t* p_group96, uint8_t* s_group192, uint8_t* h_group192) {
-  const int r_ = smb_run(c, b, set_valid, set_code, stats, pk_set96, path, p_group96, s_group192, h_group192);
-  hash_path_clear(c);  // these entries report bgv_sm_stats.hashes
-  return r_;
+  return sm_done(c, smb_run(c, b, set_valid, set_code, stats, pk_set96, path, p_group96, s_group192, h_group192));
 }
 
 // ---- multi-GPU partials ---------------------------------------------------

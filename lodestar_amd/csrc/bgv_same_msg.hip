@@ -71,7 +71,11 @@ __device__ __forceinline__ static void shfl_down16(g1j& r, const g1j& p, uint32_
 //   2. d B_d by double-and-add;
 //   3. S_w = sum_d d B_d by a tree over the window's 16 lanes.
 // No bucket is indexed at run time: each lane owns exactly one.
-__global__ void BGV_SM_LB k_sm_g1_digit(sm_view v) {
+// The addend of set i: its table row, added by the mixed addition, or, for
+// aggregate sets (AGG), PK_i in Jacobian form from pk_set, added by the full
+// one (msm_g1.h msm_g1_bucket_add_jac).
+template <bool AGG>
+__device__ __forceinline__ static void sm_g1_digit(const sm_view& v) {
   const uint32_t t = sm_gtid();
   const uint32_t s = t >> 8, win = (t >> 4) & 15u, d = t & 15u;
   if (s >= v.n_segs) return;  // whole waves: 256 lanes per segment
@@ -86,8 +90,13 @@ __global__ void BGV_SM_LB k_sm_g1_digit(sm_view v) {
     }
     if (!__any(i < end)) break;
     if (i < end) {
-      g1a row;
-      if (sm_load_pk(row, v, v.pk_idx[i])) msm_g1_bucket_add(acc, row);  // in range: k_sm_classify skipped the others
+      if constexpr (AGG) {
+        const g1j pk = v.pk_set[i];  // finite: k_sma_classify skipped the others
+        msm_g1_bucket_add_jac(acc, pk);
+      } else {
+        g1a row;
+        if (sm_load_pk(row, v, v.pk_idx[i])) msm_g1_bucket_add(acc, row);  // in range: k_sm_classify skipped the others
+      }
       i++;
     }
   }
@@ -99,6 +108,8 @@ __global__ void BGV_SM_LB k_sm_g1_digit(sm_view v) {
   }
   if (d == 0) v.win[16u * s + win] = acc;
 }
+__global__ void BGV_SM_LB k_sm_g1_digit(sm_view v) { sm_g1_digit<false>(v); }
+__global__ void BGV_SM_LB k_sma_g1_digit(sm_view v) { sm_g1_digit<true>(v); }  // k_sm_g1_fold finishes the segment for both
 
 // lane = (segment, window): 16^w S_w, a tree over the segment's 16 lanes, then
 // lane 0 converts P_seg to affine and classifies the segment
@@ -158,25 +169,37 @@ __global__ void BGV_SM_LB k_sm_group_sums(sm_view v, const uint32_t* group_seg, 
 }
 
 // the per-set retry's batch: set list[k] as set k = job k with one key, its
-// group's message replicated
-__global__ void BGV_SM_LB k_sm_retry_gather(sm_retry r) {
+// group's message replicated.  Aggregate sets (AGG): the set's aggregated key
+// becomes row t of a raw-key table, o_pk[t] = PK_i affine, and the job's single
+// index is 0x80000000 | t.
+template <bool AGG>
+__device__ __forceinline__ static void sm_retry_gather(const sm_retry& r, const g1j* pk_set, g1a* o_pk) {
   const uint32_t t = sm_gtid();
   if (t > r.n) return;
   r.o_iota[t] = t;
   if (t == r.n) return;
   const uint32_t i = r.list[t], g = r.list_group[t];
-  r.o_idx[t] = r.pk_idx[i];
+  if constexpr (AGG) {
+    g1a a;
+    jac_to_aff(a, pk_set[i]);
+    o_pk[t] = a;
+    r.o_idx[t] = 0x80000000u | t;
+  } else {
+    r.o_idx[t] = r.pk_idx[i];
+  }
   r.o_len[t] = r.sig_len[i];
   r.o_scalars[t] = r.scalars[i];
   for (uint32_t k = 0; k < 32; k++) r.o_msgs[32u * t + k] = r.msgs[32u * g + k];
   for (uint32_t k = 0; k < 192; k++) r.o_sigs[192u * t + k] = r.sigs[192u * i + k];
 }
+__global__ void BGV_SM_LB k_sm_retry_gather(sm_retry r) { sm_retry_gather<false>(r, nullptr, nullptr); }
+__global__ void BGV_SM_LB k_sma_retry_gather(sm_retry r, const g1j* pk_set, g1a* o_pk) { sm_retry_gather<true>(r, pk_set, o_pk); }
 
 // ---- aggregate sets (bgv_verify_same_message_agg) ---------------------------
 // A set's key is PK_i = sum_j pk_{i,j}.  The balanced gather of the ordinary
 // pipeline (k_chunk_count / k_scan / k_chunk_set / k_pk_chunk) leaves one
-// partial sum per PK_CHUNK keys; the kernels below fold them per set and run
-// the weighted sum over the folded keys.
+// partial sum per PK_CHUNK keys; the kernels below fold them per set, and the
+// weighted sum (sm_g1_digit<true> above) runs over the folded keys.
 
 // lane = set: the fold of k_pk without its scalar multiplication and without
 // its inversion.  PK_i stays Jacobian; the key code is k_pk's: the range marker
@@ -214,39 +237,6 @@ __global__ void BGV_SM_LB k_sma_classify(sm_view v) {
   v.skip[i] = code != C_OK ? 1u : 0u;
 }
 
-// k_sm_g1_digit over the per-set keys: the addend is PK_i in Jacobian form,
-// read from pk_set, and the bucket addition the full one (msm_g1.h
-// msm_g1_bucket_add_jac).  Scaling and the 16-lane fold are k_sm_g1_digit's;
-// k_sm_g1_fold finishes the segment.
-__global__ void BGV_SM_LB k_sma_g1_digit(sm_view v) {
-  const uint32_t t = sm_gtid();
-  const uint32_t s = t >> 8, win = (t >> 4) & 15u, d = t & 15u;
-  if (s >= v.n_segs) return;  // whole waves: 256 lanes per segment
-  const uint32_t beg = v.seg_off[s], end = v.seg_off[s + 1];
-  g1j acc;
-  jac_set_inf(acc);
-  uint32_t i = beg;
-  for (;;) {
-    while (i < end) {
-      if (d != 0 && !v.skip[i] && msm_g1_digit(v.scalars[i], win) == d) break;
-      i++;
-    }
-    if (!__any(i < end)) break;
-    if (i < end) {
-      const g1j pk = v.pk_set[i];  // finite: k_sma_classify skipped the others
-      msm_g1_bucket_add_jac(acc, pk);
-      i++;
-    }
-  }
-  msm_g1_scale_digit(acc, d);
-  for (uint32_t st = 8; st >= 1; st >>= 1) {
-    g1j o;
-    shfl_down16(o, acc, st);
-    if (d < st) jac_add(acc, acc, o);
-  }
-  if (d == 0) v.win[16u * s + win] = acc;
-}
-
 // PK_i as an affine point (all-zero for a rejected key): bgv_debug_same_message_agg
 __global__ void BGV_SM_LB k_sma_pk_aff(const g1j* pk_set, g1a* out, uint32_t n) {
   const uint32_t i = sm_gtid();
@@ -254,25 +244,6 @@ __global__ void BGV_SM_LB k_sma_pk_aff(const g1j* pk_set, g1a* out, uint32_t n) 
   g1a a;
   jac_to_aff(a, pk_set[i]);
   out[i] = a;
-}
-
-// the per-set retry's batch, as k_sm_retry_gather builds it, with the set's
-// aggregated key as row t of a raw-key table: o_pk[t] = PK_i affine, and the
-// job's single index is 0x80000000 | t
-__global__ void BGV_SM_LB k_sma_retry_gather(sm_retry r, const g1j* pk_set, g1a* o_pk) {
-  const uint32_t t = sm_gtid();
-  if (t > r.n) return;
-  r.o_iota[t] = t;
-  if (t == r.n) return;
-  const uint32_t i = r.list[t], g = r.list_group[t];
-  g1a a;
-  jac_to_aff(a, pk_set[i]);
-  o_pk[t] = a;
-  r.o_idx[t] = 0x80000000u | t;
-  r.o_len[t] = r.sig_len[i];
-  r.o_scalars[t] = r.scalars[i];
-  for (uint32_t k = 0; k < 32; k++) r.o_msgs[32u * t + k] = r.msgs[32u * g + k];
-  for (uint32_t k = 0; k < 192; k++) r.o_sigs[192u * t + k] = r.sigs[192u * i + k];
 }
 
 static inline dim3 sm_grid(uint32_t n) { return dim3((n + 63u) / 64u); }

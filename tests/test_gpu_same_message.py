@@ -293,6 +293,23 @@ def test_library_drawn_scalars(dev, layout):
     assert (verdicts[0] == verdicts[1]).all()
 
 
+def test_on_device_batch(dev, layout):
+    """inputs resident in HBM: the verdicts of the host batch, one wrong signature included"""
+    import torch
+    import bench
+    L = layout
+    bad = int(L["off"][6]) + 77  # in the group of 300
+    sigs = L["sigs"].copy()
+    sigs[bad] = L["sigs"][bad - 1]  # its neighbour's: a valid signature of another validator
+    assert L["idx"][bad] != L["idx"][bad - 1]
+    a = sm_arrays(L, sigs=sigs)
+    ok_host, code_host = dev.verify_same_message(a)
+    da = bench.to_device(a, torch, torch.device("cuda", 0))
+    ok, code = dev.verify_same_message(da, on_device=True)
+    assert np.nonzero(~ok)[0].tolist() == [bad]
+    assert (ok == ok_host).all() and (code == code_host).all()
+
+
 def test_empty_batch(dev):
     arrays = {"n_sets": 0, "n_groups": 0, "group_offsets": np.array([0], np.uint32), "pk_indices": np.zeros(1, np.uint32),
               "msgs": np.zeros((1, 32), np.uint8), "sigs": np.zeros((1, 192), np.uint8), "sig_len": np.zeros(1, np.uint32)}

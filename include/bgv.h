@@ -176,6 +176,13 @@ typedef struct bgv_cfg {
                            on N reserved CUs (the highest CU ids: with N = 8k, k CUs of every XCC), for
                            verifyOnMainThread single sets (multithread/index.ts:155-167) that must not wait for a
                            bulk batch's waves; N < 0: a bulk context whose streams leave those |N| CUs free (ABI 4) */
+  int32_t miller_steps; /* -1 auto; 0 off; 1 on: the one-lane Miller stage over fixed-argument lines (split = 0, lines = 1)
+                           as per-step line products: lanes (slice of a job's sets, line step) multiply the slice's 68
+                           evaluated lines without any squaring, and one workgroup per job runs the squaring chain
+                           once over the step products (bgv_miller_path_stats).  Auto turns
+                           it on where the layout itself chose two pairs per item over lines (bgv_cfg.pairs and
+                           bgv_cfg.lines left at auto); an explicit pairs keeps the item loop.  Results never depend
+                           on it.  (hash_dedup stays the last field.) */
   int32_t hash_dedup;   /* -1 auto; 0 off; 1 on: a bulk-layout batch evaluates hash_to_G2 once per distinct signing
                            root and copies H(m) to the other sets that carry it (bgv_hash_stats).  Auto is OFF:
                            with every root distinct the grouping costs 2.3 ms per 100,352-set batch when three
@@ -563,6 +570,18 @@ typedef struct bgv_hash_path {
   uint32_t sets, hashes, dedup;
 } bgv_hash_path;
 int bgv_hash_stats(bgv_ctx* ctx, bgv_hash_path* out);
+/* The Miller stage of the last batch whose layout the context chose (bgv_verify,
+ * bgv_verify_bits, bgv_partial, bgv_debug_stages): steps = 1 when it ran as
+ * per-step line products (bgv_cfg.miller_steps), slice_sets the sets of a job
+ * one lane multiplies per step (else the pairs per work item of the one-lane
+ * loop, 0 for the multi-lane layouts), items the work items of the batch
+ * (slices, or one-lane loop items; 0 for the multi-lane layouts).
+ * bgv_stats.pairs_per_item keeps reporting the configured pairs on the steps
+ * path.  Host-side values: no device call. */
+typedef struct bgv_miller_path {
+  uint32_t steps, slice_sets, items;
+} bgv_miller_path;
+int bgv_miller_path_stats(bgv_ctx* ctx, bgv_miller_path* out);
 /* Host-only plan (no device, no context): bgv_bits_check's checks, then the
  * rule against list_has_sums[BGV_MAX_INDEX_LISTS] (NULL: no list has sums).
  * path[i] = 1 for a complement set (path may be NULL); *keys_gathered the keys

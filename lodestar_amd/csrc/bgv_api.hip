@@ -123,6 +123,8 @@ struct bgv_ctx {
   dbuf<uint32_t> sig_grp;
   dbuf<fp2_t> lines;
   uint32_t lines_idle = 0;  // batches in a row that did not use the line buffer
+  dbuf<fp12_t> f_step;      // per (slice, step) line products (dev_batch.steps_slice); kept and released with lines
+  bgv_miller_path miller_path = {};  // bgv_miller_path_stats (prepare_layout)
   dbuf<fp12_t> f_set, f_job, f_batch, f_tmp, f_part;
   dbuf<uint32_t> set_job, s_inf, item_off, item_job;
   dbuf<g2a> s_aff;
@@ -205,7 +207,7 @@ void bgv_cfg_default(bgv_cfg* cfg) {
   memset(cfg, 0, sizeof *cfg);
   cfg->struct_size = sizeof *cfg;
   cfg->split = cfg->miller = cfg->msm = cfg->prefold = cfg->lines = cfg->defer_pct = cfg->timing = cfg->clear_lanes = -1;
-  cfg->miller_kv = cfg->hash_dedup = -1;
+  cfg->miller_kv = cfg->hash_dedup = cfg->miller_steps = -1;
   cfg->job_lanes = cfg->pairs = cfg->cu_split = 0;
 }
 
@@ -235,6 +237,7 @@ int bgv_open_cfg(int device, const bgv_cfg* cfg, bgv_ctx** out) {
     if (!tri_ok(k.lines)) return fail(BGV_E_INVALID_ARG, "bgv_cfg.lines %d", k.lines);
     if (!tri_ok(k.timing)) return fail(BGV_E_INVALID_ARG, "bgv_cfg.timing %d", k.timing);
     if (!tri_ok(k.hash_dedup)) return fail(BGV_E_INVALID_ARG, "bgv_cfg.hash_dedup %d", k.hash_dedup);
+    if (!tri_ok(k.miller_steps)) return fail(BGV_E_INVALID_ARG, "bgv_cfg.miller_steps %d", k.miller_steps);
     if (k.cu_split < -64 || k.cu_split > 64) return fail(BGV_E_INVALID_ARG, "bgv_cfg.cu_split %d (|N| <= 64 CUs)", k.cu_split);
     // two pairs per item exist only in the one-lane loop
     if (k.pairs >= 2 && k.miller != -1 && k.miller != 1)
@@ -346,7 +349,7 @@ int bgv_close(bgv_ctx* c) {
   c->scalars.release(); c->raw_conv.release();
   c->sig_aff.release(); c->h_aff.release(); c->sig_inf.release(); c->flags.release();
   c->sig_code.release(); c->pk_code.release(); c->job_code.release(); c->job_result.release(); c->set_code.release();
-  c->rpk_aff.release(); c->chunk_off.release(); c->chunk_set.release(); c->pk_part.release(); c->rsig.release(); c->q_part.release(); c->sig_grp.release(); c->lines.release(); c->f_set.release(); c->f_job.release(); c->f_batch.release(); c->f_tmp.release(); c->f_part.release();
+  c->rpk_aff.release(); c->chunk_off.release(); c->chunk_set.release(); c->pk_part.release(); c->rsig.release(); c->q_part.release(); c->sig_grp.release(); c->lines.release(); c->f_step.release(); c->f_set.release(); c->f_job.release(); c->f_batch.release(); c->f_tmp.release(); c->f_part.release();
   c->msm_bucket.release(); c->msm_win.release(); c->msm_mask.release();
   c->set_job.release(); c->s_inf.release(); c->item_off.release(); c->item_job.release(); c->s_aff.release();
   c->sm_skip.release(); c->sm_list.release(); c->sm_zero.release(); c->sm_seg_code.release(); c->sm_win.release();
@@ -488,6 +491,7 @@ static int ensure_or_release_lines(bgv_ctx* c, dbuf<T>& b, size_t n) {
   int r = b.ensure(n);
   if (r && c->lines.cap && (const void*)&b != (const void*)&c->lines) {
     c->lines.release();
+    if ((const void*)&b != (const void*)&c->f_step) c->f_step.release();
     c->lines_idle = 0;
     r = b.ensure(n);
   }
@@ -685,6 +689,13 @@ static int prepare(bgv_ctx* c, const bgv_batch* b, dev_batch& d, bool need_sigs)
 // batch whose device view (arrays, n_sets, span_log2) and key total
 // (c->pk_total) are set, and its scalars.  scalars_staged: d.scalars already
 // points at the staged copy of a host batch.
+// sets of a job per lane of k_miller_steps (dev_batch.steps_slice); a
+// compile-time knob for A/B builds (DESIGN.md section 3 r07 has the sweep)
+#ifndef BGV_STEPS_SLICE
+#define BGV_STEPS_SLICE 49
+#endif
+static const uint32_t STEPS_SLICE = BGV_STEPS_SLICE;
+
 static int prepare_layout(bgv_ctx* c, dev_batch& d, const uint64_t* scalars, bool scalars_staged) {
   const uint32_t n = d.n_sets;
   const uint32_t total = c->pk_total;
@@ -822,6 +833,30 @@ static int prepare_layout(bgv_ctx* c, dev_batch& d, const uint64_t* scalars, boo
   }
   // four pairs per item exist only over precomputed lines (miller_loop_lines4)
   if (d.pairs_per_item == 4 && !d.lines) d.pairs_per_item = 2;
+  // per-step line products (pairing.h miller_step_lines, bgv_tail.hip
+  // k_job_chain) in place of the item loop: only over the one-lane layout with
+  // lines.  Auto: where the layout itself chose two pairs per item over lines
+  // (pairs and lines left at auto); an explicit pairs keeps the item loop.
+  // f_step takes 576 B x 68 per slice (39 KB; 120 MB at C4 with 49-set slices):
+  // like the lines, only while a quarter of the free HBM covers it.
+  {
+    const bool can = !d.split && !d.miller_coop && !d.miller_kv && d.lines;
+    // (block-sized jobs only, as the MSM: k_job_chain joins a job's slices one after the other)
+    const bool want = k.miller_steps >= 0 ? k.miller_steps != 0 : (k.pairs == 0 && d.pairs_per_item >= 2 && d.span_log2 <= 8);
+    d.steps_slice = can && want ? STEPS_SLICE : 0u;
+    if (d.steps_slice) {
+      const size_t need = (size_t)miller_items_bound(d, d.steps_slice) * MILLER_STEPS * sizeof(fp12_t);
+      size_t free_b = 0, total_b = 0;
+      if (need > c->f_step.cap * sizeof(fp12_t) && (hipMemGetInfo(&free_b, &total_b) != hipSuccess || need > free_b / 4))
+        d.steps_slice = 0;
+    }
+    // what bgv_miller_path_stats reports: host values only (the job offsets are home since prepare())
+    const uint32_t per = d.steps_slice ? d.steps_slice : (d.miller_coop && !d.miller_kv ? 0u : d.pairs_per_item);
+    uint32_t items = 0;
+    if (per && c->jo_host.size() == (size_t)d.n_jobs + 1)
+      for (uint32_t j = 0; j < d.n_jobs; j++) items += miller_item_count(c->jo_host[j + 1] - c->jo_host[j], per);
+    c->miller_path = {d.steps_slice ? 1u : 0u, per, items};
+  }
   return 0;
 }
 
@@ -847,6 +882,7 @@ static int work_alloc(bgv_ctx* c, const dev_batch& d, dev_work& w) {
   int r = work_alloc_once(c, d, w);
   if (r && !d.lines && c->lines.cap) {
     c->lines.release();
+    c->f_step.release();
     c->lines_idle = 0;
     r = work_alloc_once(c, d, w);
   }
@@ -892,9 +928,16 @@ static int work_alloc_once(bgv_ctx* c, const dev_batch& d, dev_work& w) {
     c->lines_idle = 0;
     if ((r = c->lines.ensure((size_t)3 * MILLER_STEPS * ns))) return r;
     w.lines = c->lines.p;
-  } else if (c->lines.cap && ++c->lines_idle >= LINES_KEEP) {
+  } else if ((c->lines.cap || c->f_step.cap) && ++c->lines_idle >= LINES_KEEP) {
     c->lines.release();
+    c->f_step.release();
     c->lines_idle = 0;
+  }
+  // the step products live and die with the lines (steps_slice implies lines)
+  w.f_step = nullptr;
+  if (d.steps_slice) {
+    if ((r = c->f_step.ensure((size_t)miller_items_bound(d, d.steps_slice) * MILLER_STEPS))) return r;
+    w.f_step = c->f_step.p;
   }
   // message classes (bgv_dedup.hip): sized with the batch's other buffers, never inside a run
   c->mc = {};
@@ -1525,6 +1568,12 @@ int bgv_hash_stats(bgv_ctx* c, bgv_hash_path* out) {
     c->hash_pending = false;
   }
   *out = c->hash_path;
+  return BGV_OK;
+}
+
+int bgv_miller_path_stats(bgv_ctx* c, bgv_miller_path* out) {
+  if (!c || !out) return fail(BGV_E_INVALID_ARG, "null argument");
+  *out = c->miller_path;
   return BGV_OK;
 }
 
@@ -2319,6 +2368,9 @@ int bgv_debug_stages(bgv_ctx* c, const bgv_batch* b, int32_t* job_result, int32_
   const uint32_t n = d.n_sets, J = d.n_jobs;
   if (int r = c->pk_agg.ensure(n ? n : 1)) return r;
   w.pk_agg = c->pk_agg.p;
+  // the steps path has no per-item Miller value: k_job_chain leaves the job's
+  // set product at its first set (1 at the others), copied after the tree stage
+  d.steps_dbg = d.steps_slice ? 1u : 0u;
   // the Miller values are copied before the product tree, which folds groups
   // of them in place (k_job_prefold, k_f_level); deferred subgroup verdicts
   // are applied first (idempotent: the tree stage applies them again)
@@ -2327,6 +2379,7 @@ int bgv_debug_stages(bgv_ctx* c, const bgv_batch* b, int32_t* job_result, int32_
   if (int r = c->dbg_f.ensure((size_t)n + J + 1)) return r;
   if (n + J) HIPCHK(hipMemcpyAsync(c->dbg_f.p, w.f_set, (size_t)(n + J) * sizeof(fp12_t), hipMemcpyDeviceToDevice, c->st));
   if (int r = run_stages(c, d, w, ST_F_TREE, ST_COUNT)) return r;
+  if (d.steps_dbg && n) HIPCHK(hipMemcpyAsync(c->dbg_f.p, w.f_set, (size_t)n * sizeof(fp12_t), hipMemcpyDeviceToDevice, c->st));
   // final exponentiations of every Miller value, job product and the batch product
   const uint32_t n_fe = n + 2 * J + 1;
   if (int r = c->dbg_fe.ensure(n_fe)) return r;

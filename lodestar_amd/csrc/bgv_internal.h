@@ -46,6 +46,11 @@ struct dev_batch {
   uint32_t defer_from;      // defer_grp: sets below it are checked in ST_SIG as usual, the rest later (multiple of 64)
   uint32_t defer_grp;       // bulk mode: ST_SIG only decodes; the G2 subgroup check runs beside the Miller loops
                             // (launch_sig_check) and its verdicts reach the job codes before the fold (launch_sig_fixup)
+  uint32_t steps_slice;     // >0: per-step line products (pairing.h miller_step_lines): the work items are slices of at
+                            // most steps_slice sets of a job, k_miller_steps writes f_step and k_job_chain runs the
+                            // job recurrence (bgv_cfg.miller_steps); 0: the item loop (k_miller)
+  uint32_t steps_dbg;       // bgv_debug_stages on the steps path: k_job_chain also leaves the job's set product at
+                            // f_set[first set] and 1 at its other sets
   const uint32_t* job_off;
   const uint32_t* pk_off;
   const uint32_t* pk_idx;
@@ -86,6 +91,7 @@ struct dev_work {
   g2a* s_aff;         // per job: sum [r_i] sigma_i, affine
   uint32_t* s_inf;
   fp2_t* lines;       // [68 steps][3][n_sets] unevaluated Miller lines of H(m_i) (dev_batch.lines)
+  fp12_t* f_step;     // [items][68] per (slice, step) line products (dev_batch.steps_slice)
   fp12_t* f_set;      // per pair Miller value: n_sets set pairs, then n_jobs (-G1, S_job) pairs
   fp12_t* f_job;      // per-job Miller product (incl. the -G1 pair)
   fp12_t* f_batch;    // batch product scratch [n_jobs]; the product ends in f_batch[0]
@@ -145,6 +151,9 @@ void launch_prep(hipStream_t st, const dev_batch& b, const dev_work& w);  // bef
 void launch_stage(hipStream_t st, int stage, const dev_batch& b, const dev_work& w);
 void launch_miller(hipStream_t st, const dev_batch& b, const dev_work& w);  // bgv_miller.hip
 void launch_lines(hipStream_t st, const dev_batch& b, const dev_work& w);   // bgv_miller.hip
+void launch_miller_steps(hipStream_t st, const dev_batch& b, const dev_work& w);  // bgv_miller.hip
+// upper bound of the work items of a batch taken `per` sets at a time: sum ceil(k_j / per) <= n_sets / per + n_jobs
+inline uint32_t miller_items_bound(const dev_batch& b, uint32_t per) { return b.n_sets / per + b.n_jobs; }
 void launch_miller_duo(hipStream_t st, const dev_batch& b, const dev_work& w);  // bgv_miller.hip
 void launch_miller_quad(hipStream_t st, const dev_batch& b, const dev_work& w);  // bgv_miller.hip
 void launch_sig_check(hipStream_t st, const dev_batch& b, const dev_work& w);   // subgroup checks only (sig_grp)

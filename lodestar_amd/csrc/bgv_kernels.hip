@@ -831,7 +831,8 @@ __global__ void BGV_BULK k_item_count(dev_batch b, dev_work w) {
   const uint32_t j = gtid();
   if (j >= b.n_jobs) return;
   const uint32_t lo = b.job_off[j], hi = b.job_off[j + 1];
-  w.item_off[j] = hi > lo ? (hi - lo + b.pairs_per_item - 1) / b.pairs_per_item : 0u;
+  // the steps path takes a job's sets in slices of steps_slice (k_miller_steps)
+  w.item_off[j] = hi > lo ? miller_item_count(hi - lo, b.steps_slice ? b.steps_slice : b.pairs_per_item) : 0u;
 }
 
 __global__ void BGV_BULK k_item_job(dev_batch b, dev_work w) {
@@ -1311,7 +1312,8 @@ void launch_stage(hipStream_t st, int stage, const dev_batch& b, const dev_work&
           launch_miller_coop(st, b.miller_coop, b, w, 0u, b.n_sets);
         break;
       }
-      launch_miller(st, b, w);  // bgv_miller.hip
+      if (b.steps_slice) launch_miller_steps(st, b, w);  // bgv_miller.hip
+      else launch_miller(st, b, w);  // bgv_miller.hip
       break;
     case ST_MILLER_JOBS:  // (-G1, S_job) pairs: needs ST_S_TREE
       // always the cooperative loop: one pair per job is latency-bound (a lone

@@ -263,6 +263,32 @@ void launch_lines(hipStream_t st, const dev_batch& b, const dev_work& w) {
   if (b.n_sets) hipLaunchKernelGGL(k_lines, dim3((b.n_sets + 63u) / 64u), dim3(64), 0, st, b, w);
 }
 
+// Per-step line products (pairing.h miller_step_lines): lane = (slice of at
+// most steps_slice consecutive sets of one job, line step blockIdx.y).  The
+// slices are the work items of the scan (k_item_count with steps_slice); the
+// lane multiplies the slice's evaluated lines of its step into one Fp12 and
+// leaves it at f_step[item][step] for k_job_chain (bgv_tail.hip).  No
+// squaring, no dependence between steps: 68 x items short lanes, the step
+// uniform over the wave.  Same code generation as k_miller: register-ABI Fp
+// product, accumulator in LDS, one wave per SIMD.
+__global__ void __launch_bounds__(64, BGV_MILLER_WAVES) k_miller_steps(dev_batch b, dev_work w) {
+  const uint32_t n_items = w.item_off[b.n_jobs];
+  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x, s = blockIdx.y;
+  if (t >= n_items) return;
+  __shared__ fp12_t f_lds[64];
+  fp12_t& f = f_lds[threadIdx.x];
+  const uint32_t j = w.item_job[t];
+  uint32_t i0, cnt;
+  miller_item_sets(i0, cnt, b.job_off[j], b.job_off[j + 1], t - w.item_off[j], b.steps_slice);
+  miller_step_lines(f, w.lines, b.n_sets, w.rpk_aff, w.pk_code, i0, cnt, s, miller_step_is_add(s));
+  w.f_step[(size_t)t * MILLER_STEPS + s] = f;
+}
+
+void launch_miller_steps(hipStream_t st, const dev_batch& b, const dev_work& w) {
+  const uint32_t n = miller_items_bound(b, b.steps_slice);  // >= items (launch_prep); f_step holds n x 68 values
+  if (n && b.n_sets) hipLaunchKernelGGL(k_miller_steps, dim3((n + 63u) / 64u, MILLER_STEPS), dim3(64), 0, st, b, w);
+}
+
 void launch_miller(hipStream_t st, const dev_batch& b, const dev_work& w) {
   const uint32_t n = b.n_sets / b.pairs_per_item + b.n_jobs;  // >= items (launch_prep)
   if (n) hipLaunchKernelGGL(k_miller, dim3((n + 63u) / 64u), dim3(64), 0, st, b, w, 0u);

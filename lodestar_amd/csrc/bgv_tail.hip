@@ -105,6 +105,68 @@ __global__ void COOP_LB k_job_fold(dev_batch b, dev_work w, uint32_t stride) {
   c_store(w.f_batch[j], &acc);
 }
 
+// The steps path (dev_batch.steps_slice, pairing.h): one workgroup per job
+// runs the job's Miller recurrence ONCE over the per-step line products that
+// k_miller_steps left in f_step: L_k = the product of the job's slice values
+// at step k, f <- f^2 L_k on doubling steps, f <- f L_k on addition steps,
+// the conjugation (x < 0), then the job's (-G1, S_job) value.  It stands in
+// for k_job_prefold / k_job_fold; rejected jobs give 1 as there.
+// steps_dbg (bgv_debug_stages): the set product goes to f_set[first set] and 1
+// to the job's other sets, 1 to all of them when a pubkey of the job was
+// rejected: the item rule of k_miller with the job as the item.
+__global__ void COOP_LB k_job_chain(dev_batch b, dev_work w) {
+  __shared__ cscratch s;
+  __shared__ wfp12 acc, x, y;
+  __shared__ uint32_t bad_pk;
+  const uint32_t j = blockIdx.x;
+  const uint32_t beg = b.job_off[j], end = b.job_off[j + 1];
+  const uint32_t t0 = w.item_off[j], t1 = w.item_off[j + 1];
+  const bool rejected = w.job_code[j] != C_OK;
+  bool run = !rejected && t1 > t0;  // uniform per workgroup, as everything below
+  if (b.steps_dbg) {
+    if (threadIdx.x == 0) bad_pk = 0u;
+    __syncthreads();
+    if (miller_job_rejected_pk(w.pk_code, beg, end, threadIdx.x, COOP_THREADS)) bad_pk = 1u;
+    __syncthreads();
+    run = t1 > t0 && !bad_pk;
+  }
+  if (!run) {
+    c_set_one(&acc);
+  } else {
+    uint32_t k = 0;
+    for (int bit = 62; bit >= 0; bit--) {
+      const int sub = ((BLS_X_ABS >> bit) & 1ull) ? 2 : 1;
+      for (int a = 0; a < sub; a++, k++) {
+        c_load(&x, w.f_step[(size_t)t0 * MILLER_STEPS + k]);
+        for (uint32_t t = t0 + 1; t < t1; t++) {
+          c_load(&y, w.f_step[(size_t)t * MILLER_STEPS + k]);
+          c_mul(&x, &x, &y, &s);
+        }
+        if (k == 0) {
+          c_copy(&acc, &x);
+        } else {
+          if (a == 0) c_mul(&acc, &acc, &acc, &s);
+          c_mul(&acc, &acc, &x, &s);
+        }
+      }
+    }
+    c_conj(&acc, &acc);
+  }
+  if (b.steps_dbg && end > beg) {
+    c_store(w.f_set[beg], &acc);
+    c_set_one(&y);
+    for (uint32_t i = beg + 1; i < end; i++) c_store(w.f_set[i], &y);
+  }
+  if (rejected) {
+    c_set_one(&acc);  // rejected jobs take no part in the batch product
+  } else {
+    c_load(&x, w.f_set[b.n_sets + j]);
+    c_mul(&acc, &acc, &x, &s);
+  }
+  c_store(w.f_job[j], &acc);
+  c_store(w.f_batch[j], &acc);
+}
+
 // workgroup g: dst[g] = prod src[F g .. min(n, F g + F)) with fan-in F; with
 // one workgroup dst may alias src (every read precedes the write).  A
 // fan-in of 8 keeps the chain of sequential Fp12 products short: 1,024 job
@@ -183,6 +245,10 @@ void launch_fp12_tail(hipStream_t st, int stage, const dev_batch& b, const dev_w
   const dim3 ct(COOP_THREADS);
   if (stage == ST_F_TREE) {
     if (!b.n_jobs) return;
+    if (b.steps_slice) {  // per-step line products: the job's recurrence over them
+      hipLaunchKernelGGL(k_job_chain, dim3(b.n_jobs), ct, 0, st, b, w);
+      return;
+    }
     if (span <= 256) {  // every job folds in one workgroup
       uint32_t stride = b.pairs_per_item ? b.pairs_per_item : 1u;  // fold_step
       if (b.prefold_log2) {  // few large jobs: fold groups side by side first

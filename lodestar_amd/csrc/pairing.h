@@ -313,6 +313,43 @@ BGV_NIL void miller_loop_lines(fp12_t& f, const fp2_t* lines, uint32_t stride, c
   fp12_conj(f, f);  // x < 0
 }
 
+// ---- per-step line products (bgv_cfg.miller_steps) --------------------------
+// A job's Miller value is f <- f^2 prod_p l_{k,p} over its sets p, and Fp12 is
+// commutative, so the squarings need not be paid per work item: L_k = prod_p
+// l_{k,p}(P_p) for each of the 68 line steps k needs none (miller_step_lines,
+// one lane per (slice of a job's sets, step)), and the job runs the recurrence
+// ONCE over L_0 .. L_67 (miller_chain; on the device k_job_chain, bgv_tail.hip).
+// Every factor is exact, so the value is the same element of Fp12 as the
+// product of the job's miller_loop_lines items.
+
+// work items of a job of `sets` sets taken `per` at a time (0 for an empty job)
+BGV_HD uint32_t miller_item_count(uint32_t sets, uint32_t per) { return (sets + per - 1u) / per; }
+// item k of the job [beg, end): its first set and its live sets (1 .. per)
+BGV_HD void miller_item_sets(uint32_t& i0, uint32_t& cnt, uint32_t beg, uint32_t end, uint32_t k, uint32_t per) {
+  i0 = beg + per * k;
+  cnt = end - i0 < per ? end - i0 : per;
+}
+
+// a pubkey among sets beg + first, beg + first + stride, ... of the job [beg, end)
+// was rejected (k_job_chain: one strided share per thread).  Such a job has no
+// set product to report: bgv_debug_stages shows 1 at its first set.
+BGV_HD bool miller_job_rejected_pk(const int32_t* pk_code, uint32_t beg, uint32_t end, uint32_t first, uint32_t stride) {
+  bool bad = false;
+  for (uint32_t i = beg + first; i < end; i += stride) bad |= pk_code[i] != C_OK;
+  return bad;
+}
+
+// step s (0 .. MILLER_STEPS - 1) of the loop is an addition step
+BGV_HD bool miller_step_is_add(uint32_t s) {
+  uint32_t k = 0;
+  for (int b = 62; b >= 0; b--) {
+    if (k++ == s) return false;
+    if ((BLS_X_ABS >> b) & 1ull)
+      if (k++ == s) return true;
+  }
+  return false;
+}
+
 // a line forced to 1 (a0 = 1, a1 = b1 = 0) where `live` is false: the dummy
 // pairs of an item with fewer than four sets leave f unchanged, and every lane
 // issues the same products (no divergent tail for a job's last item)
@@ -354,6 +391,56 @@ BGV_NIL void miller_loop_lines4(fp12_t& f, const fp2_t* lines, uint32_t stride, 
       fp12_mul_line2(f, f, a0, a1, b1, c0, c1, d1);
       s++;
     }
+  }
+  fp12_conj(f, f);  // x < 0
+}
+
+// f = prod of the lines of sets [i0, i0 + cnt) (cnt >= 1) at step s, each
+// evaluated at its set's P[i]: the first line initialises f as the loops above
+// do, the others enter two at a time (fp12_mul_line2), an odd one alone.  A
+// set whose pubkey was rejected contributes 1 (its job is rejected anyway).
+BGV_NIL void miller_step_lines(fp12_t& f, const fp2_t* lines, uint32_t stride, const g1a* P, const int32_t* pk_code,
+                               uint32_t i0, uint32_t cnt, uint32_t s, bool add) {
+  fp2_t a0, a1, b1, c0, c1, d1;
+  {
+    const g1a p = P[i0];
+    miller_line_at_p(a0, a1, b1, lines, stride, i0, s, add, p.x, p.y);
+    miller_line_keep(a0, a1, b1, pk_code[i0] == C_OK);
+  }
+  fp12_one(f);
+  f.c0.c0 = a0;
+  f.c0.c1 = a1;
+  f.c1.c1 = b1;
+  uint32_t k = 1;
+  for (; k + 1 < cnt; k += 2) {
+    const g1a p = P[i0 + k], q = P[i0 + k + 1];
+    miller_line_at_p(a0, a1, b1, lines, stride, i0 + k, s, add, p.x, p.y);
+    miller_line_keep(a0, a1, b1, pk_code[i0 + k] == C_OK);
+    miller_line_at_p(c0, c1, d1, lines, stride, i0 + k + 1, s, add, q.x, q.y);
+    miller_line_keep(c0, c1, d1, pk_code[i0 + k + 1] == C_OK);
+    fp12_mul_line2(f, f, a0, a1, b1, c0, c1, d1);
+  }
+  if (k < cnt) {
+    const g1a p = P[i0 + k];
+    miller_line_at_p(a0, a1, b1, lines, stride, i0 + k, s, add, p.x, p.y);
+    miller_line_keep(a0, a1, b1, pk_code[i0 + k] == C_OK);
+    fp12_mul_line(f, f, a0, a1, b1);
+  }
+}
+
+// the job recurrence over its step products L[0 .. MILLER_STEPS): f <- f^2 L_k
+// on doubling steps, f <- f L_k on addition steps, conjugated at the end
+// (host restatement of k_job_chain for the op counts and the host check)
+BGV_NI void miller_chain(fp12_t& f, const fp12_t* L) {
+  uint32_t s = 0;
+  for (int b = 62; b >= 0; b--) {
+    if (b == 62) {
+      f = L[s++];
+    } else {
+      fp12_sqr(f, f);
+      fp12_mul(f, f, L[s++]);
+    }
+    if ((BLS_X_ABS >> b) & 1ull) fp12_mul(f, f, L[s++]);
   }
   fp12_conj(f, f);  // x < 0
 }

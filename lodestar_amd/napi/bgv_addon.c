@@ -182,8 +182,9 @@ static napi_value Open(napi_env env, napi_callback_info info) {
         NAPI_CALL(env, napi_get_value_int32(env, val, &x));
         if (!strcmp(name, "split")) cfg.split = x;
         else if (!strcmp(name, "hashDedup")) cfg.hash_dedup = x;
+        else if (!strcmp(name, "millerSteps")) cfg.miller_steps = x;
         else {
-          napi_throw_type_error(env, NULL, "open: cfg takes split and hashDedup");
+          napi_throw_type_error(env, NULL, "open: cfg takes split, hashDedup and millerSteps");
           return NULL;
         }
       }

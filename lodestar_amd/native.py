@@ -58,7 +58,7 @@ EXPORTS = [
     "bgv_index_list_sums", "bgv_index_list_has_sums", "bgv_bits_path_stats", "bgv_bits_plan", "bgv_debug_bits_keys",
     "bgv_debug_index_list_sums", "bgv_index_list_sums_ms",
     "bgv_verify_same_message_bits", "bgv_smb_check", "bgv_debug_same_message_bits",
-    "bgv_hash_stats",
+    "bgv_hash_stats", "bgv_miller_path_stats",
 ]
 MAX_INDEX_LISTS = 8
 SRC_EXPLICIT = 0xFFFFFFFF
@@ -223,9 +223,10 @@ class BgvCfg(ctypes.Structure):
     _fields_ = [("struct_size", ctypes.c_uint32)] + [
         (k, ctypes.c_int32) for k in
         ("split", "miller", "job_lanes", "msm", "pairs", "prefold", "lines", "defer_pct", "timing", "clear_lanes",
-         "miller_kv", "cu_split", "hash_dedup")]
+         "miller_kv", "cu_split", "miller_steps", "hash_dedup")]
     AUTO = {"split": -1, "miller": -1, "job_lanes": 0, "msm": -1, "pairs": 0, "prefold": -1, "lines": -1,
-            "defer_pct": -1, "timing": -1, "clear_lanes": -1, "miller_kv": -1, "cu_split": 0, "hash_dedup": -1}
+            "defer_pct": -1, "timing": -1, "clear_lanes": -1, "miller_kv": -1, "cu_split": 0, "miller_steps": -1,
+            "hash_dedup": -1}
 
     @classmethod
     def make(cls, **over) -> "BgvCfg":
@@ -266,6 +267,14 @@ class BgvBitsPath(ctypes.Structure):
 class BgvHashPath(ctypes.Structure):
     """bgv_hash_path (include/bgv.h): hash_to_G2 evaluations of the last ordinary batch"""
     _fields_ = [("sets", ctypes.c_uint32), ("hashes", ctypes.c_uint32), ("dedup", ctypes.c_uint32)]
+
+    def as_dict(self) -> dict:
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+class BgvMillerPath(ctypes.Structure):
+    """bgv_miller_path (include/bgv.h): how the Miller stage of the last batch ran"""
+    _fields_ = [("steps", ctypes.c_uint32), ("slice_sets", ctypes.c_uint32), ("items", ctypes.c_uint32)]
 
     def as_dict(self) -> dict:
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
@@ -371,6 +380,7 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
             "bgv_index_list_sums_ms": ([P, ctypes.POINTER(ctypes.c_float)], ctypes.c_int),
             "bgv_bits_path_stats": ([P, ctypes.POINTER(BgvBitsPath)], ctypes.c_int),
             "bgv_hash_stats": ([P, ctypes.POINTER(BgvHashPath)], ctypes.c_int),
+            "bgv_miller_path_stats": ([P, ctypes.POINTER(BgvMillerPath)], ctypes.c_int),
             "bgv_bits_plan": ([ctypes.POINTER(BgvBitsBatch), P, P, P, ctypes.POINTER(ctypes.c_uint64)], ctypes.c_int),
             "bgv_debug_bits_keys": ([P, ctypes.POINTER(BgvBitsBatch), P, P, P], ctypes.c_int),
             "bgv_debug_index_list_sums": ([P, u32, u32, u32, P], ctypes.c_int),
@@ -789,6 +799,13 @@ class Device:
         roots when dedup is 1); zeros after a same-message call"""
         out = BgvHashPath()
         self._check(self.lib.bgv_hash_stats(self.h, ctypes.byref(out)))
+        return out.as_dict()
+
+    def miller_path(self) -> dict:
+        """bgv_miller_path_stats: {steps, slice_sets, items} of the last verify, verify_bits,
+        partial or debug_stages on the context (steps 1: per-step line products, bgv_cfg.miller_steps)"""
+        out = BgvMillerPath()
+        self._check(self.lib.bgv_miller_path_stats(self.h, ctypes.byref(out)))
         return out.as_dict()
 
     def bits_path_stats(self) -> dict:

@@ -105,6 +105,56 @@ int main(int argc, char** argv) {
     fmul_c += bgv_fpmul_count;
     if (r == 0) { bgv_fpmul_count = 0; fp12_t e; fp12_final_exp(e, f); fe_c = bgv_fpmul_count; }
   }
+  // per-step line products (bgv_cfg.miller_steps; pairing.h miller_step_lines /
+  // miller_chain, kernels k_miller_steps and k_job_chain): one 98-set job in
+  // slices of G sets (argv[1], default the library's 49).  Counted: the slice
+  // products of the 68 steps (the Miller stage), then the joins of the slices
+  // per step, the chain and the product by the job pair (the tree stage; dense
+  // products at fp12_mul's count, which the cooperative c_mul spreads over 108
+  // one-product lanes).  The job value must equal the product of the two-pair
+  // items and the job pair exactly, as canonical residues.
+  const uint32_t steps_G = argc > 1 ? (uint32_t)atoi(argv[1]) : 49u;
+  double steps_loop_c = 0, steps_tree_c = 0;
+  int steps_mismatch = 0;
+  {
+    const uint32_t n = per_block;
+    static fp2_t jl[3 * MILLER_STEPS * per_block];
+    static g1a jp[per_block];
+    static int32_t jc[per_block];
+    g2j acc; jac_from_aff(acc, hsa);
+    g1j pa; jac_from_aff(pa, pts[0]);
+    for (uint32_t i = 0; i < n; i++) {
+      g2a q; jac_dbl(acc, acc); jac_to_aff(q, acc);
+      miller_lines(jl, n, i, q);
+      jac_add_aff(pa, pa, pts[1 + i % 63]); jac_to_aff(jp[i], pa);
+      jc[i] = C_OK;
+    }
+    fp12_t fpair; miller_loop(fpair, pts[5], false, hsa, false);  // stands for the (-G1, S_job) value
+    const uint32_t items = miller_item_count(n, steps_G);
+    static fp12_t fs[per_block * MILLER_STEPS];
+    bgv_fpmul_count = 0;
+    for (uint32_t t = 0; t < items; t++) {
+      uint32_t i0, cnt; miller_item_sets(i0, cnt, 0, n, t, steps_G);
+      for (uint32_t st = 0; st < (uint32_t)MILLER_STEPS; st++)
+        miller_step_lines(fs[t * MILLER_STEPS + st], jl, n, jp, jc, i0, cnt, st, miller_step_is_add(st));
+    }
+    steps_loop_c = (double)bgv_fpmul_count / n;
+    bgv_fpmul_count = 0;
+    fp12_t L[MILLER_STEPS];
+    for (uint32_t st = 0; st < (uint32_t)MILLER_STEPS; st++) {
+      L[st] = fs[st];
+      for (uint32_t t = 1; t < items; t++) fp12_mul(L[st], L[st], fs[t * MILLER_STEPS + st]);
+    }
+    fp12_t fj; miller_chain(fj, L); fp12_mul(fj, fj, fpair);
+    steps_tree_c = (double)bgv_fpmul_count / n;
+    fp12_t ref = fpair;
+    for (uint32_t i = 0; i < n; i += 2) {
+      fp12_t v; miller_loop_lines(v, jl, n, jp[i], i, jp[i + 1 < n ? i + 1 : i], i + 1, i + 1 < n);
+      fp12_mul(ref, ref, v);
+    }
+    const fp_t* x = (const fp_t*)&fj; const fp_t* y = (const fp_t*)&ref;
+    for (int k = 0; k < 12; k++) { fp_t u, v; fp_from_mont(u, x[k]); fp_from_mont(v, y[k]); if (memcmp(&u, &v, sizeof u)) steps_mismatch++; }
+  }
   // per-job bucket MSM of the signatures (bgv_kernels.hip k_msm_*), one 98-set job
   double msm_c = 0, msm_bucket_c = 0;
   {
@@ -174,6 +224,10 @@ int main(int argc, char** argv) {
   printf(" \"per_set_lines4\": {\"miller_lines\": %.1f, \"miller_loop\": %.1f, \"miller_loop_full_items\": %.1f, "
          "\"miller_product_tree\": %.1f, \"loop_values_match\": %s},\n",
          lines_c, loopl4_c * 25.0 / per_block, loopl4_c / 4.0, fmul_c * 25.0 / per_block, lines4_mismatch ? "false" : "true");
+  // per-step line products: the lines as above, the slice products in the Miller stage, joins + chain + job pair in the tree stage
+  printf(" \"per_set_steps\": {\"slice_sets\": %u, \"miller_lines\": %.1f, \"miller_loop\": %.1f, \"miller_product_tree\": %.1f, "
+         "\"loop_values_match\": %s},\n", steps_G, lines_c, steps_loop_c, steps_tree_c, steps_mismatch ? "false" : "true");
+  printf(" \"per_set_total_steps\": %.1f,\n", sig_c + hash_c + pk_c + msm_c + lines_c + steps_loop_c + miller_jobs + steps_tree_c);
   printf(" \"per_set_total\": %.1f,\n", sig_c + hash_c + pk_c + msm_c + miller_set + miller_jobs + f_tree);
   printf(" \"per_set_total_lines\": %.1f,\n", sig_c + hash_c + pk_c + msm_c + lines_c + loopl2_c / 2.0 + miller_jobs + f_tree);
   printf(" \"per_set_total_lines4\": %.1f\n}\n", sig_c + hash_c + pk_c + msm_c + lines_c + loopl4_c * 25.0 / per_block + miller_jobs +

@@ -331,6 +331,73 @@ int bgv_sm_check(const bgv_sm_batch* batch);
 int bgv_debug_same_message(bgv_ctx* ctx, const bgv_sm_batch* batch, uint8_t* set_valid, int32_t* set_code,
                            bgv_sm_stats* stats, uint8_t* p_group96, uint8_t* s_group192, uint8_t* h_group192);
 
+/* ---- same-message verification that also returns each group's aggregate ----
+ * In the reference a gossip attestation that verified goes straight into the
+ * pre-aggregation pool, where the main thread decodes the same 96 bytes again
+ * and adds the point to the committee's running aggregate:
+ *   bls.Signature.aggregate([aggregate.signature, signatureFromBytesNoCheck(sig)])
+ *   (chain/opPools/attestationPool.ts:182-199; :205-212 decodes the first
+ *   attestation of a root; syncCommitteeMessagePool.ts:139 does the same for
+ *   sync-committee messages).
+ * That is one Fp2 square root and one G2 addition per attestation over exactly
+ * the sets bgv_verify_same_message has just decoded, checked and grouped by
+ * signing root (the pool's key, the AttestationData root, maps one to one to
+ * the signing root within an epoch).  This entry returns, per group,
+ *   agg_sig96[g] = compress(prev_g + sum of sigma_i over the group's sets with
+ *                           set_valid = 1 and take != 0)
+ * an UNWEIGHTED sum (the r_i-weighted sums of the pairing check are other
+ * points), in the ZCash compressed form the pool stores.  Additive to ABI 4.
+ *
+ * set_valid, set_code and stats are exactly those of bgv_verify_same_message
+ * on the same batch, whatever `agg` holds: they do not depend on take or prev.
+ * A 192-byte (uncompressed) input signature is aggregated like a compressed
+ * one; the output is always compressed.  take and prev_sig96 follow
+ * batch->on_device: device pointers for a resident batch, otherwise staged
+ * with the other arrays.  n_sets == 0 succeeds and writes nothing.
+ *
+ * Only the single-key entry has this form.  The aggregate-set entries
+ * (bgv_verify_same_message_agg, _bits) feed aggregatedAttestationPool.ts:322,
+ * which merges on disjoint bitfields: a different rule, not built here.
+ *
+ * The sums run on the pubkey stream beside the Miller, fold and final-
+ * exponentiation stages, over the sets the classification left in; when a
+ * segment goes to the per-set retry they run once more over the final
+ * verdicts.
+ * When it pays (one MI355X, host batches): the two sum
+ * kernels take 0.57 ms of device time at 4,096 sets (64 groups of 64) and
+ * 1.3 ms at 31,232 (64 groups of 488), most of it beside the pairing stages:
+ * the clean call is 0.18 ms slower than bgv_verify_same_message at 4,096 sets
+ * (8.77 -> 8.94 ms) and 0.24 ms at 31,232 (10.63 -> 10.87 ms).  That is more
+ * than the plain call's run-to-run spread (0.015 / 0.022 ms): the sums are not
+ * free, they cost 2 %.  With 1 % wrong-message signatures the retry dominates
+ * both calls and the second pass adds 0.8 ms (22.6 -> 23.4 ms) and 1.4 ms
+ * (71.1 -> 72.5 ms).  What the caller saves, one Fp2 square root and one G2
+ * addition per attestation on its main thread, is not measured here.  A caller
+ * that does not keep a pool of compressed aggregates gains nothing: use
+ * bgv_verify_same_message. */
+typedef struct bgv_sm_agg {
+  const uint8_t* take;       /* [n_sets] or NULL (= every set): 0 keeps a set out of its group's aggregate;
+                                it is verified and reported like any other (the pool's AlreadyKnown bit,
+                                attestationPool.ts:190; two messages of one validator in one batch) */
+  const uint8_t* prev_sig96; /* [n_groups][96] or NULL: the group's running aggregate, compressed; the
+                                compressed identity (0xc0, 95 x 0) = none.  Trusted like
+                                signatureFromBytesNoCheck: decoded, NOT subgroup-checked */
+  uint8_t* agg_sig96;        /* out, host [n_groups][96]: compress(prev + sum of sigma_i over the sets with
+                                set_valid = 1 and take != 0); the compressed identity when that is the identity */
+  uint32_t* agg_count;       /* out, host [n_groups], may be NULL: sets added (prev not counted) */
+  int32_t* agg_code;         /* out, host [n_groups], may be NULL: 0, or the bgv_set_code with which prev did
+                                not decode (BAD_ENCODING, POINT_NOT_ON_CURVE); agg_sig96[g] is then the sum of
+                                the new sets alone */
+} bgv_sm_agg;
+int bgv_verify_same_message_aggregate(bgv_ctx* ctx, const bgv_sm_batch* batch, const bgv_sm_agg* agg, uint8_t* set_valid,
+                                      int32_t* set_code, bgv_sm_stats* stats);
+/* bgv_sm_check plus: agg and agg->agg_sig96 are non-NULL (host only, no device, no context) */
+int bgv_sm_agg_check(const bgv_sm_batch* batch, const bgv_sm_agg* agg);
+/* Device time (ms, HIP events on the pubkey stream) of the two sum kernels in
+ * the first pass of the last bgv_verify_same_message_aggregate on the context;
+ * 0 when the last same-message call was another entry. */
+int bgv_sm_agg_ms(bgv_ctx* ctx, float* ms);
+
 /* ---- same-message batches of aggregate sets --------------------------------
  * The same identity holds when a set's key is an aggregate:
  *   prod_i e(PK_i, H(m))^{r_i} = e(sum_i r_i PK_i, H(m)),  PK_i = sum_j pk_ij.

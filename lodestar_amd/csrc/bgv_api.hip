@@ -20,6 +20,7 @@
 
 #include "bgv_internal.h"
 #include "msm_g1.h"
+#include "sig_agg.h"
 #include "../../include/bgv.h"
 
 using namespace bgv;
@@ -141,6 +142,15 @@ struct bgv_ctx {
   dbuf<g1j> sma_pk;           // per set: PK_i, Jacobian
   dbuf<int32_t> sma_pk_code;  // per set: its key code
   dbuf<g1a> sma_aff;          // PK_i affine: the retry's sets, or every set for the debug entry
+  // bgv_verify_same_message_aggregate
+  dbuf<g2j> sag_seg;          // per segment: the unweighted signature sum
+  dbuf<uint32_t> sag_cnt;     // per segment, then per group: sets in the sum
+  dbuf<int32_t> sag_code;     // per group: the code of its running aggregate
+  dbuf<uint8_t> sag_out;      // per group: 96 compressed bytes
+  dbuf<uint8_t> sag_valid;    // second pass: the final verdicts
+  dbuf<g2a> sag_sig;          // second pass: the decoded signatures, kept across the per-set retry
+  hipEvent_t ev_sag[2] = {};  // around the two kernels of the first pass (bgv_sm_agg_ms)
+  bool sag_timed = false;
   // resident index lists (bgv_index_list_set) and the expansion of bgv_verify_bits
   uint32_t* idx_list[BGV_MAX_INDEX_LISTS] = {};
   uint32_t idx_list_n[BGV_MAX_INDEX_LISTS] = {};
@@ -310,6 +320,7 @@ int bgv_open_cfg(int device, const bgv_cfg* cfg, bgv_ctx** out) {
   HIPCHK(hipEventCreateWithFlags(&c->ev_maps, hipEventDisableTiming));
   HIPCHK(hipEventCreateWithFlags(&c->ev_chk, hipEventDisableTiming));
   for (auto& e : c->ev_bits) HIPCHK(hipEventCreate(&e));
+  for (auto& e : c->ev_sag) HIPCHK(hipEventCreate(&e));
   *out = c;
   c = nullptr;  // owned by the caller now
   return BGV_OK;
@@ -333,6 +344,7 @@ int bgv_close(bgv_ctx* c) {
   (void)hipEventDestroy(c->ev_maps);
   (void)hipEventDestroy(c->ev_chk);
   for (auto& e : c->ev_bits) (void)hipEventDestroy(e);
+  for (auto& e : c->ev_sag) (void)hipEventDestroy(e);
   for (auto& l : c->idx_list)
     if (l) (void)hipFree(l);
   for (auto& l : c->idx_sums)
@@ -355,6 +367,8 @@ int bgv_close(bgv_ctx* c) {
   c->sm_skip.release(); c->sm_list.release(); c->sm_zero.release(); c->sm_seg_code.release(); c->sm_win.release();
   c->sm_hg.release(); c->sm_sg.release(); c->sm_pg.release(); c->sm_retry.release();
   c->sma_pk.release(); c->sma_pk_code.release(); c->sma_aff.release();
+  c->sag_seg.release(); c->sag_cnt.release(); c->sag_code.release(); c->sag_out.release(); c->sag_valid.release();
+  c->sag_sig.release();
   c->mb_fp.release(); c->mb_u64.release();
   (void)hipStreamDestroy(c->st);
   (void)hipStreamDestroy(c->st_hash);
@@ -1848,11 +1862,26 @@ static int sm_groups(bgv_ctx* c, sm_dev& k, const uint32_t* group_offsets, bool 
   return BGV_OK;
 }
 
+// bgv_verify_same_message_aggregate: what sm_back computes on top of the
+// verdicts (the three other fronts pass none)
+struct sm_agg_req {
+  const uint8_t* d_take = nullptr;  // device [n] or NULL
+  const uint8_t* d_prev = nullptr;  // device [G][96] or NULL
+  uint8_t* agg_sig96 = nullptr;     // host outputs (bgv_sm_agg)
+  uint32_t* agg_count = nullptr;
+  int32_t* agg_code = nullptr;
+};
+
 // The device half of a same-message call, from the staged (or resident) arrays
 // on.  k.agg picks the key side, where the pairs of the virtual batch run and
 // what the retry takes as a set's key; everything else is one path.
+// ag (bgv_verify_same_message_aggregate): the unweighted signature sums run
+// speculatively on the pubkey stream behind the weighted G1 sum, over the sets
+// the classification left in: they need the decode, `skip` and `take`, not the
+// pairing.  When the whole-batch check holds that is the answer; when sets went
+// to the retry the two kernels run once more with the final verdicts.
 static int sm_back(bgv_ctx* c, sm_dev& k, uint8_t* set_valid, int32_t* set_code, bgv_sm_stats* stats, uint8_t* pk_set96,
-                   uint8_t* p_group96, uint8_t* s_group192, uint8_t* h_group192) {
+                   uint8_t* p_group96, uint8_t* s_group192, uint8_t* h_group192, const sm_agg_req* ag = nullptr) {
   const uint32_t n = k.n, G = k.G, S = k.sg.S, n_raw = k.n_raw;
   const std::vector<uint32_t>&seg_off = k.sg.seg_off, &seg_group = k.sg.seg_group;
   const uint32_t *d_seg_off = k.d_seg_off, *d_seg_group = k.d_seg_group, *d_group_seg = k.d_group_seg, *d_iota = k.d_iota;
@@ -1886,6 +1915,10 @@ static int sm_back(bgv_ctx* c, sm_dev& k, uint8_t* set_valid, int32_t* set_code,
   if ((r = c->sm_skip.ensure(n)) || (r = c->sm_zero.ensure(n)) || (r = c->sm_seg_code.ensure(S)) ||
       (r = c->sm_win.ensure((size_t)S * 16)) || (r = c->sm_hg.ensure(G)) || (r = c->q_part.ensure(2 * (size_t)G)) ||
       (k.agg && ((r = c->sma_pk.ensure(n)) || (r = c->sma_pk_code.ensure(n)))))
+    return r;
+  c->sag_timed = false;
+  if (ag && ((r = c->sag_seg.ensure(S)) || (r = c->sag_cnt.ensure((size_t)S + G)) || (r = c->sag_code.ensure(G)) ||
+             (r = c->sag_out.ensure((size_t)G * 96))))
     return r;
   HIPCHK(hipMemsetAsync(c->sm_zero.p, 0, (size_t)n * 4, c->st));
   sm_view v;
@@ -1944,6 +1977,19 @@ static int sm_back(bgv_ctx* c, sm_dev& k, uint8_t* set_valid, int32_t* set_code,
   else launch_sm_g1_sum(c->st_pk, v);
   HIPCHK(hipGetLastError());
   HIPCHK(hipEventRecord(c->ev_dep[ST_PK_SCALE], c->st_pk));
+  sig_agg_view av;
+  memset(&av, 0, sizeof av);
+  if (ag) {  // behind the event: nothing of the pairing path waits for these two
+    av.n_segs = S; av.n_groups = G; av.seg_off = d_seg_off; av.group_seg = d_group_seg;
+    av.sig_aff = w.sig_aff; av.skip = c->sm_skip.p; av.take = ag->d_take; av.prev = ag->d_prev;
+    av.seg_sum = c->sag_seg.p; av.seg_cnt = c->sag_cnt.p; av.out96 = c->sag_out.p; av.out_cnt = c->sag_cnt.p + S;
+    av.out_code = c->sag_code.p;
+    HIPCHK(hipEventRecord(c->ev_sag[0], c->st_pk));
+    launch_sm_sig_agg(c->st_pk, av);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(c->ev_sag[1], c->st_pk));
+    c->sag_timed = true;
+  }
   {
     // the per-job MSM sums what `skip` leaves in and rejects nothing: a
     // rejected set is left out, its segment goes on
@@ -1983,11 +2029,24 @@ static int sm_back(bgv_ctx* c, sm_dev& k, uint8_t* set_valid, int32_t* set_code,
 
   // first-pass results
   const size_t o_jr = 256, o_sc = o_jr + (((size_t)S * 4 + 255) & ~size_t(255)), o_sk = o_sc + (((size_t)n * 4 + 255) & ~size_t(255));
-  if ((r = pinned_reserve(c->pin_out, c->pin_out_cap, o_sk + (size_t)n * 4))) return r;
+  // the aggregate outputs (ag) behind them: 96 bytes, a count and a code per group, then room for the verdicts
+  const size_t o_as = o_sk + (((size_t)n * 4 + 255) & ~size_t(255)), o_ac = o_as + (((size_t)G * 96 + 255) & ~size_t(255)),
+               o_ad = o_ac + (((size_t)G * 4 + 255) & ~size_t(255)), o_av = o_ad + (((size_t)G * 4 + 255) & ~size_t(255));
+  if ((r = pinned_reserve(c->pin_out, c->pin_out_cap, ag ? o_av + n : o_sk + (size_t)n * 4))) return r;
+  auto agg_copies = [&]() -> int {
+    HIPCHK(hipMemcpyAsync(c->pin_out + o_as, av.out96, (size_t)G * 96, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(hipMemcpyAsync(c->pin_out + o_ac, av.out_cnt, (size_t)G * 4, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(hipMemcpyAsync(c->pin_out + o_ad, av.out_code, (size_t)G * 4, hipMemcpyDeviceToHost, c->st));
+    return 0;
+  };
   HIPCHK(hipMemcpyAsync(c->pin_out, w.flags, 4, hipMemcpyDeviceToHost, c->st));
   HIPCHK(hipMemcpyAsync(c->pin_out + o_jr, w.job_result, (size_t)S * 4, hipMemcpyDeviceToHost, c->st));
   HIPCHK(hipMemcpyAsync(c->pin_out + o_sc, w.set_code, (size_t)n * 4, hipMemcpyDeviceToHost, c->st));
   HIPCHK(hipMemcpyAsync(c->pin_out + o_sk, c->sm_skip.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->st));
+  if (ag) {  // the speculative sums join here: the clean path gains no synchronise
+    HIPCHK(hipStreamWaitEvent(c->st, c->ev_sag[1], 0));
+    if ((r = agg_copies())) return r;
+  }
   if (pk_set96 || p_group96 || s_group192 || h_group192) {  // the debug entries; pk_set96: aggregate keys only
     const size_t o_set = (size_t)G * 480;
     if ((r = c->sm_pg.ensure(G)) || (r = c->sm_sg.ensure(G)) || (k.agg && (r = c->sma_aff.ensure(n))) ||
@@ -2033,6 +2092,10 @@ static int sm_back(bgv_ctx* c, sm_dev& k, uint8_t* set_valid, int32_t* set_code,
                  o_msg = o_scal + up((size_t)nr * 8), o_sig = o_msg + up((size_t)nr * 32), o_pk = o_sig + up((size_t)nr * 192),
                  total_r = k.agg ? o_pk + up((size_t)nr * 96) : o_pk;
     if ((r = c->sm_retry.ensure(total_r)) || (r = c->sm_list.ensure(2 * (size_t)nr)) || (k.agg && (r = c->sma_aff.ensure(nr)))) return r;
+    if (ag) {  // the retry decodes its sets into the same work buffers: keep the batch's signatures for the second pass
+      if ((r = c->sag_sig.ensure(n)) || (r = c->sag_valid.ensure(n))) return r;
+      HIPCHK(hipMemcpyAsync(c->sag_sig.p, w.sig_aff, (size_t)n * sizeof(g2a), hipMemcpyDeviceToDevice, c->st));
+    }
     HIPCHK(hipMemcpyAsync(c->sm_list.p, list.data(), (size_t)nr * 4, hipMemcpyHostToDevice, c->st));
     HIPCHK(hipMemcpyAsync(c->sm_list.p + nr, list_group.data(), (size_t)nr * 4, hipMemcpyHostToDevice, c->st));
     uint8_t* base = c->sm_retry.p;
@@ -2064,6 +2127,21 @@ static int sm_back(bgv_ctx* c, sm_dev& k, uint8_t* set_valid, int32_t* set_code,
     std::vector<int32_t> jr2(nr);
     if ((r = finish_results(c, d2, w2, jr2.data(), nullptr, nullptr))) return r;
     for (uint32_t j = 0; j < nr; j++) set_valid[list[j]] = jr2[j] == 1 ? 1 : 0;
+    if (ag) {  // second pass: the same two kernels over the sets with set_valid = 1
+      memcpy(c->pin_out + o_av, set_valid, n);
+      HIPCHK(hipMemcpyAsync(c->sag_valid.p, c->pin_out + o_av, n, hipMemcpyHostToDevice, c->st));
+      av.sig_aff = c->sag_sig.p;
+      av.valid = c->sag_valid.p;
+      launch_sm_sig_agg(c->st, av);
+      HIPCHK(hipGetLastError());
+      if ((r = agg_copies())) return r;
+      HIPCHK(hipStreamSynchronize(c->st));
+    }
+  }
+  if (ag) {
+    memcpy(ag->agg_sig96, c->pin_out + o_as, (size_t)G * 96);
+    if (ag->agg_count) memcpy(ag->agg_count, c->pin_out + o_ac, (size_t)G * 4);
+    if (ag->agg_code) memcpy(ag->agg_code, c->pin_out + o_ad, (size_t)G * 4);
   }
   if (stats) {
     stats->n_sets = n; stats->n_groups = G; stats->n_segments = S;
@@ -2075,7 +2153,7 @@ static int sm_back(bgv_ctx* c, sm_dev& k, uint8_t* set_valid, int32_t* set_code,
 }
 
 static int sm_run(bgv_ctx* c, const bgv_sm_batch* b, uint8_t* set_valid, int32_t* set_code, bgv_sm_stats* stats,
-                  uint8_t* p_group96, uint8_t* s_group192, uint8_t* h_group192) {
+                  uint8_t* p_group96, uint8_t* s_group192, uint8_t* h_group192, const bgv_sm_agg* agg = nullptr) {
   sm_dev k;
   if (int r = sm_open(c, b, set_valid, stats, k)) return r;
   if (!k.n) return BGV_OK;
@@ -2084,7 +2162,9 @@ static int sm_run(bgv_ctx* c, const bgv_sm_batch* b, uint8_t* set_valid, int32_t
   const bool host = !b->on_device;
   k.d_idx = b->pk_indices;
   // staging: the segment tables always, the batch arrays of a host batch
-  stage_seg segs[10] = {
+  // (bgv_verify_same_message_aggregate: take and prev of a host batch ride behind them in the same copy)
+  const uint8_t *d_take = nullptr, *d_prev = nullptr;
+  stage_seg segs[12] = {
       {k.sg.seg_off.data(), ((size_t)S + 1) * 4, (const void**)&k.d_seg_off, 0},
       {k.sg.seg_group.data(), (size_t)S * 4, (const void**)&k.d_seg_group, 0},
       {k.sg.group_seg.data(), ((size_t)G + 1) * 4, (const void**)&k.d_group_seg, 0},
@@ -2095,13 +2175,20 @@ static int sm_run(bgv_ctx* c, const bgv_sm_batch* b, uint8_t* set_valid, int32_t
       {b->scalars, b->scalars ? (size_t)n * 8 : 0, (const void**)&k.d_scalars, 0},
       {b->sigs, (size_t)n * 192, (const void**)&k.d_sigs, 0},
       {b->sig_len, (size_t)n * 4, (const void**)&k.d_len, 0},
+      {agg ? agg->take : nullptr, agg && agg->take ? (size_t)n : 0, (const void**)&d_take, 0},
+      {agg ? agg->prev_sig96 : nullptr, agg && agg->prev_sig96 ? (size_t)G * 96 : 0, (const void**)&d_prev, 0},
   };
   size_t bytes = 0;
-  if (int r = stage_pack(c, segs, host ? 10 : 4, bytes)) return r;
+  if (int r = stage_pack(c, segs, host ? (agg ? 12 : 10) : 4, bytes)) return r;
   if (host && b->scalars)  // checked on the pinned copy
     if (int r = scalars_nonzero((const uint64_t*)(c->pin_in + segs[7].off), n)) return r;
   if (int r = stage_issue(c, bytes)) return r;
-  return sm_back(c, k, set_valid, set_code, stats, nullptr, p_group96, s_group192, h_group192);
+  if (!agg) return sm_back(c, k, set_valid, set_code, stats, nullptr, p_group96, s_group192, h_group192);
+  sm_agg_req q;
+  q.d_take = !agg->take ? nullptr : (host ? d_take : agg->take);
+  q.d_prev = !agg->prev_sig96 ? nullptr : (host ? d_prev : agg->prev_sig96);
+  q.agg_sig96 = agg->agg_sig96; q.agg_count = agg->agg_count; q.agg_code = agg->agg_code;
+  return sm_back(c, k, set_valid, set_code, stats, nullptr, p_group96, s_group192, h_group192, &q);
 }
 
 static int sma_run(bgv_ctx* c, const bgv_sma_batch* b, uint8_t* set_valid, int32_t* set_code, bgv_sm_stats* stats,
@@ -2233,6 +2320,34 @@ static int sm_done(bgv_ctx* c, int r) {
 
 int bgv_verify_same_message(bgv_ctx* c, const bgv_sm_batch* b, uint8_t* set_valid, int32_t* set_code, bgv_sm_stats* stats) {
   return sm_done(c, sm_run(c, b, set_valid, set_code, stats, nullptr, nullptr, nullptr));
+}
+
+static int sm_agg_args(const bgv_sm_agg* agg) {
+  if (!agg) return fail(BGV_E_INVALID_ARG, "agg is NULL");
+  if (!agg->agg_sig96) return fail(BGV_E_INVALID_ARG, "agg_sig96 is NULL");
+  return BGV_OK;
+}
+
+int bgv_sm_agg_check(const bgv_sm_batch* b, const bgv_sm_agg* agg) {
+  if (int r = bgv_sm_check(b)) return r;
+  return sm_agg_args(agg);
+}
+
+int bgv_verify_same_message_aggregate(bgv_ctx* c, const bgv_sm_batch* b, const bgv_sm_agg* agg, uint8_t* set_valid,
+                                      int32_t* set_code, bgv_sm_stats* stats) {
+  if (int r = sm_agg_args(agg)) return r;
+  if (!c) return fail(BGV_E_INVALID_ARG, "null ctx");
+  return sm_done(c, sm_run(c, b, set_valid, set_code, stats, nullptr, nullptr, nullptr, agg));
+}
+
+int bgv_sm_agg_ms(bgv_ctx* c, float* ms) {
+  if (!c || !ms) return fail(BGV_E_INVALID_ARG, "null argument");
+  *ms = 0.f;
+  if (!c->sag_timed) return BGV_OK;
+  HIPCHK(hipSetDevice(c->device));
+  HIPCHK(hipEventSynchronize(c->ev_sag[1]));
+  HIPCHK(hipEventElapsedTime(ms, c->ev_sag[0], c->ev_sag[1]));
+  return BGV_OK;
 }
 
 int bgv_debug_same_message(bgv_ctx* c, const bgv_sm_batch* b, uint8_t* set_valid, int32_t* set_code, bgv_sm_stats* stats,

@@ -244,6 +244,10 @@ void launch_sma_classify(hipStream_t st, const sm_view& v);
 void launch_sma_g1_sum(hipStream_t st, const sm_view& v);
 void launch_sma_pk_aff(hipStream_t st, const g1j* pk_set, g1a* out, uint32_t n);
 void launch_sma_retry_gather(hipStream_t st, const sm_retry& r, const g1j* pk_set, g1a* o_pk);
+// bgv_verify_same_message_aggregate: the unweighted signature sum of every
+// group, compressed (sig_agg.h; k_sm_sig_seg, k_sm_sig_group in bgv_sig_agg.hip)
+struct sig_agg_view;
+void launch_sm_sig_agg(hipStream_t st, const sig_agg_view& v);
 
 // ---- committee bitfields over resident index lists (bgv_verify_bits, bgv_bits.hip)
 struct bits_args {

@@ -1032,23 +1032,6 @@ __global__ void BGV_BULK k_gen_keys(g1a* table, uint32_t* sk_store, uint32_t fir
   table[i] = a;
 }
 
-BGV_NI void g2_compress(uint8_t* out, const g2j& p) {
-  g2a a;
-  if (!jac_to_aff(a, p)) {
-    for (int k = 0; k < 96; k++) out[k] = 0;
-    out[0] = 0xc0;
-    return;
-  }
-  uint8_t buf[96];
-  fp_t t;
-  fp_from_mont(t, a.x.c1);
-  fp_to_be48(buf, t);
-  fp_from_mont(t, a.x.c0);
-  fp_to_be48(buf + 48, t);
-  buf[0] |= 0x80u | (fp2_lex_largest(a.y) ? 0x20u : 0u);
-  for (int k = 0; k < 96; k++) out[k] = buf[k];
-}
-
 __global__ void BGV_BULK k_gen_sign(dev_batch b, const uint32_t* sk_store, uint8_t* sigs_out) {
   const uint32_t i = gtid();
   if (i >= b.n_sets) return;

@@ -388,6 +388,26 @@ BGV_NI int32_t g2_decompress(g2a& out, bool& inf, const uint8_t* b) {
   return C_OK;
 }
 
+// Jacobian -> ZCash 96-byte compressed G2 (one inversion); the identity is
+// 0xc0 and 95 zero bytes.  Users: bgv_gen_sign, and the per-group aggregate
+// signatures of bgv_verify_same_message_aggregate (sig_agg.h).
+BGV_NI void g2_compress(uint8_t* out, const g2j& p) {
+  g2a a;
+  if (!jac_to_aff(a, p)) {
+    for (int k = 0; k < 96; k++) out[k] = 0;
+    out[0] = 0xc0;
+    return;
+  }
+  uint8_t buf[96];
+  fp_t t;
+  fp_from_mont(t, a.x.c1);
+  fp_to_be48(buf, t);
+  fp_from_mont(t, a.x.c0);
+  fp_to_be48(buf + 48, t);
+  buf[0] |= 0x80u | (fp2_lex_largest(a.y) ? 0x20u : 0u);
+  for (int k = 0; k < 96; k++) out[k] = buf[k];
+}
+
 // 192-byte uncompressed G2 (blst POINTonE2_Deserialize_Z behind
 // @chainsafe/blst's Signature.fromBytes: a 192-byte input must not carry the
 // compression flag (P2_Affine rejects len != (in[0] & 0x80 ? 96 : 192)), the

@@ -23,6 +23,8 @@
  *                                                after a failed combined check
  *   verifySameMessage(ctx, smBatch) -> Promise<smResult>, verifySameMessageSync(ctx, smBatch) -> smResult
  *                                                bgv_verify_same_message (see "same-message batches" below)
+ *   verifySameMessageAggregate(ctx, smBatch + {take?, prevSigs?}) -> Promise<smResult + {aggSigs, aggCount, aggCode}>,
+ *   verifySameMessageAggregateSync(...)   bgv_verify_same_message_aggregate: the verdicts plus every group's aggregate signature
  *   verifySameMessageAgg(ctx, smaBatch) -> Promise<smResult>, verifySameMessageAggSync(ctx, smaBatch) -> smResult
  *   verifySameMessageBits(ctx, smbBatch) -> Promise<smResult>, verifySameMessageBitsSync(ctx, smbBatch) -> smResult
  *                                                bgv_verify_same_message_agg: the sets' keys are aggregates
@@ -608,7 +610,12 @@ static napi_value VerifySync(napi_env env, napi_callback_info info) {
  * the offsets are copied at call time and every length is checked against the copy.
  *
  * verifySameMessageAgg / verifySameMessageAggSync (bgv_verify_same_message_agg): the same, with
- * pkOffsets: Uint32Array (n_sets + 1 entries, copied too) and pkIndices holding pkOffsets[n_sets] keys. */
+ * pkOffsets: Uint32Array (n_sets + 1 entries, copied too) and pkIndices holding pkOffsets[n_sets] keys.
+ *
+ * verifySameMessageAggregate / verifySameMessageAggregateSync (bgv_verify_same_message_aggregate): the batch of
+ * verifySameMessage plus take?: Uint8Array (one per set, 0 keeps a valid set out of its group's aggregate) and
+ * prevSigs?: Uint8Array (96 B per GROUP, the running aggregates, compressed); the result gains aggSigs: Uint8Array
+ * (96 B per group), aggCount: Uint32Array and aggCode: Int32Array (bgv_sm_agg). */
 enum { S_GRP, S_PKI, S_MSG, S_SIG, S_LEN, S_RAW, S_PKO, S_SRC, S_BITS, S_FIELDS }; /* S_SRC on: verifySameMessageBits only */
 static const char* SM_FIELD[S_FIELDS] = {"groupOffsets", "pkIndices", "msgs", "sigs", "sigLen", "rawPks", "pkOffsets", "src", "bits"};
 static const napi_typedarray_type SM_FIELD_T[S_FIELDS] = {napi_uint32_array, napi_uint32_array, napi_uint8_array,
@@ -624,6 +631,12 @@ typedef struct {
   bgv_smb_batch bb;
   uint32_t* src_copy;
   bgv_bits_path path; /* agg == 2: the path counters of the call */
+  int with_sums;      /* verifySameMessageAggregate (agg == 0): `ag` and its three outputs */
+  bgv_sm_agg ag;
+  uint8_t* agg_sigs;
+  uint32_t* agg_count;
+  int32_t* agg_code;
+  napi_ref sum_refs[2]; /* take, prevSigs */
   uint32_t* pk_off;
   uint32_t* group_off;
   uint8_t* valid;
@@ -647,6 +660,11 @@ static void sm_free(napi_env env, sm_job* j) {
   free(j->src_copy);
   free(j->valid);
   free(j->codes);
+  for (int k = 0; k < 2; k++)
+    if (j->sum_refs[k]) napi_delete_reference(env, j->sum_refs[k]);
+  free(j->agg_sigs);
+  free(j->agg_count);
+  free(j->agg_code);
 }
 
 static int sm_read_batch(napi_env env, napi_value obj, sm_job* j, int pin) {
@@ -718,6 +736,46 @@ static int sm_read_batch(napi_env env, napi_value obj, sm_job* j, int pin) {
   j->b.n_raw = (uint32_t)(n[S_RAW] / 96);
   j->b.scalars = NULL; /* drawn inside the library */
   j->b.on_device = 0;
+  if (j->with_sums) {
+    static const char* name[2] = {"take", "prevSigs"};
+    const size_t need[2] = {n_sets, 96ull * j->b.n_groups};
+    const void* q[2] = {NULL, NULL};
+    for (int k = 0; k < 2; k++) {
+      bool has = false;
+      napi_value val;
+      napi_valuetype vt;
+      size_t len = 0;
+      void* ptr = NULL;
+      napi_has_named_property(env, obj, name[k], &has);
+      if (!has) continue;
+      napi_get_named_property(env, obj, name[k], &val);
+      napi_typeof(env, val, &vt);
+      if (vt == napi_undefined || vt == napi_null) continue;
+      if (typed(env, val, napi_uint8_array, &ptr, &len)) {
+        napi_throw_type_error(env, NULL, "take / prevSigs must be a Uint8Array");
+        return -1;
+      }
+      if (len < need[k]) {
+        napi_throw_range_error(env, NULL, "take / prevSigs shorter than the set / group count");
+        return -1;
+      }
+      q[k] = ptr;
+      if (pin) napi_create_reference(env, val, 1, &j->sum_refs[k]);
+    }
+    const size_t G = j->b.n_groups ? j->b.n_groups : 1;
+    j->agg_sigs = (uint8_t*)calloc(G, 96);
+    j->agg_count = (uint32_t*)calloc(G, 4);
+    j->agg_code = (int32_t*)calloc(G, 4);
+    if (!j->agg_sigs || !j->agg_count || !j->agg_code) {
+      napi_throw_error(env, NULL, "out of memory");
+      return -1;
+    }
+    j->ag.take = (const uint8_t*)q[0];
+    j->ag.prev_sig96 = (const uint8_t*)q[1];
+    j->ag.agg_sig96 = j->agg_sigs;
+    j->ag.agg_count = j->agg_count;
+    j->ag.agg_code = j->agg_code;
+  }
   if (j->agg) {
     memset(&j->ba, 0, sizeof j->ba);
     j->ba.n_sets = n_sets;
@@ -826,8 +884,9 @@ static void sm_run(sm_job* j) {
       j->status = bgv_verify_same_message_bits(j->c->ctx, &j->bb, j->valid, j->codes, &j->stats);
       if (j->status == BGV_OK) j->status = bgv_bits_path_stats(j->c->ctx, &j->path); /* under the same lock: this call's */
     } else {
-      j->status = j->agg ? bgv_verify_same_message_agg(j->c->ctx, &j->ba, j->valid, j->codes, &j->stats)
-                         : bgv_verify_same_message(j->c->ctx, &j->b, j->valid, j->codes, &j->stats);
+      j->status = j->agg         ? bgv_verify_same_message_agg(j->c->ctx, &j->ba, j->valid, j->codes, &j->stats)
+                  : j->with_sums ? bgv_verify_same_message_aggregate(j->c->ctx, &j->b, &j->ag, j->valid, j->codes, &j->stats)
+                                 : bgv_verify_same_message(j->c->ctx, &j->b, j->valid, j->codes, &j->stats);
     }
     if (j->status != BGV_OK) snprintf(j->err, sizeof j->err, "bgv error %d: %s", j->status, bgv_last_error());
   }
@@ -856,6 +915,20 @@ static napi_value sm_result(napi_env env, const sm_job* j) {
   if (j->agg == 2) {
     napi_create_uint32(env, j->path.keys_expanded, &v);
     napi_set_named_property(env, o, "pubkeysAggregated", v);
+  }
+  if (j->with_sums) {
+    const size_t G = j->b.n_sets ? j->b.n_groups : 0; /* an empty batch writes nothing */
+    if (napi_create_arraybuffer(env, 96 * G, &dst, &ab) != napi_ok) return NULL;
+    if (G) memcpy(dst, j->agg_sigs, 96 * G);
+    napi_create_typedarray(env, napi_uint8_array, 96 * G, ab, 0, &v);
+    napi_set_named_property(env, o, "aggSigs", v);
+    if (napi_create_arraybuffer(env, 4 * G, &dst, &ab) != napi_ok) return NULL;
+    if (G) memcpy(dst, j->agg_count, 4 * G);
+    napi_create_typedarray(env, napi_uint32_array, G, ab, 0, &v);
+    napi_set_named_property(env, o, "aggCount", v);
+    v = new_int32_array(env, j->agg_code, G);
+    if (!v) return NULL;
+    napi_set_named_property(env, o, "aggCode", v);
   }
   napi_create_double(env, (double)j->stats.total_ms, &v);
   napi_set_named_property(env, o, "deviceMs", v);
@@ -898,6 +971,8 @@ static napi_value sm_async(napi_env env, napi_callback_info info, int agg) {
   if (!c) return NULL;
   sm_job* j = (sm_job*)calloc(1, sizeof *j);
   j->c = c;
+  j->with_sums = agg == 3;
+  if (agg == 3) agg = 0;
   j->agg = agg;
   if (agg == 2 ? smb_read_batch(env, a[1], j, 1) : sm_read_batch(env, a[1], j, 1)) {
     sm_free(env, j);
@@ -907,7 +982,7 @@ static napi_value sm_async(napi_env env, napi_callback_info info, int agg) {
   napi_create_reference(env, a[0], 1, &j->ctx_ref); /* the context outlives its queued work */
   napi_value promise, name;
   NAPI_CALL(env, napi_create_promise(env, &j->deferred, &promise));
-  NAPI_CALL(env, napi_create_string_utf8(env, agg == 2 ? "bgv_verify_same_message_bits" : agg ? "bgv_verify_same_message_agg" : "bgv_verify_same_message",
+  NAPI_CALL(env, napi_create_string_utf8(env, agg == 2 ? "bgv_verify_same_message_bits" : agg ? "bgv_verify_same_message_agg" : j->with_sums ? "bgv_verify_same_message_aggregate" : "bgv_verify_same_message",
                                          NAPI_AUTO_LENGTH, &name));
   NAPI_CALL(env, napi_create_async_work(env, NULL, name, sm_exec, sm_done, j, &j->work));
   NAPI_CALL(env, napi_queue_async_work(env, j->work));
@@ -923,6 +998,8 @@ static napi_value sm_sync(napi_env env, napi_callback_info info, int agg) {
   sm_job j;
   memset(&j, 0, sizeof j);
   j.c = c;
+  j.with_sums = agg == 3;
+  if (agg == 3) agg = 0;
   j.agg = agg;
   napi_value r = NULL;
   if (!(agg == 2 ? smb_read_batch(env, a[1], &j, 0) : sm_read_batch(env, a[1], &j, 0))) {
@@ -938,6 +1015,8 @@ static napi_value VerifySameMessage(napi_env env, napi_callback_info info) { ret
 static napi_value VerifySameMessageSync(napi_env env, napi_callback_info info) { return sm_sync(env, info, 0); }
 static napi_value VerifySameMessageAgg(napi_env env, napi_callback_info info) { return sm_async(env, info, 1); }
 static napi_value VerifySameMessageAggSync(napi_env env, napi_callback_info info) { return sm_sync(env, info, 1); }
+static napi_value VerifySameMessageAggregate(napi_env env, napi_callback_info info) { return sm_async(env, info, 3); }
+static napi_value VerifySameMessageAggregateSync(napi_env env, napi_callback_info info) { return sm_sync(env, info, 3); }
 static napi_value VerifySameMessageBits(napi_env env, napi_callback_info info) { return sm_async(env, info, 2); }
 static napi_value VerifySameMessageBitsSync(napi_env env, napi_callback_info info) { return sm_sync(env, info, 2); }
 
@@ -1195,6 +1274,8 @@ static napi_value Init(napi_env env, napi_value exports) {
       {"combineFinal", NULL, CombineFinal, NULL, NULL, NULL, napi_enumerable, NULL},
       {"verifySameMessage", NULL, VerifySameMessage, NULL, NULL, NULL, napi_enumerable, NULL},
       {"verifySameMessageSync", NULL, VerifySameMessageSync, NULL, NULL, NULL, napi_enumerable, NULL},
+      {"verifySameMessageAggregate", NULL, VerifySameMessageAggregate, NULL, NULL, NULL, napi_enumerable, NULL},
+      {"verifySameMessageAggregateSync", NULL, VerifySameMessageAggregateSync, NULL, NULL, NULL, napi_enumerable, NULL},
       {"verifySameMessageAgg", NULL, VerifySameMessageAgg, NULL, NULL, NULL, napi_enumerable, NULL},
       {"verifySameMessageAggSync", NULL, VerifySameMessageAggSync, NULL, NULL, NULL, napi_enumerable, NULL},
       {"verifySameMessageBits", NULL, VerifySameMessageBits, NULL, NULL, NULL, napi_enumerable, NULL},

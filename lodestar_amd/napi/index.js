@@ -285,29 +285,68 @@ function checkSameMessage(sets, message) {
 
 // calls [{sets, message}] -> the groups of ONE device call: one group per
 // call, calls whose messages are byte-equal share a group (first appearance
-// order).  where[k] = [start, end) of call k in the flattened sets.
+// order).  where[k] = [start, end) of call k in the flattened sets.  A call
+// that asks for its aggregate (call.agg, verifyAndAggregateSameMessage) ALWAYS
+// forms its own group, because the aggregate is per call; groupOf[k] is the
+// group of call k.
 function mergeSameMessage(calls) {
   const byMsg = new Map();
   const order = [];
   calls.forEach((c, k) => {
-    const key = Buffer.from(c.message).toString("hex");
+    const key = c.agg ? `#${k}` : Buffer.from(c.message).toString("hex");
     if (!byMsg.has(key)) { byMsg.set(key, {message: c.message, calls: []}); order.push(key); }
     byMsg.get(key).calls.push(k);
   });
   const groups = [];
   const where = new Array(calls.length);
+  const groupOf = new Array(calls.length);
   let pos = 0;
   for (const key of order) {
     const g = byMsg.get(key);
     const sets = [];
     for (const k of g.calls) {
       where[k] = [pos, pos + calls[k].sets.length];
+      groupOf[k] = groups.length;
       pos += calls[k].sets.length;
       for (const s of calls[k].sets) sets.push(s);
     }
     groups.push({message: g.message, sets});
   }
-  return {groups, where};
+  return {groups, where, groupOf};
+}
+
+// the compressed identity of G2: "no running aggregate", and the aggregate of no signature
+const G2_IDENTITY_96 = (() => { const b = new Uint8Array(96); b[0] = 0xc0; return b; })();
+
+// the caller-side checks of verifyAndAggregateSameMessage's own options
+function checkAggregateOpts(sets, opts) {
+  if (opts.previous != null && opts.previous.length !== 96) throw Error("BLST_ERROR: BLST_INVALID_SIZE");
+  if (opts.take != null && opts.take.length !== sets.length) throw Error("take must have one entry per set");
+}
+
+// take (one byte per set; a plain call adds nothing to an aggregate) and prevSigs
+// (96 B per group) of a merged device call with at least one aggregate call
+function encodeAggregateSide(calls, merged, n) {
+  const take = new Uint8Array(Math.max(n, 1));
+  const prevSigs = new Uint8Array(Math.max(merged.groups.length, 1) * 96);
+  for (let g = 0; g < merged.groups.length; g++) prevSigs.set(G2_IDENTITY_96, 96 * g);
+  calls.forEach((c, k) => {
+    if (!c.agg) return;
+    const [lo, hi] = merged.where[k];
+    for (let i = lo; i < hi; i++) take[i] = c.agg.take == null || c.agg.take[i - lo] ? 1 : 0;
+    if (c.agg.previous != null) prevSigs.set(c.agg.previous, 96 * merged.groupOf[k]);
+  });
+  return {take, prevSigs};
+}
+
+// one call's share of a verifySameMessageAggregate result: booleans for a plain
+// call, {valid, aggregate, count} for an aggregate call, or the Error that
+// rejects it alone (its `previous` did not decode)
+function aggregateCallResult(addonRef, call, res, where, g) {
+  const valid = Array.from(res.valid.subarray(where[0], where[1]), (v) => v === 1);
+  if (!call.agg) return valid;
+  if (res.aggCode[g] !== 0) return Error(`BLST_ERROR: ${addonRef.codeName(res.aggCode[g])}`);
+  return {valid, aggregate: res.aggSigs.slice(96 * g, 96 * g + 96), count: res.aggCount[g]};
 }
 
 // groups [{message, sets: [{publicKey, signature}]}] -> the arrays of include/bgv.h bgv_sm_batch
@@ -512,6 +551,8 @@ function newMetrics() {
     // verifySignatureSetsSameMessage: sets sent to the device, and groups that went to the per-set retry
     lodestar_bls_thread_pool_same_message_sig_sets_started_total: 0,
     lodestar_bls_thread_pool_same_message_retries_total: 0,
+    // verifyAndAggregateSameMessage: signatures added to the callers' aggregates
+    lodestar_bls_thread_pool_same_message_aggregated_sigs_total: 0,
     // verifyAggregateSetsSameMessage: the same two counters for aggregate sets
     lodestar_bls_thread_pool_same_message_agg_sig_sets_started_total: 0,
     lodestar_bls_thread_pool_same_message_agg_retries_total: 0,
@@ -678,9 +719,32 @@ class BlsGpuVerifier {
     if (this.closed) throw new QueueError();
     if (sets.length === 0) return [];
     checkSameMessage(sets, message);
+    return this.queueSameMessage({sets, message, addedTimeMs: Date.now()}, opts.batchable);
+  }
+
+  // verifySignatureSetsSameMessage that also returns what the caller's
+  // pre-aggregation pool would compute next (chain/opPools/attestationPool.ts:182-199,
+  // syncCommitteeMessagePool.ts:139): resolves {valid: boolean[], aggregate:
+  // Uint8Array(96), count} with aggregate = compress(previous + the signatures of
+  // the valid sets whose `take` entry is true).  opts = {batchable, previous?:
+  // Uint8Array(96), take?: boolean[]}.  The call rides the queue and buffer of
+  // verifySignatureSetsSameMessage and always forms its own group of the merged
+  // device call (bgv_verify_same_message_aggregate).  A `previous` that does not
+  // decode rejects this call alone with BLST_ERROR: BLST_<NAME>.
+  async verifyAndAggregateSameMessage(sets, message, opts = {}) {
+    if (this.closed) throw new QueueError();
+    checkAggregateOpts(sets, opts);
+    if (sets.length === 0) return {valid: [], aggregate: Uint8Array.from(opts.previous != null ? opts.previous : G2_IDENTITY_96), count: 0};
+    checkSameMessage(sets, message);
+    const agg = {previous: opts.previous != null ? opts.previous : null, take: opts.take != null ? opts.take : null};
+    return this.queueSameMessage({sets, message, agg, addedTimeMs: Date.now()}, opts.batchable);
+  }
+
+  queueSameMessage(call, batchable) {
     return new Promise((resolve, reject) => {
-      const job = {resolve, reject, sets, message, addedTimeMs: Date.now()};
-      if (opts.batchable) {
+      const job = {...call, resolve, reject};
+      const sets = call.sets;
+      if (batchable) {
         if (!this.smBuffered) this.smBuffered = {jobs: [], sigCount: 0, timeout: setTimeout(this.flushSameMessage, MAX_BUFFER_WAIT_MS)};
         this.smBuffered.jobs.push(job);
         this.smBuffered.sigCount += sets.length;
@@ -715,14 +779,24 @@ class BlsGpuVerifier {
     }
     const m = this.metrics;
     try {
-      const {groups, where} = mergeSameMessage(jobs);
+      const merged = mergeSameMessage(jobs);
+      const {groups, where} = merged;
       const {best} = this.idleContexts();
       this.smDeviceCalls++;
       m.lodestar_bls_thread_pool_same_message_sig_sets_started_total += n;
-      const res = await addon.verifySameMessage(this.ctxs[best >= 0 ? best : 0], encodeSameMessage(groups));
+      const ctx = this.ctxs[best >= 0 ? best : 0];
+      const withAgg = jobs.some((j) => j.agg);
+      const res = withAgg
+        ? await addon.verifySameMessageAggregate(ctx, {...encodeSameMessage(groups), ...encodeAggregateSide(jobs, merged, n)})
+        : await addon.verifySameMessage(ctx, encodeSameMessage(groups));
       m.lodestar_bls_thread_pool_same_message_retries_total += res.groupsRetried;
       m.lodestar_bls_thread_pool_time_seconds_sum += (res.workerEndMs - res.workerStartMs) / 1000;
-      jobs.forEach((job, k) => job.resolve(Array.from(res.valid.subarray(where[k][0], where[k][1]), (v) => v === 1)));
+      jobs.forEach((job, k) => {
+        const r = withAgg ? aggregateCallResult(addon, job, res, where[k], merged.groupOf[k]) : Array.from(res.valid.subarray(where[k][0], where[k][1]), (v) => v === 1);
+        if (r instanceof Error) return job.reject(r);
+        if (job.agg) m.lodestar_bls_thread_pool_same_message_aggregated_sigs_total += r.count;
+        job.resolve(r);
+      });
     } catch (e) {
       for (const job of jobs) job.reject(e);
     }
@@ -1132,6 +1206,21 @@ class BlsGpuSingleThreadVerifier {
     return Array.from(res.valid, (v) => v === 1);
   }
 
+  // verifyAndAggregateSameMessage on the calling thread: one device call, one group
+  async verifyAndAggregateSameMessage(sets, message, opts = {}) {
+    if (this.closed) throw new QueueError();
+    checkAggregateOpts(sets, opts);
+    if (sets.length === 0) return {valid: [], aggregate: Uint8Array.from(opts.previous != null ? opts.previous : G2_IDENTITY_96), count: 0};
+    checkSameMessage(sets, message);
+    const call = {sets, message, agg: {previous: opts.previous != null ? opts.previous : null, take: opts.take != null ? opts.take : null}};
+    const merged = mergeSameMessage([call]);
+    const batch = {...encodeSameMessage(merged.groups), ...encodeAggregateSide([call], merged, sets.length)};
+    const res = addon.verifySameMessageAggregateSync(this.ctx, batch);
+    const r = aggregateCallResult(addon, call, res, merged.where[0], 0);
+    if (r instanceof Error) throw r;
+    return r;
+  }
+
   // verifyAggregateSetsSameMessage on the calling thread: one device call, one group
   async verifyAggregateSetsSameMessage(sets, message) {
     if (this.closed) throw new QueueError();
@@ -1163,6 +1252,6 @@ class BlsGpuSingleThreadVerifier {
 module.exports = {
   addon, BlsGpuVerifier, BlsGpuSingleThreadVerifier, QueueError, sourceHash, checkBuildId, chunkifyMaximizeChunkSize, encodeJobs, checkSets, shardJobs, jobWork,
   encodeJobsBits, hasCommitteeSets, encodeSameMessage, mergeSameMessage, checkSameMessage, encodeSameMessageAgg, checkAggregateSameMessage,
-  encodeSameMessageBits, hasCommitteeKeys,
+  encodeSameMessageBits, hasCommitteeKeys, encodeAggregateSide, G2_IDENTITY_96,
   MAX_BUFFERED_SIGS, MAX_BUFFER_WAIT_MS, MAX_JOBS_CAN_ACCEPT_WORK, SHARD_MIN_SETS, PRIORITY_CUS, RESERVED_CAP, CONTEXTS_PER_DEVICE,
 };

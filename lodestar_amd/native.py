@@ -59,6 +59,7 @@ EXPORTS = [
     "bgv_debug_index_list_sums", "bgv_index_list_sums_ms",
     "bgv_verify_same_message_bits", "bgv_smb_check", "bgv_debug_same_message_bits",
     "bgv_hash_stats", "bgv_miller_path_stats",
+    "bgv_verify_same_message_aggregate", "bgv_sm_agg_check", "bgv_sm_agg_ms",
 ]
 MAX_INDEX_LISTS = 8
 SRC_EXPLICIT = 0xFFFFFFFF
@@ -143,6 +144,12 @@ class BgvSmBatch(ctypes.Structure):
         ("scalars", ctypes.c_void_p),
         ("on_device", ctypes.c_uint32),
     ]
+
+
+class BgvSmAgg(ctypes.Structure):
+    """bgv_sm_agg (include/bgv.h): what bgv_verify_same_message_aggregate takes
+    and returns beside the batch."""
+    _fields_ = [(k, ctypes.c_void_p) for k in ("take", "prev_sig96", "agg_sig96", "agg_count", "agg_code")]
 
 
 class BgvSmaBatch(ctypes.Structure):
@@ -388,6 +395,10 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
             "bgv_smb_check": ([ctypes.POINTER(BgvSmbBatch), P], ctypes.c_int),
             "bgv_debug_same_message_bits": ([P, ctypes.POINTER(BgvSmbBatch), P, P, ctypes.POINTER(BgvSmStats), P, P, P, P, P],
                                             ctypes.c_int),
+            "bgv_verify_same_message_aggregate": ([P, ctypes.POINTER(BgvSmBatch), ctypes.POINTER(BgvSmAgg), P, P,
+                                                   ctypes.POINTER(BgvSmStats)], ctypes.c_int),
+            "bgv_sm_agg_check": ([ctypes.POINTER(BgvSmBatch), ctypes.POINTER(BgvSmAgg)], ctypes.c_int),
+            "bgv_sm_agg_ms": ([P, ctypes.POINTER(ctypes.c_float)], ctypes.c_int),
         }
         for name, (args, res) in sig.items():
             fn = getattr(lib, name)
@@ -431,6 +442,22 @@ def _sync_producers(*objs) -> None:
             seen.add(key)
             import torch
             torch.cuda.current_stream(dev).synchronize()
+
+
+# the compressed identity of G2: "no running aggregate" as prev, and the aggregate of no set
+G2_IDENTITY_96 = bytes([0xC0]) + bytes(95)
+
+
+def sm_agg_check(arrays: dict, take=None, prev=None, on_device: bool = False, agg_sig=True) -> tuple[int, str]:
+    """bgv_sm_agg_check: the host-side contract of bgv_verify_same_message_aggregate,
+    without a device.  agg_sig=False passes a NULL output.  (status, bgv_last_error()
+    text); the text is empty for BGV_OK."""
+    lib = load_library()
+    b = Device.make_sm_batch(arrays, on_device, sync_inputs=False)
+    out = np.zeros((max(b.n_groups, 1), 96), np.uint8)
+    a = BgvSmAgg(take=_ptr(take), prev_sig96=_ptr(prev), agg_sig96=out.ctypes.data if agg_sig else None)
+    st = lib.bgv_sm_agg_check(ctypes.byref(b), ctypes.byref(a))
+    return st, ("" if st == BGV_OK else lib.bgv_last_error().decode())
 
 
 def sma_check(arrays: dict, on_device: bool = False) -> tuple[int, str]:
@@ -669,6 +696,40 @@ class Device:
         self._check(self.lib.bgv_verify_same_message(self.h, ctypes.byref(b), ok.ctypes.data, sc.ctypes.data,
                                                      ctypes.byref(self.last_sm_stats)))
         return ok[: b.n_sets].astype(bool), sc[: b.n_sets]
+
+    def verify_same_message_aggregate(self, arrays: dict, take=None, prev=None, on_device: bool = False,
+                                      sync_inputs: bool = True) -> dict:
+        """bgv_verify_same_message_aggregate: the verdicts of verify_same_message plus,
+        per group, the compressed sum of prev and the signatures of its sets with
+        set_valid = 1 and take != 0.  take: uint8[n_sets] or None (every set); prev:
+        uint8[n_groups, 96] or None; both device tensors for an on_device batch.
+        Returns set_valid, set_code, agg_sig (G, 96) uint8, agg_count, agg_code, stats."""
+        b = self.make_sm_batch(arrays, on_device, sync_inputs)
+        if not on_device:
+            take = None if take is None else np.ascontiguousarray(take, np.uint8)
+            prev = None if prev is None else np.ascontiguousarray(prev, np.uint8)
+        elif sync_inputs:
+            _sync_producers(take, prev)
+        n, G = b.n_sets, b.n_groups
+        ok = np.zeros(max(n, 1), dtype=np.uint8)
+        sc = np.zeros(max(n, 1), dtype=np.int32)
+        sig = np.zeros((max(G, 1), 96), np.uint8)
+        cnt = np.zeros(max(G, 1), np.uint32)
+        code = np.zeros(max(G, 1), np.int32)
+        a = BgvSmAgg(take=_ptr(take), prev_sig96=_ptr(prev), agg_sig96=sig.ctypes.data, agg_count=cnt.ctypes.data,
+                     agg_code=code.ctypes.data)
+        self.last_sm_stats = BgvSmStats()
+        self._check(self.lib.bgv_verify_same_message_aggregate(self.h, ctypes.byref(b), ctypes.byref(a), ok.ctypes.data,
+                                                               sc.ctypes.data, ctypes.byref(self.last_sm_stats)))
+        return {"set_valid": ok[:n].astype(bool), "set_code": sc[:n], "agg_sig": sig[:G], "agg_count": cnt[:G],
+                "agg_code": code[:G], "stats": self.last_sm_stats.as_dict()}
+
+    def sm_agg_ms(self) -> float:
+        """bgv_sm_agg_ms: device time of the two sum kernels in the first pass of the last
+        verify_same_message_aggregate"""
+        ms = ctypes.c_float(0.0)
+        self._check(self.lib.bgv_sm_agg_ms(self.h, ctypes.byref(ms)))
+        return float(ms.value)
 
     def debug_same_message(self, arrays: dict, on_device: bool = False) -> dict:
         """bgv_debug_same_message (test only): the verdicts plus P_g, S_g and H(m_g) per group"""

@@ -482,35 +482,68 @@ def encode_same_message(groups, scalars: np.ndarray | None = None) -> dict:
     }
 
 
-def merge_same_message(calls):
-    """Merge calls [(sets, message), ...] into the groups of ONE device call:
-    one group per call, and calls whose messages are byte-equal share a group
-    (in order of first appearance).  Returns (groups, where) with where[k] the
-    slice of the flattened sets that belongs to call k."""
-    order: list[bytes] = []
-    members: dict[bytes, list[int]] = {}
-    for k, (_sets, message) in enumerate(calls):
-        m = bytes(message)
-        if m not in members:
-            members[m] = []
-            order.append(m)
-        members[m].append(k)
+@dataclass(frozen=True)
+class AggregateRequest:
+    """What a verify_and_aggregate_same_message call adds to its sets: the
+    pool's running aggregate (96 compressed bytes, None = none) and, per set,
+    whether a valid set enters the aggregate (None = every set)."""
+
+    previous: bytes | None = None
+    take: tuple | None = None
+
+
+@dataclass
+class SameMessageAggregate:
+    """Result of verify_and_aggregate_same_message: one boolean per set, the
+    compressed sum of `previous` and the valid, taken signatures, and how many
+    signatures were added."""
+
+    valid: list
+    aggregate: bytes
+    count: int
+
+
+def merge_same_message_groups(calls):
+    """Merge calls [(sets, message[, AggregateRequest]), ...] into the groups of
+    ONE device call: one group per call, and plain calls whose messages are
+    byte-equal share a group (in order of first appearance).  A call with an
+    AggregateRequest ALWAYS forms its own group: its aggregate is per call.
+    Returns (groups, where, group_of) with where[k] the slice of the flattened
+    sets that belongs to call k and group_of[k] the group of call k."""
+    order: list = []  # a message (shared group), or the number of an aggregate call
+    members: dict = {}
+    for k, call in enumerate(calls):
+        key = bytes(call[1]) if len(call) < 3 or call[2] is None else k
+        if key not in members:
+            members[key] = []
+            order.append(key)
+        members[key].append(k)
     groups = []
     where: list = [None] * len(calls)
+    group_of: list = [None] * len(calls)
     pos = 0
-    for m in order:
+    for key in order:
         sets = []
-        for k in members[m]:
+        for k in members[key]:
             where[k] = slice(pos, pos + len(calls[k][0]))
+            group_of[k] = len(groups)
             pos += len(calls[k][0])
             sets.extend(calls[k][0])
-        groups.append((m, sets))
+        groups.append((bytes(calls[members[key][0]][1]), sets))
+    return groups, where, group_of
+
+
+def merge_same_message(calls):
+    """merge_same_message_groups without the group numbers: (groups, where)"""
+    groups, where, _ = merge_same_message_groups(calls)
     return groups, where
 
 
 def run_same_message_calls(device, calls, scalars_for=None, metrics: dict | None = None) -> list:
     """One device call (Device.verify_same_message) for the merged calls;
     returns list[bool] per call."""
+    if any(len(c) > 2 and c[2] is not None for c in calls):
+        return run_same_message_aggregate_calls(device, calls, scalars_for, metrics)
     groups, where = merge_same_message(calls)
     n = sum(len(g[1]) for g in groups)
     arrays = encode_same_message(groups, scalars_for(n) if scalars_for else None)
@@ -523,12 +556,61 @@ def run_same_message_calls(device, calls, scalars_for=None, metrics: dict | None
     return [ok[w] for w in where]
 
 
+def check_aggregate_request(sets, agg: AggregateRequest) -> None:
+    """Caller-side checks of verify_and_aggregate_same_message's own arguments"""
+    if agg.previous is not None and len(agg.previous) != 96:
+        raise BlsError("BLST_ERROR: BLST_INVALID_SIZE", 8)
+    if agg.take is not None and len(agg.take) != len(sets):
+        raise BlsError("take must have one entry per set")
+
+
+def run_same_message_aggregate_calls(device, calls, scalars_for=None, metrics: dict | None = None) -> list:
+    """One device call (Device.verify_same_message_aggregate) for merged calls of
+    which at least one asks for its aggregate.  Per call: list[bool], or for a
+    call with an AggregateRequest a SameMessageAggregate, or a BlsError (returned,
+    not raised: it rejects that call alone) when its `previous` did not decode."""
+    groups, where, group_of = merge_same_message_groups(calls)
+    n = sum(len(g[1]) for g in groups)
+    arrays = encode_same_message(groups, scalars_for(n) if scalars_for else None)
+    take = np.zeros(max(n, 1), dtype=np.uint8)  # plain calls: nothing to aggregate
+    prev = np.tile(np.frombuffer(IDENTITY_SIG_96, dtype=np.uint8), (max(len(groups), 1), 1))
+    for k, call in enumerate(calls):
+        agg = call[2] if len(call) > 2 else None
+        if agg is None:
+            continue
+        take[where[k]] = 1 if agg.take is None else np.array([1 if t else 0 for t in agg.take], dtype=np.uint8)
+        if agg.previous is not None:
+            prev[group_of[k]] = np.frombuffer(bytes(agg.previous), dtype=np.uint8)
+    out = device.verify_same_message_aggregate(arrays, take=take, prev=prev)
+    ok = [bool(x) for x in out["set_valid"]]
+    res = []
+    added = 0
+    for k, call in enumerate(calls):
+        if len(call) < 3 or call[2] is None:
+            res.append(ok[where[k]])
+            continue
+        g = group_of[k]
+        code = int(out["agg_code"][g])
+        if code != 0:
+            res.append(error_for_code(code))
+            continue
+        added += int(out["agg_count"][g])
+        res.append(SameMessageAggregate(ok[where[k]], out["agg_sig"][g].tobytes(), int(out["agg_count"][g])))
+    if metrics is not None:
+        st = getattr(device, "last_sm_stats", None)
+        metrics["same_message_sets_started"] = metrics.get("same_message_sets_started", 0) + n
+        metrics["same_message_retries"] = metrics.get("same_message_retries", 0) + (int(st.groups_retried) if st is not None else 0)
+        metrics["same_message_aggregated_sigs"] = metrics.get("same_message_aggregated_sigs", 0) + added
+    return res
+
+
 @dataclass
 class _SmJob:
     sets: list
     message: bytes
     future: asyncio.Future
     added: float
+    agg: AggregateRequest | None = None  # verify_and_aggregate_same_message
 
 
 class SameMessageQueue:
@@ -557,11 +639,11 @@ class SameMessageQueue:
     def pending_sets(self) -> int:
         return sum(len(j.sets) for j in self._jobs + self._buffered)
 
-    async def submit(self, sets, message: bytes, batchable: bool) -> list:
+    async def submit(self, sets, message: bytes, batchable: bool, agg: AggregateRequest | None = None):
         if self._closed:
             raise QueueError(QueueErrorCode.QUEUE_ABORTED)
         loop = asyncio.get_running_loop()
-        job = _SmJob(list(sets), bytes(message), loop.create_future(), time.monotonic())
+        job = _SmJob(list(sets), bytes(message), loop.create_future(), time.monotonic(), agg)
         if batchable:
             if not self._buffered:
                 self._handle = loop.call_later(MAX_BUFFER_WAIT_MS / 1000, self._flush)
@@ -597,9 +679,14 @@ class SameMessageQueue:
         loop = asyncio.get_running_loop()
         try:
             self.device_calls += 1
-            res = await loop.run_in_executor(self._executor, self._run_merged, [(j.sets, j.message) for j in jobs])
+            calls = [(j.sets, j.message) if j.agg is None else (j.sets, j.message, j.agg) for j in jobs]
+            res = await loop.run_in_executor(self._executor, self._run_merged, calls)
             for j, r in zip(jobs, res):
-                if not j.future.done():
+                if j.future.done():
+                    continue
+                if isinstance(r, Exception):  # rejects this call alone (a `previous` that does not decode)
+                    j.future.set_exception(r)
+                else:
                     j.future.set_result(r)
         except Exception as e:  # noqa: BLE001 -- a device error rejects the merged calls
             for j in jobs:
@@ -940,6 +1027,28 @@ class BlsGpuVerifier:
         if self._closed:
             raise QueueError(QueueErrorCode.QUEUE_ABORTED)
         return await self._sm.submit(sets, message, opts.batchable)
+
+    async def verify_and_aggregate_same_message(self, sets, message: bytes, opts: VerifySignatureOpts | None = None,
+                                                previous: bytes | None = None, take=None) -> SameMessageAggregate:
+        """verify_signature_sets_same_message that also returns what the caller's
+        pre-aggregation pool would compute next (chain/opPools/
+        attestationPool.ts:182-199, syncCommitteeMessagePool.ts:139): the
+        compressed sum of `previous` (the pool's running aggregate, 96 bytes) and
+        the signatures of the valid sets whose `take` entry is true (None: all).
+        The call rides the queue and buffer of verify_signature_sets_same_message
+        and always forms its own group of the merged device call
+        (bgv_verify_same_message_aggregate).  A `previous` that does not decode
+        rejects this call alone with BLST_ERROR: BLST_<NAME>."""
+        opts = opts or VerifySignatureOpts()
+        sets = list(sets)
+        agg = AggregateRequest(None if previous is None else bytes(previous), None if take is None else tuple(bool(t) for t in take))
+        check_aggregate_request(sets, agg)
+        if not sets:  # no device call: nothing is added, `previous` comes back as it is
+            return SameMessageAggregate([], agg.previous or IDENTITY_SIG_96, 0)
+        check_same_message(sets, message)
+        if self._closed:
+            raise QueueError(QueueErrorCode.QUEUE_ABORTED)
+        return await self._sm.submit(sets, message, opts.batchable, agg)
 
     async def verify_aggregate_sets_same_message(self, sets, message: bytes, opts: VerifySignatureOpts | None = None) -> list:
         """verifySignatureSetsSameMessage for aggregate sets: `sets` is a list of
@@ -1346,6 +1455,20 @@ class BlsGpuSingleThreadVerifier:
         check_same_message(sets, message)
         return run_same_message_calls(self.device, [(sets, message)], None, self.metrics)[0]
 
+    async def verify_and_aggregate_same_message(self, sets, message: bytes, opts: VerifySignatureOpts | None = None,
+                                                previous: bytes | None = None, take=None) -> SameMessageAggregate:
+        """verify_and_aggregate_same_message in the calling thread: one device call, one group"""
+        sets = list(sets)
+        agg = AggregateRequest(None if previous is None else bytes(previous), None if take is None else tuple(bool(t) for t in take))
+        check_aggregate_request(sets, agg)
+        if not sets:  # no device call: nothing is added, `previous` comes back as it is
+            return SameMessageAggregate([], agg.previous or IDENTITY_SIG_96, 0)
+        check_same_message(sets, message)
+        r = run_same_message_calls(self.device, [(sets, message, agg)], None, self.metrics)[0]
+        if isinstance(r, Exception):
+            raise r
+        return r
+
     async def verify_aggregate_sets_same_message(self, sets, message: bytes, opts: VerifySignatureOpts | None = None) -> list:
         """verify_aggregate_sets_same_message in the calling thread: one device call, one group"""
         if self._closed:
@@ -1437,6 +1560,7 @@ def _new_metrics() -> dict:
         "job_wait_time_s": [],
         "same_message_sets_started": 0,
         "same_message_retries": 0,
+        "same_message_aggregated_sigs": 0,
         "same_message_agg_sets_started": 0,
         "same_message_agg_retries": 0,
     }

@@ -649,6 +649,77 @@ typedef struct bgv_miller_path {
   uint32_t steps, slice_sets, items;
 } bgv_miller_path;
 int bgv_miller_path_stats(bgv_ctx* ctx, bgv_miller_path* out);
+/* One Miller pair per distinct signing root of a job (opt-in, off by default;
+ * DESIGN.md section 3i).  A job's verdict is the AND of its sets, and only the
+ * job's product is ever read (the whole-batch check, the per-job retry,
+ * bgv_partial), so with merging on the sets of a job that carry the same root
+ * m pair once, as (sum_i r_i PK_i, H(m)) over the already scaled keys, where
+ * they paired once each.  Classes never span jobs: the same root in two jobs
+ * gives two pairs.  The caller groups nothing; job_result, set_code and every
+ * bgv_stats counter are those of the unmerged run.  Signature decoding and
+ * subgroup checks, the per-set gather and scaling, S_job and its (-G1, S_job)
+ * pair, the folds, the final exponentiations and the per-job retry are
+ * unchanged; the fixed-argument lines are computed and stored once per class.
+ *
+ * Where it applies: bgv_verify, bgv_verify_bits and bgv_partial (with
+ * bgv_partial_finish) on a batch that runs the bulk layout (bgv_stats.split ==
+ * 0) with the one-lane set-pair loop (bgv_stats.miller_lanes == 1): its item
+ * loop at 1, 2 or 4 pairs per item, with or without lines, and the per-step
+ * line products (bgv_cfg.miller_steps).  Every other layout (latency mode, the
+ * two-, four- and many-lane loops) runs unmerged and reports merged = 0.  The
+ * same-message entries already pay one pair per segment: they never merge and
+ * leave zeros below.  bgv_debug_stages stays the per-set plan.  Merging implies
+ * the root classes of bgv_cfg.hash_dedup for that batch, whatever the field
+ * says (bgv_hash_stats reports dedup = 1).
+ *
+ * With merging on, bgv_partial's 576 bytes may differ from the unmerged bytes
+ * (Miller values are not canonical: the product of two pairs' values and the
+ * value of the summed pair differ by a factor the final exponentiation kills);
+ * the verdict after bgv_combine_final does not.
+ *
+ * Fallback: a class whose keys sum to the identity (reachable only with
+ * injected scalars, e.g. a key beside its negation with equal scalars) has the
+ * pair value 1, which the item loop cannot tell from a rejected pair.  A device
+ * flag comes home with the results the call copies anyway; when it is set the
+ * call discards the pass, runs the batch again unmerged before it returns and
+ * reports fallback = 1, merged = 0.  Results never depend on the switch.
+ *
+ * When it pays (one MI355X, the 100,352-set range-sync segment, 784 jobs of
+ * 128, consecutive sets of a block sharing a root in runs of g;
+ * tools/bench_pair_merge.py, profiles/pair_merge.json, DESIGN.md section 3i;
+ * against hash_dedup = 0 / against hash_dedup = 1):
+ *   g = 2 (half of the pairs merged)      lone 35.2 -> 30.5 ms (4.7 / 3.6 ms gained),
+ *                                         three in flight 30.9 -> 26.2 ms per batch (4.7 / 4.2)
+ *   g = 4 (three quarters merged)         lone 35.3 -> 26.4 ms (8.9 / 5.7),
+ *                                         three in flight 30.8 -> 20.8 ms per batch (10.0 / 7.4)
+ *   g = 1 (every root distinct)           lone inside the spread (35.1 against 35.2 ms); three in flight
+ *                                         2.6 ms per batch SLOWER than hash_dedup = 0 (33.4 against 30.8),
+ *                                         the cost hash_dedup = 1 has there too (33.4): the class set-up
+ *                                         queues behind the other batches' waves
+ * so a caller whose jobs repeat roots opts in, and one whose roots are all
+ * distinct keeps it off.  The default stays off; there is no auto rule yet.
+ *
+ * mode: 0 off (default), 1 on; any other value BGV_E_INVALID_ARG.  Takes
+ * effect from the next call on the context. */
+int bgv_pair_merge(bgv_ctx* ctx, int32_t mode);
+/* The set-pair part of the Miller stage of the last bgv_verify, bgv_verify_bits
+ * or bgv_partial on the context: sets the batch's sets, pairs the set pairs it
+ * ran (the classes when merged = 1, else sets), fallback 1 when a merged pass
+ * was discarded.  Zeros after any other entry.  The class count comes home with
+ * the call's results (no synchronise of its own). */
+typedef struct bgv_pair_path {
+  uint32_t sets, pairs, merged, fallback;
+} bgv_pair_path;
+int bgv_pair_stats(bgv_ctx* ctx, bgv_pair_path* out);
+/* test-only: bgv_verify through the merged path (whatever bgv_pair_merge says;
+ * BGV_E_STATE when the batch's layout does not merge) plus cls[n_sets] (class
+ * index of every set), class_off[n_jobs + 1], p_class96[n_sets][96] (P_c affine
+ * in bgv_debug's layout, all-zero for the identity or a rejected member; the
+ * first class_off[n_jobs] rows), job_fe[n_jobs][576], batch_fe[576] (final
+ * exponentiations of the job products and of the batch product, as
+ * bgv_debug).  Any output may be NULL.  bgv_pair_stats reports the call. */
+int bgv_debug_pair_classes(bgv_ctx* ctx, const bgv_batch* batch, int32_t* job_result, int32_t* set_code, uint32_t* cls,
+                           uint32_t* class_off, uint8_t* p_class96, uint8_t* job_fe, uint8_t* batch_fe);
 /* Host-only plan (no device, no context): bgv_bits_check's checks, then the
  * rule against list_has_sums[BGV_MAX_INDEX_LISTS] (NULL: no list has sums).
  * path[i] = 1 for a complement set (path may be NULL); *keys_gathered the keys

@@ -21,6 +21,7 @@
 #include "bgv_internal.h"
 #include "msm_g1.h"
 #include "sig_agg.h"
+#include "pair_merge.h"
 #include "../../include/bgv.h"
 
 using namespace bgv;
@@ -172,6 +173,19 @@ struct bgv_ctx {
   msg_classes mc = {};                // the batch's view of them (work_alloc); n_sets == 0: no class pass
   bgv_hash_path hash_path = {};       // bgv_hash_stats
   bool hash_pending = false;          // hash_path.hashes is still the device's n_uniq: fetched with the results
+  // pair classes of a bulk batch (bgv_pair_merge, bgv_pair_merge.hip)
+  int32_t pair_merge = 0;             // the switch
+  bool pm_entry = false;              // inside bgv_verify / bgv_verify_bits / bgv_partial: run_stages records pair_path
+  bool pm_call = false;               // ... and the call may merge (off for the unmerged second pass of a fallback)
+  dbuf<uint64_t> pm_tab;
+  dbuf<uint32_t> pm_slot, pm_slot_idx, pm_off, pm_cls, pm_head, pm_next, pm_job, pm_rep, pm_item_off, pm_item_job;
+  dbuf<g1a> pm_p;
+  dbuf<int32_t> pm_code;
+  dbuf<g2a> pm_h;
+  pair_classes pc = {};               // the batch's view of them (work_alloc); n_sets == 0: no class pass
+  bgv_pair_path pair_path = {};       // bgv_pair_stats
+  bool pair_pending = false;          // pair_path.pairs and the identity flag are still on the device
+  bool pair_redo = false;             // the last merged pass met an identity class: its results are void
   // microbench scratch
   dbuf<fp_t> mb_fp;
   dbuf<uint64_t> mb_u64;
@@ -351,6 +365,9 @@ int bgv_close(bgv_ctx* c) {
     if (l) (void)hipFree(l);
   c->bits_off.release(); c->bits_idx.release(); c->bits_win.release();
   c->msg_rep.release(); c->msg_uniq.release(); c->msg_tab.release(); c->msg_cnt.release();
+  c->pm_tab.release(); c->pm_slot.release(); c->pm_slot_idx.release(); c->pm_off.release(); c->pm_cls.release();
+  c->pm_head.release(); c->pm_next.release(); c->pm_job.release(); c->pm_rep.release(); c->pm_item_off.release();
+  c->pm_item_job.release(); c->pm_p.release(); c->pm_code.release(); c->pm_h.release();
   if (c->pin_in) (void)hipHostFree(c->pin_in);
   if (c->pin_out) (void)hipHostFree(c->pin_out);
   if (c->table) (void)hipFree(c->table);
@@ -887,8 +904,15 @@ static int work_alloc_once(bgv_ctx* c, const dev_batch& d, dev_work& w);
 // repeated it gains 1.4 ms alone and 0.75 ms in flight, with three quarters
 // 4.5 and 3.4 ms.
 // The table's slot count is a uint32_t power of two >= 2 n_sets.
-static bool hash_dedup_on(const bgv_cfg& k, const dev_batch& d) {
-  return !d.split && k.hash_dedup == 1 && d.n_sets > 0 && d.n_sets <= (1u << 30);
+// Pair classes (bgv_pair_merge): the bulk layout's one-lane set-pair loop only,
+// and only inside the three entries whose callers can take the fallback.
+static bool pair_merge_on(const bgv_ctx* c, const dev_batch& d) {
+  return c->pm_call && !d.split && !d.miller_coop && !d.miller_kv && !d.steps_dbg && d.pairs_per_item >= 1 && d.n_jobs > 0 &&
+         d.n_sets > 0 && d.n_sets <= (1u << 30);
+}
+// (merging needs the root representatives, so it implies the class pass)
+static bool hash_dedup_on(const bgv_ctx* c, const dev_batch& d) {
+  return !d.split && (c->cfg.hash_dedup == 1 || pair_merge_on(c, d)) && d.n_sets > 0 && d.n_sets <= (1u << 30);
 }
 
 // a kept line buffer the batch does not use gives way under memory pressure
@@ -955,7 +979,7 @@ static int work_alloc_once(bgv_ctx* c, const dev_batch& d, dev_work& w) {
   }
   // message classes (bgv_dedup.hip): sized with the batch's other buffers, never inside a run
   c->mc = {};
-  if (hash_dedup_on(c->cfg, d)) {
+  if (hash_dedup_on(c, d)) {
     size_t slots = 64;
     while (slots < 2 * ns) slots *= 2;
     if ((r = c->msg_rep.ensure(ns)) || (r = c->msg_uniq.ensure(ns)) || (r = c->msg_tab.ensure(slots)) || (r = c->msg_cnt.ensure(1)))
@@ -965,6 +989,28 @@ static int work_alloc_once(bgv_ctx* c, const dev_batch& d, dev_work& w) {
     c->mc.msgs = d.msgs;
     c->mc.table = c->msg_tab.p; c->mc.rep = c->msg_rep.p; c->mc.uniq = c->msg_uniq.p; c->mc.n_uniq = c->msg_cnt.p;
     c->mc.h_aff = w.h_aff;
+  }
+  // pair classes (bgv_pair_merge.hip): likewise, and only when merging is on
+  c->pc = {};
+  if (pair_merge_on(c, d)) {
+    size_t slots = 64;
+    while (slots < 2 * ns) slots *= 2;
+    if ((r = c->pm_tab.ensure(slots)) || (r = c->pm_slot_idx.ensure(slots)) || (r = c->pm_slot.ensure(ns)) ||
+        (r = c->pm_off.ensure(nj + 1)) || (r = c->pm_cls.ensure(ns)) || (r = c->pm_head.ensure(ns)) ||
+        (r = c->pm_next.ensure(ns)) || (r = c->pm_job.ensure(ns)) || (r = c->pm_rep.ensure(ns)) ||
+        (r = c->pm_item_off.ensure(nj + 1)) || (r = c->pm_item_job.ensure(ns + nj + 1)) || (r = c->pm_p.ensure(ns)) ||
+        (r = c->pm_code.ensure(ns)) || (r = c->pm_h.ensure(ns)))
+      return r;
+    pair_classes& p = c->pc;
+    p.n_sets = n; p.n_jobs = J;
+    p.mask = (uint32_t)(slots - 1);
+    p.per = d.steps_slice ? d.steps_slice : d.pairs_per_item;
+    p.job_off = d.job_off; p.rep = c->msg_rep.p;
+    p.table = c->pm_tab.p; p.slot = c->pm_slot.p; p.slot_idx = c->pm_slot_idx.p; p.class_off = c->pm_off.p;
+    p.cls = c->pm_cls.p; p.head = c->pm_head.p; p.next = c->pm_next.p; p.cls_job = c->pm_job.p; p.cls_rep = c->pm_rep.p;
+    p.item_off = c->pm_item_off.p; p.item_job = c->pm_item_job.p;
+    p.p_cls = c->pm_p.p; p.code_cls = c->pm_code.p; p.h_cls = c->pm_h.p;
+    p.ident = c->flags.p + 1;
   }
   w.msm_bucket = nullptr; w.msm_mask = nullptr; w.msm_win = nullptr;
   if (d.msm == 2) {
@@ -1009,17 +1055,34 @@ static int run_stages(bgv_ctx* c, const dev_batch& d, const dev_work& w, int fro
   // order tried (profiles/r05m_bulk_stage_order.txt)
   const bool early_hash = fork && d.split && from <= ST_HASH && to > ST_HASH;
   const bool hashes = from <= ST_HASH && to > ST_HASH;
-  const bool classes = hashes && c->mc.n_sets == d.n_sets && hash_dedup_on(c->cfg, d);
+  const bool classes = hashes && c->mc.n_sets == d.n_sets && hash_dedup_on(c, d);
   if (hashes) {
     c->hash_path = {d.n_sets, d.n_sets, classes ? 1u : 0u};
     c->hash_pending = classes;  // hashes = n_uniq, home with the results (finish_results, bgv_partial)
+  }
+  // pair classes: the set-pair kernels and the per-job fold run over a view
+  // whose sets are the classes (bgv_pair_merge.hip); n_sets, lines, f_set and
+  // f_step stay the real ones, every other stage sees the real batch
+  const bool merge = fork && from == 0 && classes && c->pc.n_sets == d.n_sets && pair_merge_on(c, d);
+  dev_batch dv = d;
+  dev_work wv = w;
+  if (merge) {
+    dv.job_off = c->pc.class_off;
+    wv.rpk_aff = c->pc.p_cls; wv.pk_code = c->pc.code_cls; wv.h_aff = c->pc.h_cls;
+    wv.set_job = c->pc.cls_job; wv.item_off = c->pc.item_off; wv.item_job = c->pc.item_job;
+  }
+  if (c->pm_entry && from <= ST_MILLER && to > ST_MILLER) {
+    c->pair_path = {d.n_sets, d.n_sets, merge ? 1u : 0u, 0u};
+    c->pair_pending = merge;  // pairs = the class count, home with the results
+    c->pair_redo = false;
   }
   auto launch_one = [&](int s) -> int {
     hipStream_t st = c->st;
     // fixed-argument lines: right behind the hash on its stream, before the
     // Miller stage waits for the pubkeys (timed in neither stage)
     if (s == ST_MILLER && d.lines) {
-      launch_lines(fork ? c->st_hash : c->st, d, w);  // bgv_miller.hip
+      if (merge) launch_pair_lines(fork ? c->st_hash : c->st, c->pc, w.lines);  // one lane per class
+      else launch_lines(fork ? c->st_hash : c->st, d, w);  // bgv_miller.hip
       HIPCHK(hipGetLastError());
     }
     if (fork) {
@@ -1038,7 +1101,11 @@ static int run_stages(bgv_ctx* c, const dev_batch& d, const dev_work& w, int fro
       launch_sig_fixup(st, d, w);
     }
     if (s == ST_HASH && classes) launch_hash_classes(st, c->mc);  // bgv_dedup.hip: the representatives, then the copies
+    else if (merge && (s == ST_MILLER || s == ST_F_TREE)) launch_stage(st, s, dv, wv);
     else launch_stage(st, s, d, w);
+    if (merge && s == ST_HASH) launch_pair_h(st, c->pc, w.h_aff);  // H(m) per class, for the class lines / the loops
+    // P_c per class, in front of whatever waits for the scaled keys
+    if (merge && s == ST_PK_SCALE) launch_pair_sum(st, c->pc, w.rpk_aff, w.pk_code);
     HIPCHK(hipGetLastError());
     if (timed) HIPCHK(hipEventRecord(c->ev_end[s], st));
     else if (fork && (s == ST_PK_SCALE || s == ST_HASH || s == ST_MILLER)) HIPCHK(hipEventRecord(c->ev_dep[s], st));
@@ -1083,6 +1150,19 @@ static int run_stages(bgv_ctx* c, const dev_batch& d, const dev_work& w, int fro
     launch_msg_dedup(c->st, c->mc);
     HIPCHK(hipGetLastError());
   }
+  // the pair classes follow the root classes they are built from, in the same place (on the hash stream behind
+  // ev_prep they measured the same with three batches in flight)
+  if (merge) {
+    const pair_classes& p = c->pc;
+    random_bytes(&c->pc.key, sizeof c->pc.key);
+    HIPCHK(hipMemsetAsync(p.table, 0xff, ((size_t)p.mask + 1) * 8, c->st));
+    HIPCHK(hipMemsetAsync(p.head, 0xff, (size_t)p.n_sets * 4, c->st));
+    HIPCHK(hipMemsetAsync(p.class_off, 0, ((size_t)p.n_jobs + 1) * 4, c->st));
+    HIPCHK(hipMemsetAsync(p.cls_job, 0, (size_t)p.n_sets * 4, c->st));  // the dead tail names job 0 (k_f_level)
+    HIPCHK(hipMemsetAsync(p.ident, 0, 4, c->st));
+    launch_pair_classes(c->st, c->pc);
+    HIPCHK(hipGetLastError());
+  }
   if (fork) {
     HIPCHK(hipEventRecord(c->ev_prep, c->st));
     if (!early_hash) HIPCHK(hipStreamWaitEvent(c->st_hash, c->ev_prep, 0));
@@ -1118,10 +1198,22 @@ static int finish_results(bgv_ctx* c, const dev_batch& d, const dev_work& w, int
   HIPCHK(hipMemcpyAsync(c->pin_out, w.flags, 4, hipMemcpyDeviceToHost, c->st));
   const bool want_uniq = c->hash_pending;  // the class count of this run rides along (written before ev_prep on c->st)
   if (want_uniq) HIPCHK(hipMemcpyAsync(c->pin_out + 64, c->mc.n_uniq, 4, hipMemcpyDeviceToHost, c->st));
+  const bool want_pair = c->pair_pending;  // the class count and the identity flag of this run ride along too
+  if (want_pair) {
+    HIPCHK(hipMemcpyAsync(c->pin_out + 68, c->pc.class_off + c->pc.n_jobs, 4, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(hipMemcpyAsync(c->pin_out + 72, c->pc.ident, 4, hipMemcpyDeviceToHost, c->st));
+  }
   HIPCHK(hipStreamSynchronize(c->st));
   c->staged_pending = false;
   uint32_t flag = 0;
   memcpy(&flag, c->pin_out, 4);
+  if (want_pair) {
+    uint32_t ident = 0;
+    memcpy(&c->pair_path.pairs, c->pin_out + 68, 4);
+    memcpy(&ident, c->pin_out + 72, 4);
+    c->pair_redo = ident != 0;
+    c->pair_pending = false;
+  }
   if (want_uniq) {
     memcpy(&c->hash_path.hashes, c->pin_out + 64, 4);
     c->hash_pending = false;
@@ -1160,17 +1252,63 @@ int bgv_last_stats(bgv_ctx* c, bgv_stats* stats) {
   return BGV_OK;
 }
 
+// The entries that may merge pairs (bgv_pair_merge): run_stages records
+// bgv_pair_stats only inside one of them, and merges only while pm_call is set.
+struct pair_entry {
+  bgv_ctx* c;
+  pair_entry(bgv_ctx* c_, bool may_merge) : c(c_) {
+    c->pm_entry = true;
+    c->pm_call = may_merge;
+    c->pair_path = {};
+    c->pair_pending = c->pair_redo = false;
+  }
+  ~pair_entry() { c->pm_entry = c->pm_call = false; }
+};
+
+// the whole pipeline and its results; a merged pass that met an identity class
+// is discarded and the batch runs again unmerged (its inputs are still resident)
+static int run_and_finish(bgv_ctx* c, const dev_batch& d, const dev_work& w, int32_t* job_result, int32_t* set_code,
+                          bgv_stats* stats) {
+  if (int r = run_stages(c, d, w, 0, ST_COUNT)) return r;
+  if (int r = finish_results(c, d, w, job_result, set_code, stats)) return r;
+  if (!c->pair_redo) return 0;
+  c->pm_call = false;
+  if (int r = run_stages(c, d, w, 0, ST_COUNT)) return r;
+  if (int r = finish_results(c, d, w, job_result, set_code, stats)) return r;
+  c->pair_path.fallback = 1;
+  return 0;
+}
+
 int bgv_verify(bgv_ctx* c, const bgv_batch* b, int32_t* job_result, int32_t* set_code, bgv_stats* stats) {
   if (!c || !b || (!job_result && b->n_jobs)) return fail(BGV_E_INVALID_ARG, "null argument");
   c->partial_pending = false;
   HIPCHK(hipSetDevice(c->device));
   active_guard ag(c->device);
+  pair_entry pe(c, c->pair_merge != 0);
   dev_batch d;
   if (int r = prepare(c, b, d, true)) return r;
   dev_work w;
   if (int r = work_alloc(c, d, w)) return r;
-  if (int r = run_stages(c, d, w, 0, ST_COUNT)) return r;
-  return finish_results(c, d, w, job_result, set_code, stats);
+  return run_and_finish(c, d, w, job_result, set_code, stats);
+}
+
+int bgv_pair_merge(bgv_ctx* c, int32_t mode) {
+  if (!c) return fail(BGV_E_INVALID_ARG, "null ctx");
+  if (mode != 0 && mode != 1) return fail(BGV_E_INVALID_ARG, "bgv_pair_merge mode %d", mode);
+  c->pair_merge = mode;
+  return BGV_OK;
+}
+
+int bgv_pair_stats(bgv_ctx* c, bgv_pair_path* out) {
+  if (!c || !out) return fail(BGV_E_INVALID_ARG, "null argument");
+  if (c->pair_pending) {  // a call that failed between its launches and its results
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipMemcpyAsync(&c->pair_path.pairs, c->pc.class_off + c->pc.n_jobs, 4, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(hipStreamSynchronize(c->st));
+    c->pair_pending = false;
+  }
+  *out = c->pair_path;
+  return BGV_OK;
 }
 
 // ---- committee bitfields over resident index lists ---------------------------
@@ -1571,6 +1709,8 @@ static void hash_path_clear(bgv_ctx* c) {
   if (!c) return;
   c->hash_path = {};
   c->hash_pending = false;
+  c->pair_path = {};  // nor do they merge pairs: bgv_pair_stats reports zeros as well
+  c->pair_pending = c->pair_redo = false;
 }
 
 int bgv_hash_stats(bgv_ctx* c, bgv_hash_path* out) {
@@ -1596,13 +1736,13 @@ int bgv_verify_bits(bgv_ctx* c, const bgv_bits_batch* b, int32_t* job_result, in
   c->partial_pending = false;
   HIPCHK(hipSetDevice(c->device));
   active_guard ag(c->device);
+  pair_entry pe(c, c->pair_merge != 0);
   dev_batch d;
   if (int r = bits_front(c, b, d, true)) return r;
   if (int r = bits_layout(c, d, b->scalars, b->scalars && !b->on_device)) return r;
   dev_work w;
   if (int r = work_alloc(c, d, w)) return r;
-  if (int r = run_stages(c, d, w, 0, ST_COUNT)) return r;
-  return finish_results(c, d, w, job_result, set_code, stats);
+  return run_and_finish(c, d, w, job_result, set_code, stats);
 }
 
 int bgv_bits_expand_ms(bgv_ctx* c, float* ms) {
@@ -2400,25 +2540,41 @@ int bgv_partial(bgv_ctx* c, const bgv_batch* b, uint8_t* miller576, int32_t* set
   dev_batch d;
   if (int r = prepare(c, b, d, true)) return r;
   dev_work w;
+  pair_entry pe(c, c->pair_merge != 0);
   if (int r = work_alloc(c, d, w)) return r;
-  if (int r = run_stages(c, d, w, ST_SIG, ST_BATCH_FINAL)) return r;
-  launch_stage(c->st, ST_SET_CODES, d, w);
   fp12_t f;
-  if (d.n_jobs) {
-    launch_fp12_convert(c->st, w.f_batch, w.f_part, 1, false);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(&f, w.f_part, sizeof f, hipMemcpyDeviceToHost, c->st));
-  } else {
-    memset(&f, 0, sizeof f);
-    f.c0.c0.c0.l[0] = 1;  // plain 1
-  }
   std::vector<int32_t> jc(d.n_jobs ? d.n_jobs : 1);
-  if (d.n_jobs) HIPCHK(hipMemcpyAsync(jc.data(), w.job_code, (size_t)d.n_jobs * 4, hipMemcpyDeviceToHost, c->st));
-  if (set_code && d.n_sets) HIPCHK(hipMemcpyAsync(set_code, w.set_code, (size_t)d.n_sets * 4, hipMemcpyDeviceToHost, c->st));
-  if (c->hash_pending) HIPCHK(hipMemcpyAsync(&c->hash_path.hashes, c->mc.n_uniq, 4, hipMemcpyDeviceToHost, c->st));
-  HIPCHK(hipStreamSynchronize(c->st));
-  c->hash_pending = false;
-  c->staged_pending = false;
+  // (a second, unmerged pass only after a merged one met an identity class)
+  bool fell_back = false;
+  for (int pass = 0; pass < 2; pass++) {
+    if (int r = run_stages(c, d, w, ST_SIG, ST_BATCH_FINAL)) return r;
+    launch_stage(c->st, ST_SET_CODES, d, w);
+    if (d.n_jobs) {
+      launch_fp12_convert(c->st, w.f_batch, w.f_part, 1, false);
+      HIPCHK(hipGetLastError());
+      HIPCHK(hipMemcpyAsync(&f, w.f_part, sizeof f, hipMemcpyDeviceToHost, c->st));
+    } else {
+      memset(&f, 0, sizeof f);
+      f.c0.c0.c0.l[0] = 1;  // plain 1
+    }
+    if (d.n_jobs) HIPCHK(hipMemcpyAsync(jc.data(), w.job_code, (size_t)d.n_jobs * 4, hipMemcpyDeviceToHost, c->st));
+    if (set_code && d.n_sets) HIPCHK(hipMemcpyAsync(set_code, w.set_code, (size_t)d.n_sets * 4, hipMemcpyDeviceToHost, c->st));
+    if (c->hash_pending) HIPCHK(hipMemcpyAsync(&c->hash_path.hashes, c->mc.n_uniq, 4, hipMemcpyDeviceToHost, c->st));
+    uint32_t ident = 0;
+    const bool want_pair = c->pair_pending;
+    if (want_pair) {
+      HIPCHK(hipMemcpyAsync(&c->pair_path.pairs, c->pc.class_off + c->pc.n_jobs, 4, hipMemcpyDeviceToHost, c->st));
+      HIPCHK(hipMemcpyAsync(&ident, c->pc.ident, 4, hipMemcpyDeviceToHost, c->st));
+    }
+    HIPCHK(hipStreamSynchronize(c->st));
+    c->hash_pending = false;
+    c->pair_pending = false;
+    c->staged_pending = false;
+    if (!(want_pair && ident)) break;
+    c->pm_call = false;  // an identity class: the pass is void, once more with one pair per set
+    fell_back = true;
+  }
+  if (fell_back) c->pair_path.fallback = 1;
   fp12_plain_to_bytes(miller576, f);
   int32_t ok = 1;
   for (uint32_t j = 0; j < d.n_jobs; j++) {
@@ -2475,6 +2631,8 @@ int bgv_combine_final(bgv_ctx* c, const uint8_t* parts, uint32_t n, int32_t* is_
 int bgv_debug_stages(bgv_ctx* c, const bgv_batch* b, int32_t* job_result, int32_t* set_code, bgv_debug* o) {
   if (!c || !b || !o || (!job_result && b->n_jobs)) return fail(BGV_E_INVALID_ARG, "null argument");
   c->partial_pending = false;
+  c->pair_path = {};  // the per-set golden plan: never merged, zeros in bgv_pair_stats
+  c->pair_pending = c->pair_redo = false;
   HIPCHK(hipSetDevice(c->device));
   dev_batch d;
   if (int r = prepare(c, b, d, true)) return r;
@@ -2540,6 +2698,60 @@ int bgv_debug_stages(bgv_ctx* c, const bgv_batch* b, int32_t* job_result, int32_
   if (o->batch_fe) {
     if (J) fp12_plain_to_bytes(o->batch_fe, fe[n + 2 * J]);
     else memset(o->batch_fe, 0, 576);
+  }
+  return BGV_OK;
+}
+
+// test-only: bgv_verify through the merged path plus the classes (include/bgv.h)
+int bgv_debug_pair_classes(bgv_ctx* c, const bgv_batch* b, int32_t* job_result, int32_t* set_code, uint32_t* cls,
+                           uint32_t* class_off, uint8_t* p_class96, uint8_t* job_fe, uint8_t* batch_fe) {
+  if (!c || !b || (!job_result && b->n_jobs)) return fail(BGV_E_INVALID_ARG, "null argument");
+  c->partial_pending = false;
+  HIPCHK(hipSetDevice(c->device));
+  pair_entry pe(c, true);
+  dev_batch d;
+  if (int r = prepare(c, b, d, true)) return r;
+  if (!pair_merge_on(c, d)) return fail(BGV_E_STATE, "bgv_debug_pair_classes: the batch's layout does not merge pairs");
+  dev_work w;
+  if (int r = work_alloc(c, d, w)) return r;
+  const uint32_t n = d.n_sets, J = d.n_jobs;
+  if (int r = run_stages(c, d, w, 0, ST_COUNT)) return r;
+  if (int r = finish_results(c, d, w, job_result, set_code, nullptr)) return r;
+  // the classes of the merged pass, also when it met an identity class
+  const bgv_pair_path path = c->pair_path;
+  const uint32_t n_cls = path.pairs <= n ? path.pairs : n;
+  if (cls) HIPCHK(hipMemcpyAsync(cls, c->pc.cls, (size_t)n * 4, hipMemcpyDeviceToHost, c->st));
+  if (class_off) HIPCHK(hipMemcpyAsync(class_off, c->pc.class_off, ((size_t)J + 1) * 4, hipMemcpyDeviceToHost, c->st));
+  if (p_class96 && n_cls) {
+    if (int r = c->dbg_out.ensure((size_t)n_cls * 96)) return r;
+    launch_export_g1a(c->st, c->pc.p_cls, c->dbg_out.p, n_cls);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(p_class96, c->dbg_out.p, (size_t)n_cls * 96, hipMemcpyDeviceToHost, c->st));
+  }
+  HIPCHK(hipStreamSynchronize(c->st));
+  if (c->pair_redo) {  // the verdicts and products of the unmerged pass
+    c->pm_call = false;
+    if (int r = run_stages(c, d, w, 0, ST_COUNT)) return r;
+    if (int r = finish_results(c, d, w, job_result, set_code, nullptr)) return r;
+    c->pair_path = path;
+    c->pair_path.merged = 0;
+    c->pair_path.pairs = n;
+    c->pair_path.fallback = 1;
+  }
+  if ((job_fe || batch_fe) && J) {
+    if (int r = c->dbg_fe.ensure((size_t)J + 1)) return r;
+    launch_final_exp_many(c->st, w.f_job, c->dbg_fe.p, J);
+    launch_final_exp_many(c->st, w.f_batch, c->dbg_fe.p + J, 1);
+    launch_fp12_convert(c->st, c->dbg_fe.p, c->dbg_fe.p, J + 1, false);
+    HIPCHK(hipGetLastError());
+    std::vector<fp12_t> fe((size_t)J + 1);
+    HIPCHK(hipMemcpyAsync(fe.data(), c->dbg_fe.p, ((size_t)J + 1) * sizeof(fp12_t), hipMemcpyDeviceToHost, c->st));
+    HIPCHK(hipStreamSynchronize(c->st));
+    if (job_fe)
+      for (uint32_t k = 0; k < J; k++) fp12_plain_to_bytes(job_fe + 576u * k, fe[k]);
+    if (batch_fe) fp12_plain_to_bytes(batch_fe, fe[J]);
+  } else if (batch_fe) {
+    memset(batch_fe, 0, 576);
   }
   return BGV_OK;
 }

@@ -297,4 +297,13 @@ struct msg_classes {
 void launch_msg_dedup(hipStream_t st, const msg_classes& c);     // index-only set-up, beside launch_prep
 void launch_hash_classes(hipStream_t st, const msg_classes& c);  // ST_HASH of the bulk layout: k_hash_reps, k_hash_spread
 
+// ---- pair classes of a bulk batch (bgv_pair_merge, pair_merge.h, bgv_pair_merge.hip)
+// One set-pair Miller loop per (job, signing root).  The caller clears table
+// (0xff), head (0xff), class_off, cls_job and *ident (0) on the same stream.
+struct pair_classes;
+void launch_pair_classes(hipStream_t st, const pair_classes& p);  // index-only set-up, after launch_msg_dedup
+void launch_pair_h(hipStream_t st, const pair_classes& p, const g2a* h_aff);  // hash stream, after launch_hash_classes
+void launch_pair_lines(hipStream_t st, const pair_classes& p, fp2_t* lines);  // launch_lines, one lane per class
+void launch_pair_sum(hipStream_t st, const pair_classes& p, const g1a* rpk_aff, const int32_t* pk_code);  // after ST_PK_SCALE
+
 }  // namespace bgv

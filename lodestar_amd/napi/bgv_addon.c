@@ -8,7 +8,7 @@
  *   open(device, cuSplit = 0, cfg?) -> ctx (external)  bgv_open_cfg  (multithread/index.ts:120); cuSplit N > 0:
  *                                                a priority context on N reserved CUs (verifyOnMainThread),
  *                                                N < 0: a bulk context that leaves them free (bgv_cfg.cu_split);
- *                                                cfg (tests and A/B tools): {split, hashDedup} as in bgv_cfg
+ *                                                cfg (tests and A/B tools): {split, miller, hashDedup, millerSteps} as in bgv_cfg
  *   close(ctx)                                   bgv_close     (multithread/index.ts:193-214)
  *   pubkeysSet(ctx, first, Uint8Array, format)   bgv_pubkeys_set (pubkeyCache.ts:56-77)
  *   pubkeysCount(ctx) -> number
@@ -34,6 +34,9 @@
  *   setIndexListSums(ctx, id, bool)              bgv_index_list_sums: build (or drop) the list's resident prefix sums
  *   indexListHasSums(ctx, id) -> boolean         bgv_index_list_has_sums
  *   hashStats(ctx) -> {sets, hashes, dedup}      bgv_hash_stats (the last verify / verifyBits / partial, for the sync paths)
+ *   pairMerge(ctx, on)                           bgv_pair_merge: one Miller pair per distinct signing root of a job, from the
+ *                                                next call on (bulk layout, one-lane loop; off by default)
+ *   pairStats(ctx) -> {sets, pairs, merged, fallback}   bgv_pair_stats (the last verify / verifyBits / partial)
  *   bitsPathStats(ctx) -> {setsComplement, keysExpanded, keysGathered}   bgv_bits_path_stats (the last verifyBits / verifySameMessageBits)
  *   verifyBits(ctx, bitsBatch) -> Promise<result>, verifyBitsSync(ctx, bitsBatch) -> result
  *                                                bgv_verify_bits: sets given as (list, window, participation bits)
@@ -47,7 +50,8 @@
  * deviceMs, workerStartMs, workerEndMs}: the BlsWorkResult fields
  * (multithread/types.ts:26-38) the pool's metrics are fed from; verify,
  * verifyBits and partial add hashes, the call's hash_to_G2 evaluations
- * (bgv_hash_stats, read while the context is still locked).  For
+ * (bgv_hash_stats, read while the context is still locked), and millerPairs,
+ * the set pairs its Miller stage ran (bgv_pair_stats.pairs).  For
  * partial() `results` is provisional: -code for a job rejected by a parse /
  * subgroup / pubkey error (final), 1 for every other job (valid iff the
  * combined check passes).  Contexts on different devices run their queued
@@ -183,10 +187,11 @@ static napi_value Open(napi_env env, napi_callback_info info) {
         NAPI_CALL(env, napi_get_property(env, a[2], key, &val));
         NAPI_CALL(env, napi_get_value_int32(env, val, &x));
         if (!strcmp(name, "split")) cfg.split = x;
+        else if (!strcmp(name, "miller")) cfg.miller = x;
         else if (!strcmp(name, "hashDedup")) cfg.hash_dedup = x;
         else if (!strcmp(name, "millerSteps")) cfg.miller_steps = x;
         else {
-          napi_throw_type_error(env, NULL, "open: cfg takes split, hashDedup and millerSteps");
+          napi_throw_type_error(env, NULL, "open: cfg takes split, miller, hashDedup and millerSteps");
           return NULL;
         }
       }
@@ -320,6 +325,7 @@ typedef struct {
   int32_t* job_result;
   bgv_stats stats;
   bgv_hash_path hash_path; /* K_VERIFY, K_BITS, K_PARTIAL: read under the context's lock */
+  bgv_pair_path pair_path; /* likewise */
   double t_start_ms, t_end_ms;
   int status;
   char err[512];
@@ -434,6 +440,8 @@ static void run_verify(verify_job* j) {
     /* under the same lock: this call's evaluations, not a later call's */
     if (j->status == BGV_OK && (j->kind == K_VERIFY || j->kind == K_BITS || j->kind == K_PARTIAL))
       j->status = bgv_hash_stats(j->c->ctx, &j->hash_path);
+    if (j->status == BGV_OK && (j->kind == K_VERIFY || j->kind == K_BITS || j->kind == K_PARTIAL))
+      j->status = bgv_pair_stats(j->c->ctx, &j->pair_path);
     if (j->status != BGV_OK) snprintf(j->err, sizeof j->err, "bgv error %d: %s", j->status, bgv_last_error());
   }
   j->t_end_ms = now_ms();
@@ -462,6 +470,8 @@ static napi_value result_object(napi_env env, const verify_job* j) {
   if (j->kind == K_VERIFY || j->kind == K_BITS || j->kind == K_PARTIAL) {
     napi_create_uint32(env, j->hash_path.hashes, &v);
     napi_set_named_property(env, o, "hashes", v);
+    napi_create_uint32(env, j->pair_path.pairs, &v);
+    napi_set_named_property(env, o, "millerPairs", v);
   }
   if (j->kind == K_PARTIAL) {
     void* dst = NULL;
@@ -1235,6 +1245,55 @@ static napi_value HashStats(napi_env env, napi_callback_info info) {
   return r;
 }
 
+/* pairMerge(ctx, on): bgv_pair_merge (a boolean, or 0 / 1; any other number is refused by the library) */
+static napi_value PairMerge(napi_env env, napi_callback_info info) {
+  size_t argc = 2;
+  napi_value a[2];
+  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, a, NULL, NULL));
+  addon_ctx* c = get_ctx(env, a[0]);
+  if (!c) return NULL;
+  int32_t mode = 0;
+  napi_valuetype t = napi_undefined;
+  if (argc >= 2) NAPI_CALL(env, napi_typeof(env, a[1], &t));
+  if (t == napi_boolean) {
+    bool on = false;
+    NAPI_CALL(env, napi_get_value_bool(env, a[1], &on));
+    mode = on ? 1 : 0;
+  } else {
+    NAPI_CALL(env, napi_get_value_int32(env, a[1], &mode));
+  }
+  pthread_mutex_lock(&c->mu);
+  const int st = bgv_pair_merge(c->ctx, mode);
+  pthread_mutex_unlock(&c->mu);
+  if (st != BGV_OK) return throw_bgv(env, st);
+  return NULL;
+}
+
+/* pairStats(ctx): bgv_pair_stats of the context's last ordinary batch */
+static napi_value PairStats(napi_env env, napi_callback_info info) {
+  size_t argc = 1;
+  napi_value a[1];
+  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, a, NULL, NULL));
+  addon_ctx* c = get_ctx(env, a[0]);
+  if (!c) return NULL;
+  bgv_pair_path p;
+  pthread_mutex_lock(&c->mu);
+  const int st = bgv_pair_stats(c->ctx, &p);
+  pthread_mutex_unlock(&c->mu);
+  if (st != BGV_OK) return throw_bgv(env, st);
+  napi_value r, v;
+  NAPI_CALL(env, napi_create_object(env, &r));
+  NAPI_CALL(env, napi_create_uint32(env, p.sets, &v));
+  NAPI_CALL(env, napi_set_named_property(env, r, "sets", v));
+  NAPI_CALL(env, napi_create_uint32(env, p.pairs, &v));
+  NAPI_CALL(env, napi_set_named_property(env, r, "pairs", v));
+  NAPI_CALL(env, napi_create_uint32(env, p.merged, &v));
+  NAPI_CALL(env, napi_set_named_property(env, r, "merged", v));
+  NAPI_CALL(env, napi_create_uint32(env, p.fallback, &v));
+  NAPI_CALL(env, napi_set_named_property(env, r, "fallback", v));
+  return r;
+}
+
 static napi_value BitsPathStats(napi_env env, napi_callback_info info) {
   size_t argc = 1;
   napi_value a[1];
@@ -1286,6 +1345,8 @@ static napi_value Init(napi_env env, napi_value exports) {
       {"indexListHasSums", NULL, IndexListHasSums, NULL, NULL, NULL, napi_enumerable, NULL},
       {"bitsPathStats", NULL, BitsPathStats, NULL, NULL, NULL, napi_enumerable, NULL},
       {"hashStats", NULL, HashStats, NULL, NULL, NULL, napi_enumerable, NULL},
+      {"pairMerge", NULL, PairMerge, NULL, NULL, NULL, napi_enumerable, NULL},
+      {"pairStats", NULL, PairStats, NULL, NULL, NULL, napi_enumerable, NULL},
       {"verifyBits", NULL, VerifyBits, NULL, NULL, NULL, napi_enumerable, NULL},
       {"verifyBitsSync", NULL, VerifyBitsSync, NULL, NULL, NULL, napi_enumerable, NULL},
   };

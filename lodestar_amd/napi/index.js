@@ -159,6 +159,14 @@ function recordHashes(m, sets, res) {
   m.hashToG2Evaluated = (m.hashToG2Evaluated || 0) + res.hashes;
 }
 
+// Set pairs of the Miller stage per device batch (bgv_pair_stats): the sets that needed a pair and the pairs the
+// device ran (fewer where a context with pairMerge met repeated signing roots inside a job).  Added on first use too.
+function recordPairs(m, sets, res) {
+  if (!Number.isFinite(res.millerPairs)) return;
+  m.millerPairsSets = (m.millerPairsSets || 0) + sets;
+  m.millerPairsEvaluated = (m.millerPairsEvaluated || 0) + res.millerPairs;
+}
+
 function aggregatedPubkeysCount(sets) {
   let n = 0;
   for (const s of sets) {
@@ -581,8 +589,10 @@ class BlsGpuVerifier {
   // contextsPerDevice: device batches in flight per GPU (one context each,
   // each with its own table replica); a batch large enough to shard is split
   // over one idle context per device
+  // pairMerge (bgv_pair_merge, off by default): every bulk context pairs once per distinct signing root of a job
+  // where its batch runs the bulk layout's one-lane loop; the priority context serves latency batches
   constructor({device = 0, devices = null, maxSetsPerDeviceBatch = MAX_SETS_PER_DEVICE_BATCH, shardMinSets = SHARD_MIN_SETS,
-    priorityCus = null, blsVerifyAllMultiThread = false, contextsPerDevice = CONTEXTS_PER_DEVICE} = {}) {
+    priorityCus = null, blsVerifyAllMultiThread = false, contextsPerDevice = CONTEXTS_PER_DEVICE, pairMerge = false} = {}) {
     const ids = devices && devices.length ? devices : [device];
     if (!(contextsPerDevice >= 1)) throw new Error(`contextsPerDevice ${contextsPerDevice}`);
     if (priorityCus === null || priorityCus === undefined) priorityCus = ids.length > 1 ? PRIORITY_CUS : 0;
@@ -612,6 +622,8 @@ class BlsGpuVerifier {
         this.ctxDev.push(i);
       }
     });
+    this.pairMerge = !!pairMerge;
+    if (this.pairMerge) for (const c of this.ctxs) addon.pairMerge(c, true);
     this.nDevices = ids.length;
     this.contextsPerDevice = contextsPerDevice;
     this.ctx = this.ctxs[0];
@@ -1098,6 +1110,7 @@ class BlsGpuVerifier {
       results, batchRetries: valid ? 0 : 1, batchSigsSuccess: sigsOk,
       pubkeysAggregated: parts.reduce((a, p) => a + p.pubkeysAggregated, 0),
       hashes: parts.reduce((a, p) => a + p.hashes, 0), // per shard: a root on two shards is hashed on both
+      millerPairs: parts.reduce((a, p) => a + p.millerPairs, 0),
       deviceMs: Math.max(...parts.map((p) => p.deviceMs)),
       workerStartMs: Math.min(...parts.map((p) => p.workerStartMs)),
       workerEndMs: Math.max(...finals.map((p) => p.workerEndMs)),
@@ -1121,6 +1134,7 @@ class BlsGpuVerifier {
     m.lodestar_bls_thread_pool_batch_retries_total += res.batchRetries;
     m.lodestar_bls_thread_pool_batch_sigs_success_total += res.batchSigsSuccess;
     recordHashes(m, ok + err, res);
+    recordPairs(m, ok + err, res);
   }
 
   // gauges sampled at scrape time (index.ts:135-139)
@@ -1166,8 +1180,9 @@ class BlsGpuVerifier {
 // thread (addon.verifySync); canAcceptWork is always true.  Its pubkey table
 // is its own replica.
 class BlsGpuSingleThreadVerifier {
-  constructor({device = 0} = {}) {
+  constructor({device = 0, pairMerge = false} = {}) {
     this.ctx = addon.open(device, 0);
+    if (pairMerge) addon.pairMerge(this.ctx, true); // bgv_pair_merge: bulk-layout batches only
     this.closed = false;
     this.metrics = {lodestar_bls_aggregated_pubkeys_total: 0, lodestar_bls_thread_pool_main_thread_time_seconds: {count: 0, sum: 0}};
   }

@@ -60,6 +60,7 @@ EXPORTS = [
     "bgv_verify_same_message_bits", "bgv_smb_check", "bgv_debug_same_message_bits",
     "bgv_hash_stats", "bgv_miller_path_stats",
     "bgv_verify_same_message_aggregate", "bgv_sm_agg_check", "bgv_sm_agg_ms",
+    "bgv_pair_merge", "bgv_pair_stats", "bgv_debug_pair_classes",
 ]
 MAX_INDEX_LISTS = 8
 SRC_EXPLICIT = 0xFFFFFFFF
@@ -287,6 +288,15 @@ class BgvMillerPath(ctypes.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
+class BgvPairPath(ctypes.Structure):
+    """bgv_pair_path (include/bgv.h): the set pairs the Miller stage of the last ordinary batch ran"""
+    _fields_ = [("sets", ctypes.c_uint32), ("pairs", ctypes.c_uint32), ("merged", ctypes.c_uint32),
+                ("fallback", ctypes.c_uint32)]
+
+    def as_dict(self) -> dict:
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
 def source_hash(root: str = ROOT) -> str:
     """SHA-256 over (path, content) of source_files(): the id tools/build.py
     compiles into the library (bgv_build_id) and load_library checks."""
@@ -388,6 +398,9 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
             "bgv_bits_path_stats": ([P, ctypes.POINTER(BgvBitsPath)], ctypes.c_int),
             "bgv_hash_stats": ([P, ctypes.POINTER(BgvHashPath)], ctypes.c_int),
             "bgv_miller_path_stats": ([P, ctypes.POINTER(BgvMillerPath)], ctypes.c_int),
+            "bgv_pair_merge": ([P, ctypes.c_int32], ctypes.c_int),
+            "bgv_pair_stats": ([P, ctypes.POINTER(BgvPairPath)], ctypes.c_int),
+            "bgv_debug_pair_classes": ([P, ctypes.POINTER(BgvBatch), P, P, P, P, P, P, P], ctypes.c_int),
             "bgv_bits_plan": ([ctypes.POINTER(BgvBitsBatch), P, P, P, ctypes.POINTER(ctypes.c_uint64)], ctypes.c_int),
             "bgv_debug_bits_keys": ([P, ctypes.POINTER(BgvBitsBatch), P, P, P], ctypes.c_int),
             "bgv_debug_index_list_sums": ([P, u32, u32, u32, P], ctypes.c_int),
@@ -577,6 +590,7 @@ class Device:
         """cfg: bgv_cfg overrides (tests and A/B tools only), e.g. miller=36, split=0"""
         self.lib = load_library()
         h = ctypes.c_void_p()
+        pair_merge = cfg.pop("pair_merge", None)  # a context call, not a bgv_cfg field (bgv_pair_merge)
         if cfg:
             self._check(self.lib.bgv_open_cfg(device, ctypes.byref(BgvCfg.make(**cfg)), ctypes.byref(h)))
         else:
@@ -584,6 +598,8 @@ class Device:
         self.h = h
         self.device = device
         self.last_stats = BgvStats()
+        if pair_merge is not None:
+            self.pair_merge(pair_merge)
 
     # -------------------------------------------------------------- helpers
     def _check(self, st: int):
@@ -861,6 +877,37 @@ class Device:
         out = BgvHashPath()
         self._check(self.lib.bgv_hash_stats(self.h, ctypes.byref(out)))
         return out.as_dict()
+
+    def pair_merge(self, on) -> None:
+        """bgv_pair_merge: one Miller pair per distinct signing root of a job, from the next
+        call on (bulk layout, one-lane loop; off by default).  on: bool, or 0 / 1."""
+        self._check(self.lib.bgv_pair_merge(self.h, int(on)))
+
+    def pair_stats(self) -> dict:
+        """bgv_pair_stats: {sets, pairs, merged, fallback} of the last verify, verify_bits or
+        partial on the context (pairs: the classes when merged is 1, else sets); zeros after
+        any other entry"""
+        out = BgvPairPath()
+        self._check(self.lib.bgv_pair_stats(self.h, ctypes.byref(out)))
+        return out.as_dict()
+
+    def debug_pair_classes(self, arrays: dict, on_device: bool = False) -> dict:
+        """bgv_debug_pair_classes (test only): verify through the merged path plus cls
+        uint32[n_sets], class_off uint32[n_jobs + 1], p_class uint8[classes, 96], job_fe
+        uint8[n_jobs, 576], batch_fe uint8[576], job_result, set_code"""
+        b = self.make_batch(arrays, on_device)
+        n, J = b.n_sets, b.n_jobs
+        jr = np.zeros(max(J, 1), np.int32)
+        sc = np.zeros(max(n, 1), np.int32)
+        cls = np.zeros(max(n, 1), np.uint32)
+        off = np.zeros(J + 1, np.uint32)
+        pc = np.zeros((max(n, 1), 96), np.uint8)
+        jfe = np.zeros((max(J, 1), 576), np.uint8)
+        bfe = np.zeros(576, np.uint8)
+        self._check(self.lib.bgv_debug_pair_classes(self.h, ctypes.byref(b), jr.ctypes.data, sc.ctypes.data, cls.ctypes.data,
+                                                    off.ctypes.data, pc.ctypes.data, jfe.ctypes.data, bfe.ctypes.data))
+        return {"job_result": jr[:J], "set_code": sc[:n], "cls": cls[:n], "class_off": off, "p_class": pc[: int(off[J])],
+                "job_fe": jfe[:J], "batch_fe": bfe}
 
     def miller_path(self) -> dict:
         """bgv_miller_path_stats: {steps, slice_sets, items} of the last verify, verify_bits,

@@ -929,7 +929,7 @@ class BlsGpuVerifier:
     def __init__(self, devices=(0,), metrics: dict | None = None, scalar_seed: int | None = None,
                  max_sets_per_device_batch: int = MAX_SETS_PER_DEVICE_BATCH, shard_min_sets: int = SHARD_MIN_SETS,
                  priority_cus: int | None = None, bls_verify_all_multi_thread: bool = False,
-                 contexts_per_device: int = CONTEXTS_PER_DEVICE):
+                 contexts_per_device: int = CONTEXTS_PER_DEVICE, pair_merge: bool = False, device_cfg: dict | None = None):
         # priority_cus CUs of the first device (a multiple of 8) are kept for
         # verifyOnMainThread (bgv_cfg.cu_split): its own context runs there,
         # the first bulk context leaves them free; 0 shares every CU.  Default:
@@ -954,13 +954,22 @@ class BlsGpuVerifier:
         self.contexts_per_device = contexts_per_device
         self.n_devices = len(devices)
         self._ctx_dev = [i for i in range(len(devices)) for _ in range(contexts_per_device)]
-        self.devices = [native.Device(devices[i], cu_split=-priority_cus) if i == 0 and priority_cus > 0
-                        else native.Device(devices[i]) for i in self._ctx_dev]
+        # device_cfg: bgv_cfg overrides of the bulk contexts (tests and A/B tools only; production pools leave
+        # every field at auto)
+        bulk_cfg = dict(device_cfg or {})
+        self.devices = [native.Device(devices[i], **{**bulk_cfg, "cu_split": -priority_cus}) if i == 0 and priority_cus > 0
+                        else native.Device(devices[i], **bulk_cfg) for i in self._ctx_dev]
         if bls_verify_all_multi_thread:
             self.prio = None
         else:
             self.prio = native.Device(devices[0], cu_split=priority_cus) if priority_cus > 0 else native.Device(devices[0])
         self.prio_reserved = priority_cus > 0  # device 0's bulk context runs at RESERVED_CAP (shard_jobs caps)
+        # pair_merge (bgv_pair_merge, off by default): every bulk context pairs once per distinct signing root of
+        # a job where its batch runs the bulk layout's one-lane loop; the priority context serves latency batches
+        self.pair_merge = bool(pair_merge)
+        if self.pair_merge:
+            for d in self.devices:
+                d.pair_merge(True)
         if self.prio is not None:
             self._warm_priority()
         self._prio_lock = threading.Lock()
@@ -1226,17 +1235,29 @@ class BlsGpuVerifier:
     def _record_hashes(self, hs: list[dict | None]):
         """hash_to_G2 per device batch (bgv_hash_stats of each context that ran a part of it): the sets that
         needed H(m) and the evaluations made, fewer where a bulk-layout batch repeats signing roots.  Both keys
-        appear with the first batch that reports them; sharded batches add up their shards."""
+        appear with the first batch that reports them; sharded batches add up their shards.  Beside them the set
+        pairs of the Miller stage (bgv_pair_stats): the sets that needed a pair and the pairs run, fewer where a
+        context with pair_merge met repeated roots inside a job."""
         for h in hs:
             if h:
                 self.metrics["hash_to_g2_sets"] = self.metrics.get("hash_to_g2_sets", 0) + int(h["sets"])
                 self.metrics["hash_to_g2_evaluated"] = self.metrics.get("hash_to_g2_evaluated", 0) + int(h["hashes"])
+                pp = h.get("pair")
+                if pp:
+                    self.metrics["miller_pairs_sets"] = self.metrics.get("miller_pairs_sets", 0) + int(pp["sets"])
+                    self.metrics["miller_pairs_evaluated"] = self.metrics.get("miller_pairs_evaluated", 0) + int(pp["pairs"])
 
     @staticmethod
     def _hash_stats(dev) -> dict | None:
         """read under the context's lock, right after its call (a device stand-in without the getter reports nothing)"""
         get = getattr(dev, "hash_stats", None)
-        return get() if get is not None else None
+        if get is None:
+            return None
+        out = dict(get())
+        pair = getattr(dev, "pair_stats", None)
+        if pair is not None:
+            out["pair"] = pair()
+        return out
 
     def _warm_priority(self):
         """sizes the priority context's work buffers for a full job (128 sets)
@@ -1424,8 +1445,10 @@ class BlsGpuSingleThreadVerifier:
     waits, as it does for blst on the main thread); can_accept_work() is always
     True.  Its pubkey table is its own replica."""
 
-    def __init__(self, device: int = 0, metrics: dict | None = None):
+    def __init__(self, device: int = 0, metrics: dict | None = None, pair_merge: bool = False):
         self.device = native.Device(device)
+        if pair_merge:  # bgv_pair_merge: one pair per distinct root of a job in bulk-layout batches
+            self.device.pair_merge(True)
         self.table = PubkeyTable([self.device])
         self.metrics = metrics if metrics is not None else {"aggregated_pubkeys_total": 0, "main_thread_time_s": 0.0,
                                                             "main_thread_calls": 0}

@@ -711,6 +711,28 @@ typedef struct bgv_pair_path {
   uint32_t sets, pairs, merged, fallback;
 } bgv_pair_path;
 int bgv_pair_stats(bgv_ctx* ctx, bgv_pair_path* out);
+/* Batch-first tail of the steps path (additive to ABI 4).
+ * A batch on the steps path (bgv_miller_path.steps) with the (job, window) MSM
+ * gets its whole-batch verdict from ONE (-G1, sum_j S_job) pair and ONE Miller
+ * recurrence over the step products of all its slices; the per-job signature
+ * sums, (-G1, S_job) pairs and chains run behind that verdict, on the device
+ * and with no host round trip, and only when it failed (the worker's per-job
+ * retry).  Verdicts, set codes and bgv_stats are those of the per-job tail;
+ * bgv_partial's 576 bytes differ as a field element and agree after the final
+ * exponentiation.  mode: -1 auto (on wherever the steps path is; the default),
+ * 0 off, 1 on (still only on that path).  From the next call on the context;
+ * bgv_debug_stages and bgv_debug_pair_classes always run the per-job tail.
+ * BGV_E_INVALID_ARG for a null context or any other mode. */
+int bgv_batch_tail(bgv_ctx* ctx, int32_t mode);
+/* The tail of the context's last bgv_verify / bgv_verify_bits / bgv_partial(+
+ * _finish): batch_first 1 when it ran batch-first, retried 1 when its batch
+ * check failed and the per-job kernels ran (always 0 right after bgv_partial:
+ * the check is bgv_partial_finish's).  Zeros after bgv_debug_stages and
+ * bgv_debug_pair_classes, which run the per-job tail. */
+typedef struct bgv_tail_path {
+  uint32_t batch_first, retried;
+} bgv_tail_path;
+int bgv_tail_stats(bgv_ctx* ctx, bgv_tail_path* out);
 /* test-only: bgv_verify through the merged path (whatever bgv_pair_merge says;
  * BGV_E_STATE when the batch's layout does not merge) plus cls[n_sets] (class
  * index of every set), class_off[n_jobs + 1], p_class96[n_sets][96] (P_c affine

@@ -186,6 +186,13 @@ struct bgv_ctx {
   bgv_pair_path pair_path = {};       // bgv_pair_stats
   bool pair_pending = false;          // pair_path.pairs and the identity flag are still on the device
   bool pair_redo = false;             // the last merged pass met an identity class: its results are void
+  // batch-first tail of the steps path (bgv_batch_tail)
+  int32_t batch_tail = -1;            // the switch: -1 auto (on wherever the steps path is), 0 off, 1 on
+  dbuf<g2j> win_tmp;                  // dev_work.win_tmp
+  dbuf<fp12_t> f_fold;                // dev_work.f_fold
+  dev_batch tail_d = {};              // the view ST_F_TREE .. ST_BATCH_FINAL of the last run_stages ran over (the pair
+  dev_work tail_w = {};               // classes' when merged): bgv_partial_finish launches the retry kernels over it
+  bgv_tail_path tail_path = {};       // bgv_tail_stats
   // microbench scratch
   dbuf<fp_t> mb_fp;
   dbuf<uint64_t> mb_u64;
@@ -386,6 +393,7 @@ int bgv_close(bgv_ctx* c) {
   c->sma_pk.release(); c->sma_pk_code.release(); c->sma_aff.release();
   c->sag_seg.release(); c->sag_cnt.release(); c->sag_code.release(); c->sag_out.release(); c->sag_valid.release();
   c->sag_sig.release();
+  c->win_tmp.release(); c->f_fold.release();
   c->mb_fp.release(); c->mb_u64.release();
   (void)hipStreamDestroy(c->st);
   (void)hipStreamDestroy(c->st_hash);
@@ -937,9 +945,9 @@ static int work_alloc_once(bgv_ctx* c, const dev_batch& d, dev_work& w) {
   w.chunk_off = c->chunk_off.p; w.chunk_set = c->chunk_set.p; w.pk_part = c->pk_part.p;
   if ((r = c->sig_aff.ensure(ns)) || (r = c->h_aff.ensure(ns)) || (r = c->sig_inf.ensure(ns)) ||
       (r = c->sig_code.ensure(ns)) || (r = c->pk_code.ensure(ns)) || (r = c->rpk_aff.ensure(ns)) ||
-      (r = c->rsig.ensure(ns)) || (r = c->f_set.ensure(ns + nj)) || (r = c->set_code.ensure(ns)) ||
+      (r = c->rsig.ensure(ns)) || (r = c->f_set.ensure(ns + nj + 1)) || (r = c->set_code.ensure(ns)) ||
       (r = c->set_job.ensure(ns)) || (r = c->item_off.ensure(nj + 1)) || (r = c->item_job.ensure(ns + nj + 1)) || (r = c->f_job.ensure(nj)) || (r = c->f_batch.ensure(nj)) || (r = c->f_tmp.ensure(nj / 8 + 1)) ||
-      (r = c->s_aff.ensure(nj)) || (r = c->s_inf.ensure(nj)) || (r = c->job_code.ensure(nj)) ||
+      (r = c->s_aff.ensure(nj + 1)) || (r = c->s_inf.ensure(nj + 1)) || (r = c->job_code.ensure(nj)) ||
       (r = c->job_result.ensure(nj)) || (r = c->f_part.ensure(4)) || (r = c->flags.ensure(8)))
     return r;
   w.sig_aff = c->sig_aff.p; w.h_aff = c->h_aff.p; w.sig_inf = c->sig_inf.p; w.sig_code = c->sig_code.p;
@@ -1012,6 +1020,14 @@ static int work_alloc_once(bgv_ctx* c, const dev_batch& d, dev_work& w) {
     p.p_cls = c->pm_p.p; p.code_cls = c->pm_code.p; p.h_cls = c->pm_h.p;
     p.ident = c->flags.p + 1;
   }
+  // batch-first tail: one extra slot of s_aff / s_inf / f_set above, the window tree and the step folds here
+  w.win_tmp = nullptr; w.f_fold = nullptr;
+  if (d.batch_tail) {
+    if ((r = c->win_tmp.ensure(16 * tail_entries(J, WIN_FAN))) ||
+        (r = c->f_fold.ensure(tail_entries(miller_items_bound(d, d.steps_slice), FOLD_FAN) * MILLER_STEPS)))
+      return r;
+    w.win_tmp = c->win_tmp.p; w.f_fold = c->f_fold.p;
+  }
   w.msm_bucket = nullptr; w.msm_mask = nullptr; w.msm_win = nullptr;
   if (d.msm == 2) {
     if ((r = c->msm_bucket.ensure(nj * 16 * 15)) || (r = c->msm_mask.ensure(nj * 16)) || (r = c->msm_win.ensure(nj * 16))) return r;
@@ -1076,6 +1092,8 @@ static int run_stages(bgv_ctx* c, const dev_batch& d, const dev_work& w, int fro
     c->pair_pending = merge;  // pairs = the class count, home with the results
     c->pair_redo = false;
   }
+  c->tail_d = dv;
+  c->tail_w = wv;
   auto launch_one = [&](int s) -> int {
     hipStream_t st = c->st;
     // fixed-argument lines: right behind the hash on its stream, before the
@@ -1091,18 +1109,27 @@ static int run_stages(bgv_ctx* c, const dev_batch& d, const dev_work& w, int fro
       if (s == ST_S_TREE || s == ST_MILLER) HIPCHK(hipStreamWaitEvent(st, dep[ST_PK_SCALE], 0));
       if (s == ST_F_TREE) HIPCHK(hipStreamWaitEvent(st, dep[ST_MILLER], 0));
     }
+
     // maps launched early on st_hash: a hash stage on another stream (a run
     // that does not fork, e.g. bgv_debug_stages' first range) waits for them
     if (s == ST_HASH && d.maps_early && st != c->st_hash) HIPCHK(hipStreamWaitEvent(st, c->ev_maps, 0));
     if (timed) HIPCHK(hipEventRecord(c->ev[s], st));
     // deferred subgroup checks: their verdicts enter the codes before the fold
-    if (s == ST_F_TREE && d.defer_grp) {
+    if (s == ST_F_TREE && d.defer_grp && !d.batch_tail) {
       if (fork) HIPCHK(hipStreamWaitEvent(st, c->ev_grp, 0));
       launch_sig_fixup(st, d, w);
     }
     if (s == ST_HASH && classes) launch_hash_classes(st, c->mc);  // bgv_dedup.hip: the representatives, then the copies
-    else if (merge && (s == ST_MILLER || s == ST_F_TREE)) launch_stage(st, s, dv, wv);
+    else if (merge && (s == ST_MILLER || s == ST_F_TREE || (s == ST_BATCH_FINAL && d.batch_tail))) launch_stage(st, s, dv, wv);
     else launch_stage(st, s, d, w);
+    // batch-first tail: the batch sum above ran over the codes k_msm_window left, beside the Miller stage and the
+    // checks.  Their verdicts enter the codes here, and the sum runs again only if one of them rejected a job
+    // (on the device: FLAG_CODES_KEPT); the main stream carries no Miller work, so the wait costs the fold nothing
+    if (s == ST_MILLER_JOBS && d.defer_grp && d.batch_tail) {
+      if (fork) HIPCHK(hipStreamWaitEvent(st, c->ev_grp, 0));
+      launch_sig_fixup(st, d, w);
+      launch_batch_sig_redo(st, d, w);
+    }
     if (merge && s == ST_HASH) launch_pair_h(st, c->pc, w.h_aff);  // H(m) per class, for the class lines / the loops
     // P_c per class, in front of whatever waits for the scaled keys
     if (merge && s == ST_PK_SCALE) launch_pair_sum(st, c->pc, w.rpk_aff, w.pk_code);
@@ -1207,6 +1234,7 @@ static int finish_results(bgv_ctx* c, const dev_batch& d, const dev_work& w, int
   c->staged_pending = false;
   uint32_t flag = 0;
   memcpy(&flag, c->pin_out, 4);
+  c->tail_path = {d.batch_tail ? 1u : 0u, d.batch_tail && d.n_jobs && !flag ? 1u : 0u};
   if (want_pair) {
     uint32_t ident = 0;
     memcpy(&c->pair_path.pairs, c->pin_out + 68, 4);
@@ -1279,6 +1307,15 @@ static int run_and_finish(bgv_ctx* c, const dev_batch& d, const dev_work& w, int
   return 0;
 }
 
+// The batch-first tail: the entries whose verdicts come
+// from k_batch_final / k_job_final over a batch on the steps path with the
+// (job, window) MSM (the window sums it folds).  Called between prepare() and
+// work_alloc(); every other entry leaves dev_batch.batch_tail at 0, and with
+// it today's tail (the debug entries report per-job values).
+static void tail_entry(const bgv_ctx* c, dev_batch& d) {
+  d.batch_tail = c->batch_tail != 0 && d.steps_slice && d.msm == 2 && !d.steps_dbg && d.n_jobs ? 1u : 0u;
+}
+
 int bgv_verify(bgv_ctx* c, const bgv_batch* b, int32_t* job_result, int32_t* set_code, bgv_stats* stats) {
   if (!c || !b || (!job_result && b->n_jobs)) return fail(BGV_E_INVALID_ARG, "null argument");
   c->partial_pending = false;
@@ -1287,6 +1324,7 @@ int bgv_verify(bgv_ctx* c, const bgv_batch* b, int32_t* job_result, int32_t* set
   pair_entry pe(c, c->pair_merge != 0);
   dev_batch d;
   if (int r = prepare(c, b, d, true)) return r;
+  tail_entry(c, d);
   dev_work w;
   if (int r = work_alloc(c, d, w)) return r;
   return run_and_finish(c, d, w, job_result, set_code, stats);
@@ -1296,6 +1334,19 @@ int bgv_pair_merge(bgv_ctx* c, int32_t mode) {
   if (!c) return fail(BGV_E_INVALID_ARG, "null ctx");
   if (mode != 0 && mode != 1) return fail(BGV_E_INVALID_ARG, "bgv_pair_merge mode %d", mode);
   c->pair_merge = mode;
+  return BGV_OK;
+}
+
+int bgv_batch_tail(bgv_ctx* c, int32_t mode) {
+  if (!c) return fail(BGV_E_INVALID_ARG, "null ctx");
+  if (mode < -1 || mode > 1) return fail(BGV_E_INVALID_ARG, "bgv_batch_tail mode %d", mode);
+  c->batch_tail = mode;
+  return BGV_OK;
+}
+
+int bgv_tail_stats(bgv_ctx* c, bgv_tail_path* out) {
+  if (!c || !out) return fail(BGV_E_INVALID_ARG, "null argument");
+  *out = c->tail_path;
   return BGV_OK;
 }
 
@@ -1740,6 +1791,7 @@ int bgv_verify_bits(bgv_ctx* c, const bgv_bits_batch* b, int32_t* job_result, in
   dev_batch d;
   if (int r = bits_front(c, b, d, true)) return r;
   if (int r = bits_layout(c, d, b->scalars, b->scalars && !b->on_device)) return r;
+  tail_entry(c, d);
   dev_work w;
   if (int r = work_alloc(c, d, w)) return r;
   return run_and_finish(c, d, w, job_result, set_code, stats);
@@ -2539,6 +2591,7 @@ int bgv_partial(bgv_ctx* c, const bgv_batch* b, uint8_t* miller576, int32_t* set
   active_guard ag(c->device);
   dev_batch d;
   if (int r = prepare(c, b, d, true)) return r;
+  tail_entry(c, d);
   dev_work w;
   pair_entry pe(c, c->pair_merge != 0);
   if (int r = work_alloc(c, d, w)) return r;
@@ -2584,6 +2637,7 @@ int bgv_partial(bgv_ctx* c, const bgv_batch* b, uint8_t* miller576, int32_t* set
   if (ok_out) *ok_out = ok;
   c->part_d = d;
   c->part_w = w;
+  c->tail_path = {d.batch_tail ? 1u : 0u, 0u};
   c->partial_pending = true;
   return BGV_OK;
 }
@@ -2600,7 +2654,9 @@ int bgv_partial_finish(bgv_ctx* c, int32_t* job_result, bgv_stats* stats) {
   c->run_from = 0;
   c->run_to = ST_COUNT;
   HIPCHK(hipEventRecord(c->ev[0], c->st));
-  launch_stage(c->st, ST_BATCH_FINAL, d, w);
+  // batch-first tail: k_batch_final, then the guarded per-job kernels over the view the shard's fold ran over
+  if (d.batch_tail) launch_stage(c->st, ST_BATCH_FINAL, c->tail_d, c->tail_w);
+  else launch_stage(c->st, ST_BATCH_FINAL, d, w);
   launch_stage(c->st, ST_JOB_FINAL, d, w);
   HIPCHK(hipGetLastError());
   HIPCHK(hipEventRecord(c->ev[ST_COUNT], c->st));

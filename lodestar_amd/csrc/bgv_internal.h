@@ -4,6 +4,7 @@
 #include "pairing.h"
 #include "rng.h"
 #include "bits_expand.h"
+#include "batch_tail.h"
 
 namespace bgv {
 
@@ -51,6 +52,9 @@ struct dev_batch {
                             // job recurrence (bgv_cfg.miller_steps); 0: the item loop (k_miller)
   uint32_t steps_dbg;       // bgv_debug_stages on the steps path: k_job_chain also leaves the job's set product at
                             // f_set[first set] and 1 at its other sets
+  uint32_t batch_tail;      // steps path: the batch-first tail (bgv_batch_tail): the batch verdict comes from ONE (-G1,
+                            // S_batch) pair and ONE recurrence over the step products of all slices; the per-job sums,
+                            // pairs and chains run behind k_batch_final and only when it failed
   const uint32_t* job_off;
   const uint32_t* pk_off;
   const uint32_t* pk_idx;
@@ -88,11 +92,13 @@ struct dev_work {
   uint32_t* set_job;  // job id of every set
   uint32_t* item_off; // [n_jobs + 1] scan of Miller work items per job (2 sets each)
   uint32_t* item_job; // job of every Miller work item
-  g2a* s_aff;         // per job: sum [r_i] sigma_i, affine
+  g2j* win_tmp;       // batch-first tail: the window sums over the jobs, two regions (launch_batch_sig)
+  g2a* s_aff;         // per job: sum [r_i] sigma_i, affine; slot n_jobs: S_batch (batch-first tail)
   uint32_t* s_inf;
   fp2_t* lines;       // [68 steps][3][n_sets] unevaluated Miller lines of H(m_i) (dev_batch.lines)
   fp12_t* f_step;     // [items][68] per (slice, step) line products (dev_batch.steps_slice)
-  fp12_t* f_set;      // per pair Miller value: n_sets set pairs, then n_jobs (-G1, S_job) pairs
+  fp12_t* f_fold;     // batch-first tail: per-step products over groups of slices, two regions (launch_batch_chain)
+  fp12_t* f_set;      // per pair Miller value: n_sets set pairs, then n_jobs (-G1, S_job) pairs, then (-G1, S_batch)
   fp12_t* f_job;      // per-job Miller product (incl. the -G1 pair)
   fp12_t* f_batch;    // batch product scratch [n_jobs]; the product ends in f_batch[0]
   fp12_t* f_tmp;      // batch fold ping-pong [ceil(n_jobs / 8)]
@@ -100,8 +106,10 @@ struct dev_work {
   int32_t* job_result;
   int32_t* set_code;
   fp12_t* f_part;     // conversion scratch for partials
-  uint32_t* flags;    // [0] = whole batch verified
+  uint32_t* flags;    // [0] = whole batch verified; [1] pair classes: an identity class; [FLAG_CODES_KEPT]; [4] bgv_combine_final
 };
+// batch-first tail under deferred checks: 1 while no check has rejected a job that k_msm_window (job_code16) accepted
+constexpr uint32_t FLAG_CODES_KEPT = 2;
 
 enum Stage {
   ST_SIG = 0,
@@ -166,6 +174,8 @@ void launch_msm_job_coop(hipStream_t st, const dev_batch& b, const dev_work& w);
 void launch_pk_coop(hipStream_t st, const dev_batch& b, const dev_work& w);  // bgv_latency.hip
 void launch_miller_kv(hipStream_t st, const dev_batch& b, const dev_work& w);  // bgv_miller.hip
 void launch_fp12_tail(hipStream_t st, int stage, const dev_batch& b, const dev_work& w);  // bgv_tail.hip
+void launch_batch_sig_redo(hipStream_t st, const dev_batch& b, const dev_work& w);  // batch-first tail, behind launch_sig_fixup
+void launch_job_chain_retry(hipStream_t st, const dev_batch& b, const dev_work& w);  // k_job_chain behind flags[0]
 void launch_combine_final(hipStream_t st, const fp12_t* parts, uint32_t n, uint32_t* flag);
 void launch_final_exp_many(hipStream_t st, const fp12_t* in, fp12_t* out, uint32_t n);  // bgv_debug_stages
 void launch_export_g1a(hipStream_t st, const g1a* in, uint8_t* out96, uint32_t n);

@@ -308,6 +308,7 @@ __global__ void BGV_BULK k_job_recode(dev_batch b, dev_work w) {
   if (code == was) return;
   w.job_code[j] = code;
   if (was != C_OK) return;  // rejected at decode time: S_job and its pair are already the identity
+  if (b.batch_tail) w.flags[FLAG_CODES_KEPT] = 0u;  // S_batch was summed with this job in it: launch_batch_sig runs again
   g2a z;
   z.x = fp2_zero();
   z.y = fp2_zero();
@@ -524,10 +525,39 @@ __global__ void BGV_BULK k_msm_bucket(dev_batch b, dev_work w) {
   w.msm_mask[t] = mask;
 }
 
+// The job codes for the batch-first tail (dev_batch.batch_tail), whose batch
+// sum waits for them, on the 16 lanes k_msm_window has per job: lane l scans
+// the sets l, l + 16, ... for the job's first failing signature and first
+// failing pubkey, then a minimum over the 16 lanes (first failing set,
+// signatures before pubkeys, as k_job_code).  A kernel of its own cost the
+// chain a launch that waits ~3 ms for SIMD slots beside k_miller_steps.  No
+// identity substitution: S_job is written by the retry's Horner under these
+// codes.  Also arms FLAG_CODES_KEPT.
+__device__ __forceinline__ void job_code16(const dev_batch& b, const dev_work& w, uint32_t j, uint32_t l) {
+  const uint32_t beg = b.job_off[j], end = b.job_off[j + 1];
+  uint32_t bad_sig = 0xffffffffu, bad_pk = 0xffffffffu;
+  for (uint32_t i = beg + l; i < end; i += 16u) {
+    if (bad_sig == 0xffffffffu && w.sig_code[i] != C_OK) bad_sig = i;
+    if (bad_pk == 0xffffffffu && w.pk_code[i] != C_OK) bad_pk = i;
+  }
+  for (uint32_t st = 8; st >= 1; st >>= 1) {
+    bad_sig = min(bad_sig, (uint32_t)__shfl_down((int)bad_sig, st, 16));
+    bad_pk = min(bad_pk, (uint32_t)__shfl_down((int)bad_pk, st, 16));
+  }
+  if (l != 0) return;
+  int32_t code = C_OK;
+  if (bad_sig != 0xffffffffu) code = w.sig_code[bad_sig];
+  else if (bad_pk != 0xffffffffu) code = w.pk_code[bad_pk];
+  if (end == beg) code = C_EMPTY_JOB;
+  w.job_code[j] = code;
+  if (j == 0) w.flags[FLAG_CODES_KEPT] = 1u;  // until k_job_recode rejects a job these codes accepted
+}
+
 // lane = (job, window): S_w = sum_d d B_d = sum_{d'} (sum_{d >= d'} B_d)
 __global__ void BGV_BULK k_msm_window(dev_batch b, dev_work w) {
   const uint32_t t = gtid();
-  if (t >= b.n_jobs * 16u) return;
+  if (t >= b.n_jobs * 16u) return;  // whole 16-lane groups
+  if (b.batch_tail) job_code16(b, w, t >> 4, t & 15u);
   const g2j* bk = w.msm_bucket + (size_t)t * 15u;
   const uint32_t mask = w.msm_mask[t];
   g2j run, tot;
@@ -610,21 +640,36 @@ __global__ void BGV_BULK k_msm_digit(dev_batch b, dev_work w) {
 // doubles its window sum 4 w times, then a tree over the job's 16 lanes
 // (cross-lane shuffles): 60 doublings + 4 additions on the chain instead of a
 // one-lane Horner's 60 doublings + 15 additions
-__global__ void BGV_BULK k_msm_job(dev_batch b, dev_work w) {
+//
+// mode (the batch-first tail, dev_batch.batch_tail, splits the two halves):
+//   MSM_JOB_ALL    the job code and the Horner (every other layout);
+//   MSM_JOB_HORNER the Horner alone under the code k_msm_window / k_job_recode
+//                  left (the retry path; `skip` set and *skip != 0: return);
+//   MSM_JOB_BATCH  one virtual job n_jobs over the window sums `win`
+//                  (k_win_fold): S_batch into slot n_jobs of s_aff / s_inf.
+enum : uint32_t { MSM_JOB_ALL = 0, MSM_JOB_HORNER = 1, MSM_JOB_BATCH = 2 };
+__global__ void BGV_BULK k_msm_job(dev_batch b, dev_work w, uint32_t mode, const g2j* win_src, const uint32_t* skip) {
+  if (skip && *skip) return;  // uniform over the grid
   const uint32_t t = gtid();
-  const uint32_t j = t >> 4, win = t & 15u;
-  if (j >= b.n_jobs) return;  // whole 16-lane groups (n_jobs * 16 lanes)
-  const uint32_t beg = b.job_off[j], end = b.job_off[j + 1];
+  uint32_t j = t >> 4;
+  const uint32_t win = t & 15u;
+  if (j >= (mode == MSM_JOB_BATCH ? 1u : b.n_jobs)) return;  // whole 16-lane groups (n_jobs * 16 lanes)
   int32_t code = C_OK;
-  for (uint32_t i = beg; i < end && code == C_OK; i++) code = w.sig_code[i];
-  for (uint32_t i = beg; i < end && code == C_OK; i++) code = w.pk_code[i];
-  if (end == beg) code = C_EMPTY_JOB;
+  if (mode == MSM_JOB_ALL) {
+    const uint32_t beg = b.job_off[j], end = b.job_off[j + 1];
+    for (uint32_t i = beg; i < end && code == C_OK; i++) code = w.sig_code[i];
+    for (uint32_t i = beg; i < end && code == C_OK; i++) code = w.pk_code[i];
+    if (end == beg) code = C_EMPTY_JOB;
+  } else if (mode == MSM_JOB_HORNER) {
+    code = w.job_code[j];
+  }
   g2j s;
   jac_set_inf(s);
   if (code == C_OK) {
-    s = w.msm_win[16u * j + win];
+    s = mode == MSM_JOB_BATCH ? win_src[win] : w.msm_win[16u * j + win];
     for (uint32_t k = 0; k < 4u * win; k++) jac_dbl(s, s);
   }
+  if (mode == MSM_JOB_BATCH) j = b.n_jobs;
   for (uint32_t st = 8; st >= 1; st >>= 1) {
     g2j o;
     shfl_down16(o, s, st);
@@ -638,7 +683,27 @@ __global__ void BGV_BULK k_msm_job(dev_batch b, dev_work w) {
   if (code == C_OK) inf = jac_to_aff(sa, s) ? 0u : 1u;
   w.s_aff[j] = sa;
   w.s_inf[j] = inf;
-  w.job_code[j] = code;
+  if (mode == MSM_JOB_ALL) w.job_code[j] = code;
+}
+
+// batch-first tail: W_w = the sum over the accepted jobs of msm_win[16 j + w],
+// as a tree of fan-in WIN_FAN with lane = (group, window).  Level 0 leaves out
+// the jobs whose code is not C_OK (after k_job_recode: the late rejects too);
+// dst holds 16 ceil(n / WIN_FAN) sums.
+__global__ void BGV_BULK k_win_fold(dev_work w, const g2j* src, uint32_t n, g2j* dst, uint32_t level0, const uint32_t* skip) {
+  if (skip && *skip) return;  // uniform over the grid
+  const uint32_t t = gtid();
+  const uint32_t g = t >> 4, win = t & 15u;
+  if (g >= (n + WIN_FAN - 1) / WIN_FAN) return;
+  const uint32_t end = min(n, WIN_FAN * g + WIN_FAN);
+  g2j acc;
+  jac_set_inf(acc);
+  for (uint32_t j = WIN_FAN * g; j < end; j++) {
+    if (level0 && w.job_code[j] != C_OK) continue;
+    const g2j v = src[16u * j + win];
+    jac_add(acc, acc, v);
+  }
+  dst[16u * g + win] = acc;
 }
 
 // ------------------------------------------ fused per-job MSM (msm mode)
@@ -847,8 +912,10 @@ __global__ void BGV_BULK k_item_job(dev_batch b, dev_work w) {
 // 6 x SUB x HALF lanes per pair; pair t < n_sets is (r_t PK_t, H(m_t)), then
 // (-G1, S_job).
 template <int SUB, int HALF>
-__global__ void __launch_bounds__(64, BGV_WAVES) k_miller_coop(dev_batch b, dev_work w, uint32_t first, uint32_t count) {
+__global__ void __launch_bounds__(64, BGV_WAVES) k_miller_coop(dev_batch b, dev_work w, uint32_t first, uint32_t count,
+                                                                      const uint32_t* skip) {
   using cfg = coop_cfg<SUB, HALF>;
+  if (skip && *skip) return;  // the batch-first tail's retry launch: the batch verified (uniform over the grid)
   __shared__ coop_grp_t<SUB, HALF> sm[cfg::GROUPS];
   const uint32_t lane = threadIdx.x, grp = lane / cfg::LANES;
   const uint32_t r = lane % cfg::LANES;
@@ -868,7 +935,8 @@ __global__ void __launch_bounds__(64, BGV_WAVES) k_miller_coop(dev_batch b, dev_
       Q = w.h_aff[t];
     } else {
       const uint32_t j = t - b.n_sets;
-      active = w.job_code[j] == C_OK && !w.s_inf[j];
+      // slot n_jobs: (-G1, S_batch) of the batch-first tail, under no job's code
+      active = (j >= b.n_jobs || w.job_code[j] == C_OK) && !w.s_inf[j];
       P.x = G1_X_MONT;
       P.y = G1_NEG_Y_MONT;
       Q = w.s_aff[j];
@@ -1173,17 +1241,17 @@ void launch_prep(hipStream_t st, const dev_batch& b, const dev_work& w) {
 // pairs [first, first + count) through the cooperative layout of `lanes`
 // lanes per pair (6, 18 or 36)
 static void launch_miller_coop(hipStream_t st, uint32_t lanes, const dev_batch& b, const dev_work& w, uint32_t first,
-                               uint32_t count) {
+                               uint32_t count, const uint32_t* skip = nullptr) {
   if (!count) return;
   if (lanes == 6) {
     constexpr uint32_t G = coop_cfg<1, 1>::GROUPS;
-    hipLaunchKernelGGL((k_miller_coop<1, 1>), dim3((count + G - 1) / G), dim3(64), 0, st, b, w, first, count);
+    hipLaunchKernelGGL((k_miller_coop<1, 1>), dim3((count + G - 1) / G), dim3(64), 0, st, b, w, first, count, skip);
   } else if (lanes == 18) {
     constexpr uint32_t G = coop_cfg<3, 1>::GROUPS;
-    hipLaunchKernelGGL((k_miller_coop<3, 1>), dim3((count + G - 1) / G), dim3(64), 0, st, b, w, first, count);
+    hipLaunchKernelGGL((k_miller_coop<3, 1>), dim3((count + G - 1) / G), dim3(64), 0, st, b, w, first, count, skip);
   } else {
     constexpr uint32_t G = coop_cfg<3, 2>::GROUPS;
-    hipLaunchKernelGGL((k_miller_coop<3, 2>), dim3((count + G - 1) / G), dim3(64), 0, st, b, w, first, count);
+    hipLaunchKernelGGL((k_miller_coop<3, 2>), dim3((count + G - 1) / G), dim3(64), 0, st, b, w, first, count, skip);
   }
 }
 
@@ -1196,6 +1264,34 @@ void launch_sig_check(hipStream_t st, const dev_batch& b, const dev_work& w) {
 void launch_sig_fixup(hipStream_t st, const dev_batch& b, const dev_work& w) {
   BGV_LAUNCH(k_sig_fix, b.n_sets, b, w);
   BGV_LAUNCH(k_job_recode, b.n_jobs, b, w);
+}
+
+// batch-first tail, ST_MILLER_JOBS: the window sums over the accepted jobs
+// (k_win_fold, ping-ponging the two regions of win_tmp), ONE Horner into slot
+// n_jobs of s_aff / s_inf, ONE pair into slot n_sets + n_jobs of f_set.
+// Under deferred subgroup checks it runs twice: at once, over the codes of
+// k_msm_window, beside the Miller stage; and again behind k_job_recode, every
+// workgroup returning at once unless a check rejected a job the first pass
+// summed (launch_batch_sig_redo: skip = FLAG_CODES_KEPT).
+static void launch_batch_sig(hipStream_t st, const dev_batch& b, const dev_work& w, const uint32_t* skip) {
+  if (!b.n_jobs) return;
+  g2j* reg[2] = {w.win_tmp, w.win_tmp + 16u * tail_region1(b.n_jobs, WIN_FAN)};
+  const g2j* src = w.msm_win;
+  uint32_t n = b.n_jobs, lvl = 0;
+  do {
+    const uint32_t groups = tail_groups(n, WIN_FAN);
+    g2j* dst = reg[lvl & 1u];
+    BGV_LAUNCH(k_win_fold, groups * 16u, w, src, n, dst, lvl == 0 ? 1u : 0u, skip);
+    src = dst;
+    n = groups;
+    lvl++;
+  } while (n > 1);
+  BGV_LAUNCH(k_msm_job, 16u, b, w, MSM_JOB_BATCH, src, skip);
+  launch_miller_coop(st, b.job_lanes, b, w, b.n_sets + b.n_jobs, 1u, skip);
+}
+
+void launch_batch_sig_redo(hipStream_t st, const dev_batch& b, const dev_work& w) {
+  launch_batch_sig(st, b, w, w.flags + FLAG_CODES_KEPT);
 }
 
 void launch_stage(hipStream_t st, int stage, const dev_batch& b, const dev_work& w) {
@@ -1262,8 +1358,8 @@ void launch_stage(hipStream_t st, int stage, const dev_batch& b, const dev_work&
         // the latency mode; bulk batches keep the 16-lane one-lane form
         if ((b.msm == 4 && BGV_MSM_JOB_COOP) || (b.msm == 2 && BGV_MSM_JOB_COOP_BULK))
           launch_msm_job_coop(st, b, w);
-        else
-          BGV_LAUNCH(k_msm_job, b.n_jobs * 16u, b, w);
+        else if (!b.batch_tail)  // batch-first tail: k_msm_window left the codes; the sums wait for the batch sum or the retry
+          BGV_LAUNCH(k_msm_job, b.n_jobs * 16u, b, w, MSM_JOB_ALL, (const g2j*)nullptr, (const uint32_t*)nullptr);
         break;
       }
       if (b.msm == 1) {
@@ -1302,7 +1398,8 @@ void launch_stage(hipStream_t st, int stage, const dev_batch& b, const dev_work&
       // always the cooperative loop: one pair per job is latency-bound (a lone
       // lane takes ~19 ms at C4, the cooperative loop ~5 ms) and its waves
       // fit on the SIMDs the set-pair kernel leaves free
-      if (b.n_jobs)
+      if (b.batch_tail) launch_batch_sig(st, b, w, nullptr);  // one pair: (-G1, S_batch)
+      else if (b.n_jobs)
         launch_miller_coop(st, b.job_lanes, b, w, b.n_sets, b.n_jobs);
       break;
     case ST_F_TREE:
@@ -1312,6 +1409,15 @@ void launch_stage(hipStream_t st, int stage, const dev_batch& b, const dev_work&
       launch_fp12_tail(st, stage, b, w);
       break;
     case ST_BATCH_FINAL:
+      launch_fp12_tail(st, stage, b, w);
+      if (b.batch_tail && b.n_jobs) {
+        // the retry path, enqueued behind the verdict and returning at once when it is "verified" (flags[0]):
+        // the per-job sums, pairs and chains k_job_final reads after a failed batch check
+        BGV_LAUNCH(k_msm_job, b.n_jobs * 16u, b, w, MSM_JOB_HORNER, (const g2j*)nullptr, (const uint32_t*)w.flags);
+        launch_miller_coop(st, b.job_lanes, b, w, b.n_sets, b.n_jobs, w.flags);
+        launch_job_chain_retry(st, b, w);  // bgv_tail.hip
+      }
+      break;
     case ST_JOB_FINAL: launch_fp12_tail(st, stage, b, w); break;
     case ST_SET_CODES: BGV_LAUNCH(k_set_codes, b.n_sets, b, w); break;
     default: break;

@@ -114,10 +114,13 @@ __global__ void COOP_LB k_job_fold(dev_batch b, dev_work w, uint32_t stride) {
 // steps_dbg (bgv_debug_stages): the set product goes to f_set[first set] and 1
 // to the job's other sets, 1 to all of them when a pubkey of the job was
 // rejected: the item rule of k_miller with the job as the item.
-__global__ void COOP_LB k_job_chain(dev_batch b, dev_work w) {
+// skip (the batch-first tail's retry launch): non-null and *skip != 0, the
+// batch verified and nobody reads f_job: every workgroup returns at once.
+__global__ void COOP_LB k_job_chain(dev_batch b, dev_work w, const uint32_t* skip) {
   __shared__ cscratch s;
   __shared__ wfp12 acc, x, y;
   __shared__ uint32_t bad_pk;
+  if (skip && *skip) return;  // uniform over the grid
   const uint32_t j = blockIdx.x;
   const uint32_t beg = b.job_off[j], end = b.job_off[j + 1];
   const uint32_t t0 = w.item_off[j], t1 = w.item_off[j + 1];
@@ -169,9 +172,9 @@ __global__ void COOP_LB k_job_chain(dev_batch b, dev_work w) {
 
 // workgroup g: dst[g] = prod src[F g .. min(n, F g + F)) with fan-in F; with
 // one workgroup dst may alias src (every read precedes the write).  A
-// fan-in of 8 keeps the chain of sequential Fp12 products short: 1,024 job
-// values fold in 8 + 8 + 8 + 8 + 2 products instead of 32 + 32.
-constexpr uint32_t FOLD_FAN = 8;
+// fan-in of 8 (FOLD_FAN, batch_tail.h) keeps the chain of sequential Fp12
+// products short: 1,024 job values fold in 8 + 8 + 8 + 8 + 2 products instead
+// of 32 + 32.
 __global__ void COOP_LB k_fold(const fp12_t* src, uint32_t n, fp12_t* dst) {
   __shared__ cscratch s;
   __shared__ wfp12 acc, x;
@@ -182,6 +185,57 @@ __global__ void COOP_LB k_fold(const fp12_t* src, uint32_t n, fp12_t* dst) {
     c_mul(&acc, &acc, &x, &s);
   }
   c_store(dst[blockIdx.x], &acc);
+}
+
+// The batch-first tail (dev_batch.batch_tail): the recurrence f <- f^2 L_k is
+// multiplicative in the L_k, so ONE recurrence over L_k = the product of ALL
+// slices' step values equals the product of the per-job chains, as field
+// elements.  k_step_fold folds f_step over the slices with fan-in FOLD_FAN,
+// one workgroup per (group, step); level 0 reads 1 for a slice past the last
+// one (the grid is sized by the host's bound) and for a slice of a rejected
+// job.  k_batch_chain then runs the 68 steps once, conjugates, multiplies by
+// the (-G1, S_batch) value and leaves the batch product in f_batch[0].
+__global__ void COOP_LB k_step_fold(dev_batch b, dev_work w, const fp12_t* src, uint32_t n, fp12_t* dst, uint32_t level0) {
+  __shared__ cscratch s;
+  __shared__ wfp12 acc, x;
+  const uint32_t g = blockIdx.x, k = blockIdx.y;
+  const uint32_t live = level0 ? min(n, w.item_off[b.n_jobs]) : n;
+  const uint32_t beg = g * FOLD_FAN, end = min(live, beg + FOLD_FAN);
+  bool have = false;  // uniform per workgroup, as everything here
+  for (uint32_t t = beg; t < end; t++) {
+    if (level0 && w.job_code[w.item_job[t]] != C_OK) continue;
+    if (!have) {
+      c_load(&acc, src[(size_t)t * MILLER_STEPS + k]);
+      have = true;
+    } else {
+      c_load(&x, src[(size_t)t * MILLER_STEPS + k]);
+      c_mul(&acc, &acc, &x, &s);
+    }
+  }
+  if (!have) c_set_one(&acc);
+  c_store(dst[(size_t)g * MILLER_STEPS + k], &acc);
+}
+
+__global__ void COOP_LB k_batch_chain(dev_batch b, dev_work w, const fp12_t* steps) {
+  __shared__ cscratch s;
+  __shared__ wfp12 acc, x;
+  uint32_t k = 0;
+  for (int bit = 62; bit >= 0; bit--) {
+    const int sub = ((BLS_X_ABS >> bit) & 1ull) ? 2 : 1;
+    for (int a = 0; a < sub; a++, k++) {
+      c_load(&x, steps[k]);
+      if (k == 0) {
+        c_copy(&acc, &x);
+      } else {
+        if (a == 0) c_mul(&acc, &acc, &acc, &s);
+        c_mul(&acc, &acc, &x, &s);
+      }
+    }
+  }
+  c_conj(&acc, &acc);
+  c_load(&x, w.f_set[b.n_sets + b.n_jobs]);
+  c_mul(&acc, &acc, &x, &s);
+  c_store(w.f_batch[0], &acc);
 }
 
 // the whole-batch check: ONE final exponentiation over 128 lanes
@@ -239,14 +293,40 @@ __global__ void COOP_LB k_final_exp_many(const fp12_t* in, fp12_t* out) {
 
 #undef gtid
 
+// the levels ping-pong between the two regions of f_fold; level 0 always runs
+// (it is the one that leaves out the rejected jobs)
+static void launch_batch_chain(hipStream_t st, const dev_batch& b, const dev_work& w) {
+  const dim3 ct(COOP_THREADS);
+  uint32_t n = miller_items_bound(b, b.steps_slice), lvl = 0;
+  fp12_t* reg[2] = {w.f_fold, w.f_fold + tail_region1(n, FOLD_FAN) * MILLER_STEPS};
+  const fp12_t* src = w.f_step;
+  do {
+    const uint32_t groups = tail_groups(n, FOLD_FAN);
+    fp12_t* dst = reg[lvl & 1u];
+    hipLaunchKernelGGL(k_step_fold, dim3(groups, MILLER_STEPS), ct, 0, st, b, w, src, n, dst, lvl == 0 ? 1u : 0u);
+    src = dst;
+    n = groups;
+    lvl++;
+  } while (n > 1);
+  hipLaunchKernelGGL(k_batch_chain, dim3(1), ct, 0, st, b, w, src);
+}
+
+void launch_job_chain_retry(hipStream_t st, const dev_batch& b, const dev_work& w) {
+  if (b.n_jobs) hipLaunchKernelGGL(k_job_chain, dim3(b.n_jobs), dim3(COOP_THREADS), 0, st, b, w, (const uint32_t*)w.flags);
+}
+
 void launch_fp12_tail(hipStream_t st, int stage, const dev_batch& b, const dev_work& w) {
   const uint32_t span = 1u << b.span_log2;
   auto grid = [](uint32_t n) { return dim3((n + 63u) / 64u); };
   const dim3 ct(COOP_THREADS);
   if (stage == ST_F_TREE) {
     if (!b.n_jobs) return;
+    if (b.batch_tail) {  // one recurrence over the step products of all slices
+      launch_batch_chain(st, b, w);
+      return;
+    }
     if (b.steps_slice) {  // per-step line products: the job's recurrence over them
-      hipLaunchKernelGGL(k_job_chain, dim3(b.n_jobs), ct, 0, st, b, w);
+      hipLaunchKernelGGL(k_job_chain, dim3(b.n_jobs), ct, 0, st, b, w, (const uint32_t*)nullptr);
       return;
     }
     if (span <= 256) {  // every job folds in one workgroup
@@ -263,6 +343,7 @@ void launch_fp12_tail(hipStream_t st, int stage, const dev_batch& b, const dev_w
       for (uint32_t s = 1; s < span; s *= 2) hipLaunchKernelGGL(k_f_level, grid(b.n_sets), dim3(64), 0, st, b, w, s);
     hipLaunchKernelGGL(k_job_f, grid(b.n_jobs), dim3(64), 0, st, b, w, span);
   } else if (stage == ST_BATCH_PROD) {
+    if (b.batch_tail) return;  // k_batch_chain left the product in f_batch[0]
     // fold by FOLD_FAN, ping-ponging f_batch <-> f_tmp, the product landing in f_batch[0]
     uint32_t n = b.n_jobs;
     fp12_t* src = w.f_batch;

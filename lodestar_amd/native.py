@@ -61,6 +61,7 @@ EXPORTS = [
     "bgv_hash_stats", "bgv_miller_path_stats",
     "bgv_verify_same_message_aggregate", "bgv_sm_agg_check", "bgv_sm_agg_ms",
     "bgv_pair_merge", "bgv_pair_stats", "bgv_debug_pair_classes",
+    "bgv_batch_tail", "bgv_tail_stats",
 ]
 MAX_INDEX_LISTS = 8
 SRC_EXPLICIT = 0xFFFFFFFF
@@ -288,6 +289,14 @@ class BgvMillerPath(ctypes.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
+class BgvTailPath(ctypes.Structure):
+    """bgv_tail_path (include/bgv.h): the tail the last ordinary batch ran"""
+    _fields_ = [("batch_first", ctypes.c_uint32), ("retried", ctypes.c_uint32)]
+
+    def as_dict(self) -> dict:
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
 class BgvPairPath(ctypes.Structure):
     """bgv_pair_path (include/bgv.h): the set pairs the Miller stage of the last ordinary batch ran"""
     _fields_ = [("sets", ctypes.c_uint32), ("pairs", ctypes.c_uint32), ("merged", ctypes.c_uint32),
@@ -400,6 +409,8 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
             "bgv_miller_path_stats": ([P, ctypes.POINTER(BgvMillerPath)], ctypes.c_int),
             "bgv_pair_merge": ([P, ctypes.c_int32], ctypes.c_int),
             "bgv_pair_stats": ([P, ctypes.POINTER(BgvPairPath)], ctypes.c_int),
+            "bgv_batch_tail": ([P, ctypes.c_int32], ctypes.c_int),
+            "bgv_tail_stats": ([P, ctypes.POINTER(BgvTailPath)], ctypes.c_int),
             "bgv_debug_pair_classes": ([P, ctypes.POINTER(BgvBatch), P, P, P, P, P, P, P], ctypes.c_int),
             "bgv_bits_plan": ([ctypes.POINTER(BgvBitsBatch), P, P, P, ctypes.POINTER(ctypes.c_uint64)], ctypes.c_int),
             "bgv_debug_bits_keys": ([P, ctypes.POINTER(BgvBitsBatch), P, P, P], ctypes.c_int),
@@ -889,6 +900,18 @@ class Device:
         any other entry"""
         out = BgvPairPath()
         self._check(self.lib.bgv_pair_stats(self.h, ctypes.byref(out)))
+        return out.as_dict()
+
+    def batch_tail(self, mode) -> None:
+        """bgv_batch_tail: the batch-first tail of the steps path, from the next call on:
+        -1 auto (on wherever the steps path is), 0 off, 1 on."""
+        self._check(self.lib.bgv_batch_tail(self.h, int(mode)))
+
+    def tail_path(self) -> dict:
+        """bgv_tail_stats: {batch_first, retried} of the last verify, verify_bits or partial
+        (+ partial_finish) on the context"""
+        out = BgvTailPath()
+        self._check(self.lib.bgv_tail_stats(self.h, ctypes.byref(out)))
         return out.as_dict()
 
     def debug_pair_classes(self, arrays: dict, on_device: bool = False) -> dict:

@@ -156,7 +156,7 @@ int main(int argc, char** argv) {
     for (int k = 0; k < 12; k++) { fp_t u, v; fp_from_mont(u, x[k]); fp_from_mont(v, y[k]); if (memcmp(&u, &v, sizeof u)) steps_mismatch++; }
   }
   // per-job bucket MSM of the signatures (bgv_kernels.hip k_msm_*), one 98-set job
-  double msm_c = 0, msm_bucket_c = 0;
+  double msm_c = 0, msm_bucket_c = 0, msm_window_c = 0, g2dbl_c = 0, sqr12_c = 0;
   {
     g2a pts[per_block];
     g2j acc; jac_from_aff(acc, hsa);
@@ -183,10 +183,19 @@ int main(int argc, char** argv) {
       for (int d = 15; d >= 1; d--) { if ((mask >> d) & 1u) jac_add(run, run, bk[d - 1]); jac_add(tot, tot, run); }
       win[w] = tot;
     }
+    msm_window_c = (double)bgv_fpmul_count / per_block - msm_bucket_c;  // k_msm_window alone
     g2j s = win[15];
     for (int w = 14; w >= 0; w--) { for (int k = 0; k < 4; k++) jac_dbl(s, s); jac_add(s, s, win[w]); }
     g2a sa; jac_to_aff(sa, s);
     msm_c = (double)bgv_fpmul_count / per_block;
+    // the batch-first tail's other components: one G2 doubling, one dense Fp12 squaring
+    bgv_fpmul_count = 0;
+    jac_dbl(s, s);
+    g2dbl_c = (double)bgv_fpmul_count;
+    fp12_t q; fp12_one(q); q.c1.c1 = sa.x; q.c0.c2 = sa.y;  // any dense value: the count does not depend on it
+    bgv_fpmul_count = 0;
+    fp12_sqr(q, q);
+    sqr12_c = (double)bgv_fpmul_count;
   }
   sig_c /= reps; sig_dec_c /= reps; hash_c /= reps; pk_add_c /= reps; pk_fix_c /= reps; sig_scale_c /= reps; miller_c /= reps; miller2_c /= reps; lines_c /= reps; loopl2_c /= reps; loopl4_c /= reps;
   fmul_c /= reps; g2add_c /= reps; aff2_c /= reps;
@@ -230,7 +239,25 @@ int main(int argc, char** argv) {
   printf(" \"per_set_total_steps\": %.1f,\n", sig_c + hash_c + pk_c + msm_c + lines_c + steps_loop_c + miller_jobs + steps_tree_c);
   printf(" \"per_set_total\": %.1f,\n", sig_c + hash_c + pk_c + msm_c + miller_set + miller_jobs + f_tree);
   printf(" \"per_set_total_lines\": %.1f,\n", sig_c + hash_c + pk_c + msm_c + lines_c + loopl2_c / 2.0 + miller_jobs + f_tree);
-  printf(" \"per_set_total_lines4\": %.1f\n}\n", sig_c + hash_c + pk_c + msm_c + lines_c + loopl4_c * 25.0 / per_block + miller_jobs +
+  printf(" \"per_set_total_lines4\": %.1f,\n", sig_c + hash_c + pk_c + msm_c + lines_c + loopl4_c * 25.0 / per_block + miller_jobs +
          fmul_c * 25.0 / per_block);
+  // the batch-first tail of the steps path (bgv_batch_tail) at C4, per set of the
+  // 1,024 x 98-set batch: the window sums per job as before, then ONE tree over the jobs (k_win_fold), ONE
+  // Horner (k_msm_job's 16 lanes: 4 w doublings per lane and a 15-addition tree) and ONE affine conversion;
+  // ONE (-G1, S_batch) pair; the folds of the step values over all slices (k_step_fold: items - 1 products
+  // per step), ONE chain and the product by the pair.  per_job_tail: the same three stages of the per-job tail.
+  {
+    const double J = 1024.0, sets = J * per_block;
+    const double items = J * miller_item_count(per_block, steps_G);
+    const double bt_sum = msm_window_c + (16.0 * (J - 1.0) * g2add_c + 480.0 * g2dbl_c + 15.0 * g2add_c + aff2_c) / sets;
+    const double bt_pair = miller_c / sets;
+    const double bt_tree = (MILLER_STEPS * (items - 1.0) * fmul_c + 62.0 * sqr12_c + 67.0 * fmul_c + fmul_c) / sets;
+    printf(" \"per_set_batch_tail\": {\"jobs\": %.0f, \"slice_sets\": %u, \"sig_sum_tree\": %.2f, \"miller_loop_jobs\": %.3f, "
+           "\"miller_product_tree\": %.2f, \"per_job_tail\": {\"sig_sum_tree\": %.2f, \"miller_loop_jobs\": %.2f, "
+           "\"miller_product_tree\": %.2f}, \"saved\": %.2f},\n",
+           J, steps_G, bt_sum, bt_pair, bt_tree, s_tree, miller_jobs, steps_tree_c,
+           s_tree + miller_jobs + steps_tree_c - bt_sum - bt_pair - bt_tree);
+    printf(" \"per_set_total_batch_tail\": %.1f\n}\n", sig_c + hash_c + pk_c + msm_bucket_c + lines_c + steps_loop_c + bt_sum + bt_pair + bt_tree);
+  }
   return 0;
 }

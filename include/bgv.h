@@ -821,6 +821,79 @@ int bgv_debug_same_message_bits(bgv_ctx* ctx, const bgv_smb_batch* batch, uint8_
                                 bgv_sm_stats* stats, uint8_t* pk_set96, uint8_t* path, uint8_t* p_group96,
                                 uint8_t* s_group192, uint8_t* h_group192);
 
+/* ---- same-message retry that localises failing sets by subset checks ---------
+ * The retry of the four same-message entries (bgv_verify_same_message,
+ * _aggregate, _agg, _bits) decides every surviving set of every failing segment
+ * as a one-set job of the ordinary pipeline: the set is decoded, subgroup-
+ * checked and hashed a second time, scaled, paired twice and gets a final
+ * exponentiation of its own.  A remote peer controls how often that happens.
+ *
+ * bgv_sm_retry(ctx, 1) switches the context to the split retry.  It uses only
+ * what the first pass left on the device (the decoded signatures, the keys and
+ * H(m_g)), so it decodes and hashes nothing:
+ *  - A retried segment's m surviving sets, in set order, are cut into subs: m
+ *    subs of one set when m <= BGV_SM_SUB, else ceil(m / BGV_SM_SUB) subs of
+ *    BGV_SM_SUB sets with a shorter last one (bgv_sm_split_plan).
+ *  - Level 1: per sub P = sum r_i pk_i and S = sum r_i sigma_i with the batch's
+ *    scalars, and the check e(P, H(m_g)) e(-G1, S) == 1, all subs of the call
+ *    as one virtual batch.  A passing sub makes its sets valid; a failing sub
+ *    of one set makes it invalid (the scaled check is the unscaled one raised
+ *    to r_i != 0).  A sub whose P is the identity skips its pair and counts as
+ *    failed, as a segment does.
+ *  - Level 2: every set of a failing sub of two or more sets is a leaf,
+ *    e(pk_i, H(m_g)) e(-G1, sigma_i) == 1 unscaled, all leaves as one virtual
+ *    batch.  Leaf verdicts are exact.
+ * set_valid, set_code, every field of bgv_sm_stats but total_ms and the
+ * outputs of bgv_verify_same_message_aggregate are those of mode 0
+ * (sets_retried stays "surviving sets of retried segments", pairs the first
+ * pass's).  The one place where the modes can differ: a caller who injects
+ * scalars chosen so that the faults of one sub cancel (sum r_i (sigma_i -
+ * sk_i H(m)) = 0 over the sub) has that sub accepted where mode 0 would have
+ * opened it, exactly as the faults of a whole segment can cancel in either
+ * mode.  With the scalars the library draws this has probability 2^-64 per sub
+ * check, the bound the whole-batch check rests on.
+ *
+ * When it pays (one MI355X, host batches, wrong-message
+ * faults, mode 0 and mode 1 alternating on one context, p50 over three
+ * repeats of 20 calls; mode 0's run-to-run spread is 0.01 to 0.17 ms):
+ *   31,232 sets (64 groups of 488, one slot), 1 % faults: 71.3 -> 39.5 ms;
+ *                                             0.1 % faults: 25.0 -> 24.3 ms;
+ *   4,096 sets (64 groups of 64),             1 % faults: 22.8 -> 22.7 ms, level
+ *                                             (inside the spread);
+ *                                             0.1 % faults (4 bad sets):
+ *                                             16.6 -> 22.1 ms, 5.5 ms SLOWER.
+ * Clean calls are level at both shapes (8.7 and 10.6 ms): the first pass is
+ * untouched.  Each level is a chain of lone-wave kernels that takes about
+ * 6.7 ms however few subs it holds, so the mode pays where many segments fail
+ * (a slot's worth of committees, many faults) and costs where a few sets of a
+ * small batch do.  That is why it is opt-in and the default stays mode 0.
+ * Not measured: batches in flight beside the call, on-device inputs, fault
+ * rates above 1 %, the aggregate-set entries. */
+/* mode: 0 per-set retry through the ordinary pipeline (default, as before),
+ * 1 split retry; any other value or a null ctx: BGV_E_INVALID_ARG.  From the next call on. */
+int bgv_sm_retry(bgv_ctx* ctx, int32_t mode);
+
+typedef struct bgv_sm_retry_path {
+  uint32_t mode;         /* the mode the last same-message call ran its retry in */
+  uint32_t segments;     /* segments that went to the retry (failed, or P_seg the identity) */
+  uint32_t subs;         /* subs formed */
+  uint32_t subs_failed;  /* subs whose check failed or whose P_sub was the identity */
+  uint32_t leaves;       /* sets decided by a check of their own after the sub level */
+  uint32_t pairs;        /* Miller pairs of the retry */
+  uint32_t hashes;       /* hash_to_G2 evaluations of the retry */
+} bgv_sm_retry_path;
+/* host-side values, no device call.  A mode 0 call reports subs = subs_failed = 0,
+ * leaves = sets_retried, pairs = 2 sets_retried and hashes = sets_retried; a
+ * mode 1 call 2 pairs per sub that was paired plus 2 per leaf, and hashes = 0. */
+int bgv_sm_retry_stats(bgv_ctx* ctx, bgv_sm_retry_path* out);
+
+#define BGV_SM_SUB 8
+/* Host only (no device, no context): the subs of one retried segment.  m = its surviving sets;
+ * writes the sub offsets into sub_off[] (cap entries) and returns the number of subs.  The
+ * offsets are one more than the subs, the last one m.  When they do not fit cap entries (or
+ * sub_off is NULL) nothing is written and the result is 0xffffffff. */
+uint32_t bgv_sm_split_plan(uint32_t m, uint32_t* sub_off, uint32_t cap);
+
 /* Multi-GPU partials: run the batch up to, but excluding, the
  * final exponentiation and return this shard's Miller product (576 B, 12
  * Fp coefficients of w^0..w^5, c0||c1 each, 48-byte big-endian) with the

@@ -22,6 +22,7 @@
 #include "msm_g1.h"
 #include "sig_agg.h"
 #include "pair_merge.h"
+#include "sm_split.h"
 #include "../../include/bgv.h"
 
 using namespace bgv;
@@ -139,6 +140,9 @@ struct bgv_ctx {
   dbuf<g2a> sm_hg, sm_sg;
   dbuf<g1a> sm_pg;
   dbuf<uint8_t> sm_retry;
+  int32_t sm_mode = 0;              // bgv_sm_retry: 0 per-set retry, 1 split retry (sm_split.h)
+  bgv_sm_retry_path sm_path = {};   // bgv_sm_retry_stats
+  dbuf<uint8_t> sm_split;           // split retry: the compacted sets of level 1, the lists of both levels
   // bgv_verify_same_message_agg
   dbuf<g1j> sma_pk;           // per set: PK_i, Jacobian
   dbuf<int32_t> sma_pk_code;  // per set: its key code
@@ -389,7 +393,7 @@ int bgv_close(bgv_ctx* c) {
   c->msm_bucket.release(); c->msm_win.release(); c->msm_mask.release();
   c->set_job.release(); c->s_inf.release(); c->item_off.release(); c->item_job.release(); c->s_aff.release();
   c->sm_skip.release(); c->sm_list.release(); c->sm_zero.release(); c->sm_seg_code.release(); c->sm_win.release();
-  c->sm_hg.release(); c->sm_sg.release(); c->sm_pg.release(); c->sm_retry.release();
+  c->sm_hg.release(); c->sm_sg.release(); c->sm_pg.release(); c->sm_retry.release(); c->sm_split.release();
   c->sma_pk.release(); c->sma_pk_code.release(); c->sma_aff.release();
   c->sag_seg.release(); c->sag_cnt.release(); c->sag_code.release(); c->sag_out.release(); c->sag_valid.release();
   c->sag_sig.release();
@@ -1874,7 +1878,8 @@ int bgv_debug_bits_keys(bgv_ctx* c, const bgv_bits_batch* b, uint8_t* pk_agg96, 
 //             (-G1, S_seg) ones
 // then, only when the whole-batch check failed, the surviving sets of the
 // failing segments as one-set jobs of the ordinary pipeline (an aggregate key
-// enters as a raw key).
+// enters as a raw key); or, on a context in bgv_sm_retry mode 1, as subs of 8
+// and then the sets of the failing subs (sm_split_retry).
 
 // the rules every same-message batch shares; what passes has n_sets == 0 (and
 // no group: nothing more to check) or 1 <= n_groups <= n_sets
@@ -2064,6 +2069,164 @@ struct sm_agg_req {
   int32_t* agg_code = nullptr;
 };
 
+// A virtual batch of N sets, set t = job t (iota: its job offsets), from the
+// Miller loops to the per-job verdicts: the first pass's segments, and the subs
+// and leaves of the split retry.  w holds its rpk_aff, h_aff, s_aff, s_inf,
+// pk_code and job_code.
+static int sm_virtual_batch(bgv_ctx* c, uint32_t N, const uint32_t* d_iota, const dev_work& w, bool agg) {
+  dev_batch dB;
+  memset(&dB, 0, sizeof dB);
+  dB.n_sets = N; dB.n_jobs = N; dB.pairs_per_item = 1; dB.job_lanes = 36;
+  dB.miller_coop = N < 2000 ? 36u : (N < 6000 ? 18u : 6u);
+  dB.job_off = d_iota;
+  int first = ST_MILLER;  // one key per set: every stage of the virtual batch in order on st
+  if (agg) {
+    // the (P_seg, H(m)) pairs on the hash stream beside the (-G1, S_seg) pairs, as
+    // run_stages places them: a few thousand lanes each, one after the other they
+    // would both be on the critical path
+    HIPCHK(hipEventRecord(c->ev_prep, c->st));
+    HIPCHK(hipStreamWaitEvent(c->st_hash, c->ev_prep, 0));
+    launch_stage(c->st_hash, ST_MILLER, dB, w);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(c->ev_dep[ST_MILLER], c->st_hash));
+    launch_stage(c->st, ST_MILLER_JOBS, dB, w);
+    HIPCHK(hipStreamWaitEvent(c->st, c->ev_dep[ST_MILLER], 0));
+    first = ST_F_TREE;
+  }
+  for (int s = first; s <= ST_JOB_FINAL; s++) launch_stage(c->st, s, dB, w);
+  HIPCHK(hipGetLastError());
+  return BGV_OK;
+}
+
+// The split retry (bgv_sm_retry mode 1, sm_split.h).
+// list / list_group: the surviving sets of the retried segments and their
+// groups; sub_off: the subs (offsets into list).  w is the first pass's work
+// view: its sig_aff, with sm_hg, sma_pk and sm_skip, is read here and by the
+// second pass of bgv_verify_same_message_aggregate, so both levels work in
+// c->sm_split and in work buffers no larger than the first pass's set-sized
+// ones (work_alloc never moves a buffer that is large enough).  jr1 / jr2:
+// pinned room for the sub and leaf verdicts, list.size() words each.
+static int sm_split_retry(bgv_ctx* c, const sm_dev& k, const dev_work& w, const uint64_t* d_scalars,
+                          const std::vector<uint32_t>& list, const std::vector<uint32_t>& list_group,
+                          const std::vector<uint32_t>& sub_off, int32_t* jr1, int32_t* jr2, uint8_t* set_valid,
+                          bgv_sm_retry_path& path) {
+  const uint32_t nr = (uint32_t)list.size(), T = (uint32_t)sub_off.size() - 1, G = k.G, n_raw = k.n_raw;
+  const size_t a = 256;
+  auto up = [&](size_t x) { return (x + a - 1) & ~(a - 1); };
+  // level 1's inputs, then what the host sends: [list | list_group | sub_off | iota] and level 2's [leaf | leaf_group]
+  const size_t o_idx = 0, o_pk = o_idx + up((size_t)nr * 4), o_scal = o_pk + (k.agg ? up((size_t)nr * sizeof(g1j)) : 0),
+               o_sig = o_scal + up((size_t)nr * 8), o_skip = o_sig + up((size_t)nr * sizeof(g2a)), o_sg = o_skip + up((size_t)nr * 4),
+               o_host = o_sg + up((size_t)T * 4), host_words = 2 * (size_t)nr + 2 * ((size_t)T + 1),
+               o_leaf = o_host + up(host_words * 4), o_iota2 = o_leaf + up(2 * (size_t)nr * 4),
+               total = o_iota2 + up(((size_t)nr + 1) * 4);
+  int r = 0;
+  if ((r = c->sm_split.ensure(total)) || (r = c->sm_seg_code.ensure(T)) || (r = c->sm_win.ensure((size_t)T * 16))) return r;
+  uint8_t* base = c->sm_split.p;
+  uint32_t* d_host = (uint32_t*)(base + o_host);
+  const uint32_t *d_list = d_host, *d_list_group = d_host + nr, *d_sub_off = d_host + 2 * (size_t)nr,
+                 *d_iota1 = d_host + 2 * (size_t)nr + T + 1;
+  std::vector<uint32_t> hv;
+  hv.reserve(host_words);
+  hv.insert(hv.end(), list.begin(), list.end());
+  hv.insert(hv.end(), list_group.begin(), list_group.end());
+  hv.insert(hv.end(), sub_off.begin(), sub_off.end());
+  for (uint32_t t = 0; t <= T; t++) hv.push_back(t);
+  HIPCHK(hipMemcpyAsync(d_host, hv.data(), host_words * 4, hipMemcpyHostToDevice, c->st));
+
+  // ---- level 1: sub t = set t = job t; view A1 (the compacted sets, one job per sub) gives its sums
+  dev_batch dA;
+  memset(&dA, 0, sizeof dA);
+  dA.n_sets = nr; dA.n_jobs = T; dA.n_raw = n_raw; dA.table_n = c->table_n; dA.table = c->table;
+  dA.span_log2 = 6; dA.job_lanes = 36; dA.pairs_per_item = 1; dA.msm = 4; dA.clear_lanes = 9;
+  dA.chunk_bound = nr; dA.defer_from = nr;
+  dA.job_off = d_sub_off; dA.pk_idx = (const uint32_t*)(base + o_idx); dA.raw_pks = c->raw_conv.p;
+  dA.scalars = (const uint64_t*)(base + o_scal);
+  dev_work w1;
+  if ((r = work_alloc(c, dA, w1))) return r;
+  sm_split q;
+  memset(&q, 0, sizeof q);
+  q.n = nr; q.n_subs = T; q.list = d_list; q.list_group = d_list_group; q.sub_off = d_sub_off;
+  q.scalars = d_scalars; q.sig_aff = w.sig_aff;
+  q.o_scalars = (uint64_t*)(base + o_scal); q.o_sig = (g2a*)(base + o_sig); q.o_skip = (uint32_t*)(base + o_skip);
+  q.o_sub_group = (uint32_t*)(base + o_sg);
+  if (k.agg) { q.pk_set = c->sma_pk.p; q.o_pk = (g1j*)(base + o_pk); }
+  else { q.pk_idx = k.d_idx; q.o_idx = (uint32_t*)(base + o_idx); }
+  launch_sm_split_gather(c->st, q);
+  HIPCHK(hipGetLastError());
+  sm_view v;
+  memset(&v, 0, sizeof v);
+  v.n_sets = nr; v.n_segs = T; v.n_groups = G; v.n_raw = n_raw; v.table_n = c->table_n;
+  v.seg_off = d_sub_off; v.seg_group = q.o_sub_group; v.pk_idx = q.o_idx; v.raw_pks = c->raw_conv.p; v.table = c->table;
+  v.scalars = q.o_scalars; v.skip = q.o_skip;
+  v.win = c->sm_win.p; v.p_seg = w1.rpk_aff; v.seg_code = c->sm_seg_code.p; v.h_group = c->sm_hg.p; v.h_seg = w1.h_aff;
+  v.pk_code_v = w1.pk_code; v.job_code_v = w1.job_code; v.s_seg = w1.s_aff; v.s_inf = w1.s_inf;
+  v.pk_set = q.o_pk;
+  HIPCHK(hipEventRecord(c->ev_fork, c->st));  // P_sub on the pubkey stream beside S_sub, as in the first pass
+  HIPCHK(hipStreamWaitEvent(c->st_pk, c->ev_fork, 0));
+  if (k.agg) launch_sma_g1_sum(c->st_pk, v);
+  else launch_sm_g1_sum(c->st_pk, v);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(c->ev_dep[ST_PK_SCALE], c->st_pk));
+  {
+    dev_work wz = w1;  // the compacted signatures; every set of the list is live
+    wz.sig_aff = q.o_sig;
+    wz.sig_code = c->sm_zero.p;
+    wz.pk_code = c->sm_zero.p;
+    wz.sig_inf = q.o_skip;
+    launch_stage(c->st, ST_SIG_SCALE, dA, wz);
+    launch_stage(c->st, ST_S_TREE, dA, wz);
+    HIPCHK(hipGetLastError());
+  }
+  HIPCHK(hipStreamWaitEvent(c->st, c->ev_dep[ST_PK_SCALE], 0));
+  launch_sm_apply(c->st, v);
+  if ((r = sm_virtual_batch(c, T, d_iota1, w1, k.agg))) return r;
+  HIPCHK(hipMemcpyAsync(jr1, w1.job_result, (size_t)T * 4, hipMemcpyDeviceToHost, c->st));
+  HIPCHK(hipStreamSynchronize(c->st));
+  sm_split_counts cnt = {0, 0, 0, 0};
+  sm_split_tally(cnt, sub_off.data(), jr1, T);
+  path.subs = cnt.subs; path.subs_failed = cnt.subs_failed; path.leaves = cnt.leaves; path.pairs = cnt.pairs;
+  std::vector<uint32_t> lv;  // [leaf | leaf_group]
+  lv.reserve(2 * (size_t)cnt.leaves);
+  for (uint32_t t = 0; t < T; t++) {
+    const uint32_t beg = sub_off[t], end = sub_off[t + 1];
+    if (sm_sub_opens(jr1[t], end - beg)) {
+      lv.insert(lv.end(), list.begin() + beg, list.begin() + end);
+    } else {
+      for (uint32_t j = beg; j < end; j++) set_valid[list[j]] = sm_sub_failed(jr1[t]) ? 0 : 1;
+    }
+  }
+  const uint32_t L = (uint32_t)lv.size();
+  if (!L) return BGV_OK;
+  for (uint32_t t = 0; t < T; t++)
+    if (sm_sub_opens(jr1[t], sub_off[t + 1] - sub_off[t]))
+      lv.insert(lv.end(), list_group.begin() + sub_off[t], list_group.begin() + sub_off[t + 1]);
+
+  // ---- level 2: leaf t = set t = job t, nothing scaled
+  dev_batch dL;
+  memset(&dL, 0, sizeof dL);
+  dL.n_sets = L; dL.n_jobs = L; dL.chunk_bound = L;
+  dev_work w2;
+  if ((r = work_alloc(c, dL, w2))) return r;
+  uint32_t* d_leaf = (uint32_t*)(base + o_leaf);
+  HIPCHK(hipMemcpyAsync(d_leaf, lv.data(), 2 * (size_t)L * 4, hipMemcpyHostToDevice, c->st));
+  sm_leaves ql;
+  memset(&ql, 0, sizeof ql);
+  ql.n = L; ql.n_raw = n_raw; ql.table_n = c->table_n; ql.leaf = d_leaf; ql.leaf_group = d_leaf + L;
+  ql.raw_pks = c->raw_conv.p; ql.table = c->table;
+  if (k.agg) ql.pk_set = c->sma_pk.p;
+  else ql.pk_idx = k.d_idx;
+  ql.sig_aff = w.sig_aff; ql.h_group = c->sm_hg.p;
+  ql.rpk_aff = w2.rpk_aff; ql.h_aff = w2.h_aff; ql.s_aff = w2.s_aff; ql.s_inf = w2.s_inf;
+  ql.pk_code = w2.pk_code; ql.job_code = w2.job_code; ql.iota = (uint32_t*)(base + o_iota2);
+  launch_sm_split_leaves(c->st, ql);
+  HIPCHK(hipGetLastError());
+  if ((r = sm_virtual_batch(c, L, ql.iota, w2, k.agg))) return r;
+  HIPCHK(hipMemcpyAsync(jr2, w2.job_result, (size_t)L * 4, hipMemcpyDeviceToHost, c->st));
+  HIPCHK(hipStreamSynchronize(c->st));
+  for (uint32_t t = 0; t < L; t++) set_valid[lv[t]] = jr2[t] == 1 ? 1 : 0;
+  return BGV_OK;
+}
+
 // The device half of a same-message call, from the staged (or resident) arrays
 // on.  k.agg picks the key side, where the pairs of the virtual batch run and
 // what the retry takes as a set's key; everything else is one path.
@@ -2196,28 +2359,7 @@ static int sm_back(bgv_ctx* c, sm_dev& k, uint8_t* set_valid, int32_t* set_code,
   HIPCHK(hipStreamWaitEvent(c->st, c->ev_dep[ST_PK_SCALE], 0));
   HIPCHK(hipStreamWaitEvent(c->st, c->ev_dep[ST_HASH], 0));
   launch_sm_apply(c->st, v);
-  // view B: the virtual batch, segment s = set s = job s
-  dev_batch dB;
-  memset(&dB, 0, sizeof dB);
-  dB.n_sets = S; dB.n_jobs = S; dB.pairs_per_item = 1; dB.job_lanes = 36;
-  dB.miller_coop = S < 2000 ? 36u : (S < 6000 ? 18u : 6u);
-  dB.job_off = d_iota;
-  int first = ST_MILLER;  // one key per set: every stage of the virtual batch in order on st
-  if (k.agg) {
-    // the (P_seg, H(m)) pairs on the hash stream beside the (-G1, S_seg) pairs, as
-    // run_stages places them: a few thousand lanes each, one after the other they
-    // would both be on the critical path
-    HIPCHK(hipEventRecord(c->ev_prep, c->st));
-    HIPCHK(hipStreamWaitEvent(c->st_hash, c->ev_prep, 0));
-    launch_stage(c->st_hash, ST_MILLER, dB, w);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(c->ev_dep[ST_MILLER], c->st_hash));
-    launch_stage(c->st, ST_MILLER_JOBS, dB, w);
-    HIPCHK(hipStreamWaitEvent(c->st, c->ev_dep[ST_MILLER], 0));
-    first = ST_F_TREE;
-  }
-  for (int s = first; s <= ST_JOB_FINAL; s++) launch_stage(c->st, s, dB, w);
-  HIPCHK(hipGetLastError());
+  if ((r = sm_virtual_batch(c, S, d_iota, w, k.agg))) return r;  // view B: segment s = set s = job s
 
   // first-pass results
   const size_t o_jr = 256, o_sc = o_jr + (((size_t)S * 4 + 255) & ~size_t(255)), o_sk = o_sc + (((size_t)n * 4 + 255) & ~size_t(255));
@@ -2262,20 +2404,40 @@ static int sm_back(bgv_ctx* c, sm_dev& k, uint8_t* set_valid, int32_t* set_code,
   const int32_t* jr = (const int32_t*)(c->pin_out + o_jr);
   const int32_t* sc = (const int32_t*)(c->pin_out + o_sc);
   const uint32_t* sk = (const uint32_t*)(c->pin_out + o_sk);
-  std::vector<uint32_t> list, list_group;
+  std::vector<uint32_t> list, list_group, sub_off;  // sub_off: the split retry's subs, offsets into list
   uint32_t pairs = 0, groups_retried = 0, last_group = 0xffffffffu;
+  const bool split = c->sm_mode == 1;
+  bgv_sm_retry_path& path = c->sm_path;
+  path = {};
+  path.mode = (uint32_t)c->sm_mode;
   for (uint32_t s = 0; s < S; s++) {
     const bool ok = jr[s] == 1, retry = jr[s] == 0 || jr[s] == -C_SEG_RETRY;
     if (jr[s] >= 0) pairs += 2;
     if (retry && seg_group[s] != last_group) { groups_retried++; last_group = seg_group[s]; }
+    const uint32_t first = (uint32_t)list.size();
     for (uint32_t i = seg_off[s]; i < seg_off[s + 1]; i++) {
       set_valid[i] = (!sk[i] && ok) ? 1 : 0;
       if (set_code) set_code[i] = sc[i];
       if (retry && !sk[i]) { list.push_back(i); list_group.push_back(seg_group[s]); }
     }
+    if (retry) path.segments++;
+    if (retry && split) {  // SM_SEG + 1 offsets at the most, the last one the next segment's first
+      uint32_t off[SM_SEG + 1];
+      const uint32_t T = sm_split_plan((uint32_t)list.size() - first, first, off, SM_SEG + 1);
+      sub_off.insert(sub_off.end(), off, off + T);
+    }
   }
   const uint32_t nr = (uint32_t)list.size();
-  if (nr) {
+  sub_off.push_back(nr);
+  if (nr && ag && (r = c->sag_valid.ensure(n))) return r;
+  if (nr && split) {
+    // the same sets by subset checks: nothing is decoded or hashed again, and the first pass's signatures stay
+    // where the second pass below reads them
+    if ((r = sm_split_retry(c, k, w, d_scalars, list, list_group, sub_off, (int32_t*)(c->pin_out + o_sc), (int32_t*)(c->pin_out + o_sk),
+                            set_valid, path)))
+      return r;
+  } else if (nr) {
+    path.leaves = nr; path.pairs = 2 * nr; path.hashes = nr;
     // the rare path: the surviving sets of the failing segments, each on its
     // own.  An aggregated key enters as row j of a raw-key table (o_pk).
     const size_t a = 256;
@@ -2319,16 +2481,16 @@ static int sm_back(bgv_ctx* c, sm_dev& k, uint8_t* set_valid, int32_t* set_code,
     std::vector<int32_t> jr2(nr);
     if ((r = finish_results(c, d2, w2, jr2.data(), nullptr, nullptr))) return r;
     for (uint32_t j = 0; j < nr; j++) set_valid[list[j]] = jr2[j] == 1 ? 1 : 0;
-    if (ag) {  // second pass: the same two kernels over the sets with set_valid = 1
-      memcpy(c->pin_out + o_av, set_valid, n);
-      HIPCHK(hipMemcpyAsync(c->sag_valid.p, c->pin_out + o_av, n, hipMemcpyHostToDevice, c->st));
-      av.sig_aff = c->sag_sig.p;
-      av.valid = c->sag_valid.p;
-      launch_sm_sig_agg(c->st, av);
-      HIPCHK(hipGetLastError());
-      if ((r = agg_copies())) return r;
-      HIPCHK(hipStreamSynchronize(c->st));
-    }
+  }
+  if (nr && ag) {  // second pass: the same two kernels over the sets with set_valid = 1
+    memcpy(c->pin_out + o_av, set_valid, n);
+    HIPCHK(hipMemcpyAsync(c->sag_valid.p, c->pin_out + o_av, n, hipMemcpyHostToDevice, c->st));
+    av.sig_aff = split ? w.sig_aff : c->sag_sig.p;
+    av.valid = c->sag_valid.p;
+    launch_sm_sig_agg(c->st, av);
+    HIPCHK(hipGetLastError());
+    if ((r = agg_copies())) return r;
+    HIPCHK(hipStreamSynchronize(c->st));
   }
   if (ag) {
     memcpy(ag->agg_sig96, c->pin_out + o_as, (size_t)G * 96);
@@ -2564,6 +2726,22 @@ int bgv_debug_same_message_bits(bgv_ctx* c, const bgv_smb_batch* b, uint8_t* set
                                 uint8_t* pk_set96, uint8_t* path, uint8_t* p_group96, uint8_t* s_group192, uint8_t* h_group192) {
   return sm_done(c, smb_run(c, b, set_valid, set_code, stats, pk_set96, path, p_group96, s_group192, h_group192));
 }
+
+int bgv_sm_retry(bgv_ctx* c, int32_t mode) {
+  if (!c) return fail(BGV_E_INVALID_ARG, "null ctx");
+  if (mode != 0 && mode != 1) return fail(BGV_E_INVALID_ARG, "bgv_sm_retry mode %d", mode);
+  c->sm_mode = mode;
+  return BGV_OK;
+}
+
+int bgv_sm_retry_stats(bgv_ctx* c, bgv_sm_retry_path* out) {
+  if (!c || !out) return fail(BGV_E_INVALID_ARG, "null argument");
+  *out = c->sm_path;
+  return BGV_OK;
+}
+
+static_assert(SM_SUB == BGV_SM_SUB && SM_SUB <= SM_SEG, "the sub size of sm_split.h is the ABI's");
+uint32_t bgv_sm_split_plan(uint32_t m, uint32_t* sub_off, uint32_t cap) { return sm_split_plan(m, 0, sub_off, cap); }
 
 // ---- multi-GPU partials ---------------------------------------------------
 // fp12 (plain limbs, already out of Montgomery form on the device) <-> 576 B

@@ -241,6 +241,47 @@ struct sm_retry {
   uint32_t* o_len;
   uint64_t* o_scalars;
 };
+// split retry (bgv_sm_retry mode 1, sm_split.h), level 1: the surviving sets of
+// the retried segments compacted into buffers of their own, set list[t] as set
+// t, so that the sum kernels run over them with seg_off = the sub offsets
+struct sm_split {
+  uint32_t n, n_subs;
+  const uint32_t* list;        // [n] set index
+  const uint32_t* list_group;  // [n] its group
+  const uint32_t* sub_off;     // [n_subs + 1] offsets into list
+  const uint32_t* pk_idx;      // one key per set (else NULL)
+  const g1j* pk_set;           // aggregate sets: PK_i (else NULL)
+  const uint64_t* scalars;
+  const g2a* sig_aff;          // the first pass's decoded signatures
+  uint32_t* o_idx;             // [n] (one key per set)
+  g1j* o_pk;                   // [n] (aggregate sets)
+  uint64_t* o_scalars;         // [n]
+  g2a* o_sig;                  // [n]
+  uint32_t* o_skip;            // [n] zero: every set of the list survived
+  uint32_t* o_sub_group;       // [n_subs] the group of every sub
+};
+// level 2: leaf t (set leaf[t] of group leaf_group[t]) as set t = job t of a
+// virtual batch, nothing scaled: (pk_i, H(m_g)) and (-G1, sigma_i)
+struct sm_leaves {
+  uint32_t n, n_raw, table_n;
+  const uint32_t* leaf;        // [n] set index
+  const uint32_t* leaf_group;  // [n] its group
+  const uint32_t* pk_idx;      // one key per set (else NULL)
+  const g1a* raw_pks;
+  const g1a* table;
+  const g1j* pk_set;           // aggregate sets: PK_i (else NULL)
+  const g2a* sig_aff;
+  const g2a* h_group;
+  g1a* rpk_aff;                // [n] the virtual batch's arrays
+  g2a* h_aff;
+  g2a* s_aff;
+  uint32_t* s_inf;
+  int32_t* pk_code;
+  int32_t* job_code;
+  uint32_t* iota;              // [n + 1] its job offsets
+};
+void launch_sm_split_gather(hipStream_t st, const sm_split& q);
+void launch_sm_split_leaves(hipStream_t st, const sm_leaves& q);
 void launch_sm_classify(hipStream_t st, const sm_view& v);
 void launch_sm_g1_sum(hipStream_t st, const sm_view& v);
 void launch_sm_apply(hipStream_t st, const sm_view& v);

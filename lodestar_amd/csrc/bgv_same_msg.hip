@@ -26,16 +26,20 @@ namespace bgv {
 __device__ __forceinline__ static uint32_t sm_gtid() { return blockIdx.x * blockDim.x + threadIdx.x; }
 
 // row of the pubkey table, or of the raw side table for bit 31; false: out of range
-__device__ __forceinline__ static bool sm_load_pk(g1a& out, const sm_view& v, uint32_t idx) {
+__device__ __forceinline__ static bool sm_load_row(g1a& out, const g1a* table, uint32_t table_n, const g1a* raw_pks, uint32_t n_raw,
+                                                   uint32_t idx) {
   if (idx & 0x80000000u) {
     const uint32_t r = idx & 0x7fffffffu;
-    if (r >= v.n_raw) return false;
-    out = v.raw_pks[r];
+    if (r >= n_raw) return false;
+    out = raw_pks[r];
   } else {
-    if (idx >= v.table_n) return false;
-    out = v.table[idx];
+    if (idx >= table_n) return false;
+    out = table[idx];
   }
   return true;
+}
+__device__ __forceinline__ static bool sm_load_pk(g1a& out, const sm_view& v, uint32_t idx) {
+  return sm_load_row(out, v.table, v.table_n, v.raw_pks, v.n_raw, idx);
 }
 
 // per set: which sets enter the sums.  A set is rejected here, with its code
@@ -195,6 +199,65 @@ __device__ __forceinline__ static void sm_retry_gather(const sm_retry& r, const 
 __global__ void BGV_SM_LB k_sm_retry_gather(sm_retry r) { sm_retry_gather<false>(r, nullptr, nullptr); }
 __global__ void BGV_SM_LB k_sma_retry_gather(sm_retry r, const g1j* pk_set, g1a* o_pk) { sm_retry_gather<true>(r, pk_set, o_pk); }
 
+// ---- split retry (bgv_sm_retry mode 1, sm_split.h) ---------------------------
+// Level 1 reads what the first pass left on the device: lane t copies set
+// list[t]'s scalar, key (its index, or PK_i of an aggregate set) and decoded
+// signature to position t of the retry's own buffers, so that the sum kernels
+// above and k_msm_digit run over them with a sub as a short segment.  Nothing
+// is computed; the first n_subs lanes also write their sub's group.
+template <bool AGG>
+__device__ __forceinline__ static void sm_split_gather(const sm_split& q) {
+  const uint32_t t = sm_gtid();
+  if (t >= q.n) return;
+  const uint32_t i = q.list[t];
+  if constexpr (AGG) {
+    const g1j pk = q.pk_set[i];
+    q.o_pk[t] = pk;
+  } else {
+    q.o_idx[t] = q.pk_idx[i];
+  }
+  q.o_scalars[t] = q.scalars[i];
+  const g2a sig = q.sig_aff[i];
+  q.o_sig[t] = sig;
+  q.o_skip[t] = 0u;
+  if (t < q.n_subs) q.o_sub_group[t] = q.list_group[q.sub_off[t]];  // n_subs <= n: a sub is never empty
+}
+__global__ void BGV_SM_LB k_sm_split_gather(sm_split q) { sm_split_gather<false>(q); }
+__global__ void BGV_SM_LB k_sma_split_gather(sm_split q) { sm_split_gather<true>(q); }
+
+// Level 2: leaf t = set t = job t of a virtual batch whose pairs are
+// (pk_i, H(m_g)) and (-G1, sigma_i), unscaled, so its verdict is the set's own.
+// One jac_to_aff per aggregate key, no other arithmetic.
+template <bool AGG>
+__device__ __forceinline__ static void sm_split_leaves(const sm_leaves& q) {
+  const uint32_t t = sm_gtid();
+  if (t > q.n) return;
+  q.iota[t] = t;
+  if (t == q.n) return;
+  const uint32_t i = q.leaf[t];
+  g1a pk;
+  int32_t code = C_OK;
+  if constexpr (AGG) {
+    if (!jac_to_aff(pk, q.pk_set[i])) code = C_PK_IS_INFINITY;  // k_sma_classify skipped such a set
+  } else {
+    if (!sm_load_row(pk, q.table, q.table_n, q.raw_pks, q.n_raw, q.pk_idx[i])) {  // k_sm_classify skipped such a set
+      code = C_INDEX_RANGE;
+      fp_set_zero(pk.x);
+      fp_set_zero(pk.y);
+    }
+  }
+  q.rpk_aff[t] = pk;
+  const g2a h = q.h_group[q.leaf_group[t]];
+  q.h_aff[t] = h;
+  const g2a sig = q.sig_aff[i];
+  q.s_aff[t] = sig;
+  q.s_inf[t] = 0u;
+  q.pk_code[t] = code;
+  q.job_code[t] = code;
+}
+__global__ void BGV_SM_LB k_sm_split_leaves(sm_leaves q) { sm_split_leaves<false>(q); }
+__global__ void BGV_SM_LB k_sma_split_leaves(sm_leaves q) { sm_split_leaves<true>(q); }
+
 // ---- aggregate sets (bgv_verify_same_message_agg) ---------------------------
 // A set's key is PK_i = sum_j pk_{i,j}.  The balanced gather of the ordinary
 // pipeline (k_chunk_count / k_scan / k_chunk_set / k_pk_chunk) leaves one
@@ -268,6 +331,17 @@ void launch_sm_group_sums(hipStream_t st, const sm_view& v, const uint32_t* grou
 
 void launch_sm_retry_gather(hipStream_t st, const sm_retry& r) {
   hipLaunchKernelGGL(k_sm_retry_gather, sm_grid(r.n + 1u), dim3(64), 0, st, r);
+}
+
+void launch_sm_split_gather(hipStream_t st, const sm_split& q) {
+  if (!q.n) return;
+  if (q.pk_set) hipLaunchKernelGGL(k_sma_split_gather, sm_grid(q.n), dim3(64), 0, st, q);
+  else hipLaunchKernelGGL(k_sm_split_gather, sm_grid(q.n), dim3(64), 0, st, q);
+}
+
+void launch_sm_split_leaves(hipStream_t st, const sm_leaves& q) {
+  if (q.pk_set) hipLaunchKernelGGL(k_sma_split_leaves, sm_grid(q.n + 1u), dim3(64), 0, st, q);
+  else hipLaunchKernelGGL(k_sm_split_leaves, sm_grid(q.n + 1u), dim3(64), 0, st, q);
 }
 
 void launch_sma_set_sum(hipStream_t st, const dev_batch& b, const dev_work& w, g1j* pk_set, int32_t* pk_set_code) {

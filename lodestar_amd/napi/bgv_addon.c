@@ -37,6 +37,9 @@
  *   pairMerge(ctx, on)                           bgv_pair_merge: one Miller pair per distinct signing root of a job, from the
  *                                                next call on (bulk layout, one-lane loop; off by default)
  *   pairStats(ctx) -> {sets, pairs, merged, fallback}   bgv_pair_stats (the last verify / verifyBits / partial)
+ *   smRetry(ctx, mode)                            bgv_sm_retry: the retry of the same-message entries, from the next call on:
+ *                                                 0 one-set jobs (the default), 1 subs of 8, then the sets of the failing subs
+ *   smRetryStats(ctx) -> {mode, segments, subs, subsFailed, leaves, pairs, hashes}   bgv_sm_retry_stats (the last same-message call)
  *   bitsPathStats(ctx) -> {setsComplement, keysExpanded, keysGathered}   bgv_bits_path_stats (the last verifyBits / verifySameMessageBits)
  *   verifyBits(ctx, bitsBatch) -> Promise<result>, verifyBitsSync(ctx, bitsBatch) -> result
  *                                                bgv_verify_bits: sets given as (list, window, participation bits)
@@ -1294,6 +1297,54 @@ static napi_value PairStats(napi_env env, napi_callback_info info) {
   return r;
 }
 
+/* smRetry(ctx, mode): bgv_sm_retry (a boolean, or 0 / 1; any other number is refused by the library) */
+static napi_value SmRetry(napi_env env, napi_callback_info info) {
+  size_t argc = 2;
+  napi_value a[2];
+  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, a, NULL, NULL));
+  addon_ctx* c = get_ctx(env, a[0]);
+  if (!c) return NULL;
+  int32_t mode = 0;
+  napi_valuetype t = napi_undefined;
+  if (argc >= 2) NAPI_CALL(env, napi_typeof(env, a[1], &t));
+  if (t == napi_boolean) {
+    bool on = false;
+    NAPI_CALL(env, napi_get_value_bool(env, a[1], &on));
+    mode = on ? 1 : 0;
+  } else {
+    NAPI_CALL(env, napi_get_value_int32(env, a[1], &mode));
+  }
+  pthread_mutex_lock(&c->mu);
+  const int st = bgv_sm_retry(c->ctx, mode);
+  pthread_mutex_unlock(&c->mu);
+  if (st != BGV_OK) return throw_bgv(env, st);
+  return NULL;
+}
+
+/* smRetryStats(ctx): bgv_sm_retry_stats of the context's last same-message call */
+static napi_value SmRetryStats(napi_env env, napi_callback_info info) {
+  size_t argc = 1;
+  napi_value a[1];
+  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, a, NULL, NULL));
+  addon_ctx* c = get_ctx(env, a[0]);
+  if (!c) return NULL;
+  bgv_sm_retry_path p;
+  pthread_mutex_lock(&c->mu);
+  const int st = bgv_sm_retry_stats(c->ctx, &p);
+  pthread_mutex_unlock(&c->mu);
+  if (st != BGV_OK) return throw_bgv(env, st);
+  const struct { const char* name; uint32_t val; } u[] = {
+      {"mode", p.mode}, {"segments", p.segments}, {"subs", p.subs}, {"subsFailed", p.subs_failed},
+      {"leaves", p.leaves}, {"pairs", p.pairs}, {"hashes", p.hashes}};
+  napi_value r, v;
+  NAPI_CALL(env, napi_create_object(env, &r));
+  for (size_t k = 0; k < sizeof u / sizeof u[0]; k++) {
+    NAPI_CALL(env, napi_create_uint32(env, u[k].val, &v));
+    NAPI_CALL(env, napi_set_named_property(env, r, u[k].name, v));
+  }
+  return r;
+}
+
 static napi_value BitsPathStats(napi_env env, napi_callback_info info) {
   size_t argc = 1;
   napi_value a[1];
@@ -1347,6 +1398,8 @@ static napi_value Init(napi_env env, napi_value exports) {
       {"hashStats", NULL, HashStats, NULL, NULL, NULL, napi_enumerable, NULL},
       {"pairMerge", NULL, PairMerge, NULL, NULL, NULL, napi_enumerable, NULL},
       {"pairStats", NULL, PairStats, NULL, NULL, NULL, napi_enumerable, NULL},
+      {"smRetry", NULL, SmRetry, NULL, NULL, NULL, napi_enumerable, NULL},
+      {"smRetryStats", NULL, SmRetryStats, NULL, NULL, NULL, napi_enumerable, NULL},
       {"verifyBits", NULL, VerifyBits, NULL, NULL, NULL, napi_enumerable, NULL},
       {"verifyBitsSync", NULL, VerifyBitsSync, NULL, NULL, NULL, napi_enumerable, NULL},
   };

@@ -559,6 +559,11 @@ function newMetrics() {
     // verifySignatureSetsSameMessage: sets sent to the device, and groups that went to the per-set retry
     lodestar_bls_thread_pool_same_message_sig_sets_started_total: 0,
     lodestar_bls_thread_pool_same_message_retries_total: 0,
+    // the retry of the same-message calls (bgv_sm_retry_stats): subs a split retry formed, sets decided by a check of
+    // their own, Miller pairs of the retry
+    sm_retry_subs: 0,
+    sm_retry_leaves: 0,
+    sm_retry_pairs: 0,
     // verifyAndAggregateSameMessage: signatures added to the callers' aggregates
     lodestar_bls_thread_pool_same_message_aggregated_sigs_total: 0,
     // verifyAggregateSetsSameMessage: the same two counters for aggregate sets
@@ -570,6 +575,14 @@ function newMetrics() {
 function observe(h, v) {
   h.count++;
   h.sum += v;
+}
+
+// the retry of the context's last same-message call into the pool's counters (the caller still holds the context)
+function recordSmRetry(m, ctx) {
+  const p = addon.smRetryStats(ctx);
+  m.sm_retry_subs += p.subs;
+  m.sm_retry_leaves += p.leaves;
+  m.sm_retry_pairs += p.pairs;
 }
 
 class BlsGpuVerifier {
@@ -591,8 +604,11 @@ class BlsGpuVerifier {
   // over one idle context per device
   // pairMerge (bgv_pair_merge, off by default): every bulk context pairs once per distinct signing root of a job
   // where its batch runs the bulk layout's one-lane loop; the priority context serves latency batches
+  // smRetry (bgv_sm_retry, off by default): every context localises the failing sets of a same-message call by
+  // subset checks (subs of 8, then the sets of the failing subs) instead of one-set jobs
   constructor({device = 0, devices = null, maxSetsPerDeviceBatch = MAX_SETS_PER_DEVICE_BATCH, shardMinSets = SHARD_MIN_SETS,
-    priorityCus = null, blsVerifyAllMultiThread = false, contextsPerDevice = CONTEXTS_PER_DEVICE, pairMerge = false} = {}) {
+    priorityCus = null, blsVerifyAllMultiThread = false, contextsPerDevice = CONTEXTS_PER_DEVICE, pairMerge = false,
+    smRetry = false} = {}) {
     const ids = devices && devices.length ? devices : [device];
     if (!(contextsPerDevice >= 1)) throw new Error(`contextsPerDevice ${contextsPerDevice}`);
     if (priorityCus === null || priorityCus === undefined) priorityCus = ids.length > 1 ? PRIORITY_CUS : 0;
@@ -632,6 +648,8 @@ class BlsGpuVerifier {
     // waves.  Under blsVerifyAllMultiThread nothing uses it: the blocking
     // verifySignatureSetsSync then runs on the first bulk context
     this.prio = blsVerifyAllMultiThread ? null : addon.open(ids[0], priorityCus > 0 ? priorityCus : 0);
+    this.smRetry = !!smRetry;
+    if (this.smRetry) for (const c of this.prio ? [...this.ctxs, this.prio] : this.ctxs) addon.smRetry(c, 1);
     this.prioReserved = priorityCus > 0;
     this.priorityCus = priorityCus;
     if (this.prio) this.warmPriority();
@@ -802,6 +820,7 @@ class BlsGpuVerifier {
         ? await addon.verifySameMessageAggregate(ctx, {...encodeSameMessage(groups), ...encodeAggregateSide(jobs, merged, n)})
         : await addon.verifySameMessage(ctx, encodeSameMessage(groups));
       m.lodestar_bls_thread_pool_same_message_retries_total += res.groupsRetried;
+      recordSmRetry(m, ctx);
       m.lodestar_bls_thread_pool_time_seconds_sum += (res.workerEndMs - res.workerStartMs) / 1000;
       jobs.forEach((job, k) => {
         const r = withAgg ? aggregateCallResult(addon, job, res, where[k], merged.groupOf[k]) : Array.from(res.valid.subarray(where[k][0], where[k][1]), (v) => v === 1);
@@ -879,6 +898,7 @@ class BlsGpuVerifier {
       const res = await (bits ? addon.verifySameMessageBits(ctx, batch) : addon.verifySameMessageAgg(ctx, batch));
       if (bits) m.lodestar_bls_aggregated_pubkeys_total += res.pubkeysAggregated;
       m.lodestar_bls_thread_pool_same_message_agg_retries_total += res.groupsRetried;
+      recordSmRetry(m, ctx);
       m.lodestar_bls_thread_pool_time_seconds_sum += (res.workerEndMs - res.workerStartMs) / 1000;
       jobs.forEach((job, k) => job.resolve(Array.from(res.valid.subarray(where[k][0], where[k][1]), (v) => v === 1)));
     } catch (e) {
@@ -1180,8 +1200,9 @@ class BlsGpuVerifier {
 // thread (addon.verifySync); canAcceptWork is always true.  Its pubkey table
 // is its own replica.
 class BlsGpuSingleThreadVerifier {
-  constructor({device = 0, pairMerge = false} = {}) {
+  constructor({device = 0, pairMerge = false, smRetry = false} = {}) {
     this.ctx = addon.open(device, 0);
+    if (smRetry) addon.smRetry(this.ctx, 1); // bgv_sm_retry: the split retry of the same-message entries
     if (pairMerge) addon.pairMerge(this.ctx, true); // bgv_pair_merge: bulk-layout batches only
     this.closed = false;
     this.metrics = {lodestar_bls_aggregated_pubkeys_total: 0, lodestar_bls_thread_pool_main_thread_time_seconds: {count: 0, sum: 0}};

@@ -62,7 +62,10 @@ EXPORTS = [
     "bgv_verify_same_message_aggregate", "bgv_sm_agg_check", "bgv_sm_agg_ms",
     "bgv_pair_merge", "bgv_pair_stats", "bgv_debug_pair_classes",
     "bgv_batch_tail", "bgv_tail_stats",
+    "bgv_sm_retry", "bgv_sm_retry_stats",
 ]
+# exported too, listed apart: the one entry that returns a count (uint32_t), not a status
+EXPORTS_U32 = ["bgv_sm_split_plan"]
 MAX_INDEX_LISTS = 8
 SRC_EXPLICIT = 0xFFFFFFFF
 # bgv_set_src as a numpy record: (list, off, len, bits_off), 16 B per set
@@ -306,6 +309,20 @@ class BgvPairPath(ctypes.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
+class BgvSmRetryPath(ctypes.Structure):
+    """bgv_sm_retry_path (include/bgv.h): the retry the last same-message call ran"""
+    _fields_ = [("mode", ctypes.c_uint32), ("segments", ctypes.c_uint32), ("subs", ctypes.c_uint32),
+                ("subs_failed", ctypes.c_uint32), ("leaves", ctypes.c_uint32), ("pairs", ctypes.c_uint32),
+                ("hashes", ctypes.c_uint32)]
+
+    def as_dict(self) -> dict:
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+SM_SUB = 8  # BGV_SM_SUB
+SM_PLAN_FAIL = 0xFFFFFFFF
+
+
 def source_hash(root: str = ROOT) -> str:
     """SHA-256 over (path, content) of source_files(): the id tools/build.py
     compiles into the library (bgv_build_id) and load_library checks."""
@@ -409,6 +426,9 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
             "bgv_miller_path_stats": ([P, ctypes.POINTER(BgvMillerPath)], ctypes.c_int),
             "bgv_pair_merge": ([P, ctypes.c_int32], ctypes.c_int),
             "bgv_pair_stats": ([P, ctypes.POINTER(BgvPairPath)], ctypes.c_int),
+            "bgv_sm_retry": ([P, ctypes.c_int32], ctypes.c_int),
+            "bgv_sm_retry_stats": ([P, ctypes.POINTER(BgvSmRetryPath)], ctypes.c_int),
+            "bgv_sm_split_plan": ([ctypes.c_uint32, P, ctypes.c_uint32], ctypes.c_uint32),
             "bgv_batch_tail": ([P, ctypes.c_int32], ctypes.c_int),
             "bgv_tail_stats": ([P, ctypes.POINTER(BgvTailPath)], ctypes.c_int),
             "bgv_debug_pair_classes": ([P, ctypes.POINTER(BgvBatch), P, P, P, P, P, P, P], ctypes.c_int),
@@ -602,6 +622,7 @@ class Device:
         self.lib = load_library()
         h = ctypes.c_void_p()
         pair_merge = cfg.pop("pair_merge", None)  # a context call, not a bgv_cfg field (bgv_pair_merge)
+        sm_retry = cfg.pop("sm_retry", None)      # likewise (bgv_sm_retry)
         if cfg:
             self._check(self.lib.bgv_open_cfg(device, ctypes.byref(BgvCfg.make(**cfg)), ctypes.byref(h)))
         else:
@@ -611,6 +632,8 @@ class Device:
         self.last_stats = BgvStats()
         if pair_merge is not None:
             self.pair_merge(pair_merge)
+        if sm_retry is not None:
+            self.sm_retry(sm_retry)
 
     # -------------------------------------------------------------- helpers
     def _check(self, st: int):
@@ -900,6 +923,19 @@ class Device:
         any other entry"""
         out = BgvPairPath()
         self._check(self.lib.bgv_pair_stats(self.h, ctypes.byref(out)))
+        return out.as_dict()
+
+    def sm_retry(self, mode) -> None:
+        """bgv_sm_retry: the retry of the same-message entries, from the next call on: 0 every
+        surviving set of a failing segment as a one-set job (the default), 1 the split retry
+        (subs of 8, then the sets of the failing subs).  mode: bool, or 0 / 1."""
+        self._check(self.lib.bgv_sm_retry(self.h, int(mode)))
+
+    def sm_retry_stats(self) -> dict:
+        """bgv_sm_retry_stats: {mode, segments, subs, subs_failed, leaves, pairs, hashes} of the
+        retry of the last same-message call on the context"""
+        out = BgvSmRetryPath()
+        self._check(self.lib.bgv_sm_retry_stats(self.h, ctypes.byref(out)))
         return out.as_dict()
 
     def batch_tail(self, mode) -> None:

@@ -539,6 +539,17 @@ def merge_same_message(calls):
     return groups, where
 
 
+def record_sm_retry(device, metrics: dict) -> None:
+    """the retry of the device's last same-message call (bgv_sm_retry_stats) into sm_retry_subs / _leaves / _pairs:
+    the subs a split retry formed, the sets decided by a check of their own, and the Miller pairs of the retry"""
+    stats = getattr(device, "sm_retry_stats", None)
+    if stats is None:
+        return
+    path = stats()
+    for k in ("subs", "leaves", "pairs"):
+        metrics["sm_retry_" + k] = metrics.get("sm_retry_" + k, 0) + int(path[k])
+
+
 def run_same_message_calls(device, calls, scalars_for=None, metrics: dict | None = None) -> list:
     """One device call (Device.verify_same_message) for the merged calls;
     returns list[bool] per call."""
@@ -552,6 +563,7 @@ def run_same_message_calls(device, calls, scalars_for=None, metrics: dict | None
         st = getattr(device, "last_sm_stats", None)
         metrics["same_message_sets_started"] = metrics.get("same_message_sets_started", 0) + n
         metrics["same_message_retries"] = metrics.get("same_message_retries", 0) + (int(st.groups_retried) if st is not None else 0)
+        record_sm_retry(device, metrics)
     ok = [bool(x) for x in ok]
     return [ok[w] for w in where]
 
@@ -600,6 +612,7 @@ def run_same_message_aggregate_calls(device, calls, scalars_for=None, metrics: d
         st = getattr(device, "last_sm_stats", None)
         metrics["same_message_sets_started"] = metrics.get("same_message_sets_started", 0) + n
         metrics["same_message_retries"] = metrics.get("same_message_retries", 0) + (int(st.groups_retried) if st is not None else 0)
+        record_sm_retry(device, metrics)
         metrics["same_message_aggregated_sigs"] = metrics.get("same_message_aggregated_sigs", 0) + added
     return res
 
@@ -889,6 +902,7 @@ def run_same_message_agg_calls(device, calls, scalars_for=None, metrics: dict | 
             metrics["same_message_agg_sets_started"] = metrics.get("same_message_agg_sets_started", 0) + n
             metrics["same_message_agg_retries"] = (metrics.get("same_message_agg_retries", 0)
                                                    + (int(st.groups_retried) if st is not None else 0))
+            record_sm_retry(device, metrics)
             metrics["aggregated_pubkeys_total"] = (metrics.get("aggregated_pubkeys_total", 0)
                                                    + int(device.bits_path_stats()["keys_expanded"]))
         ok = [bool(x) for x in ok]
@@ -900,6 +914,7 @@ def run_same_message_agg_calls(device, calls, scalars_for=None, metrics: dict | 
         metrics["same_message_agg_sets_started"] = metrics.get("same_message_agg_sets_started", 0) + n
         metrics["same_message_agg_retries"] = (metrics.get("same_message_agg_retries", 0)
                                                + (int(st.groups_retried) if st is not None else 0))
+        record_sm_retry(device, metrics)
         metrics["aggregated_pubkeys_total"] = metrics.get("aggregated_pubkeys_total", 0) + int(arrays["pk_offsets"][-1])
     ok = [bool(x) for x in ok]
     return [ok[w] for w in where]
@@ -929,7 +944,8 @@ class BlsGpuVerifier:
     def __init__(self, devices=(0,), metrics: dict | None = None, scalar_seed: int | None = None,
                  max_sets_per_device_batch: int = MAX_SETS_PER_DEVICE_BATCH, shard_min_sets: int = SHARD_MIN_SETS,
                  priority_cus: int | None = None, bls_verify_all_multi_thread: bool = False,
-                 contexts_per_device: int = CONTEXTS_PER_DEVICE, pair_merge: bool = False, device_cfg: dict | None = None):
+                 contexts_per_device: int = CONTEXTS_PER_DEVICE, pair_merge: bool = False, device_cfg: dict | None = None,
+                 sm_retry: bool = False):
         # priority_cus CUs of the first device (a multiple of 8) are kept for
         # verifyOnMainThread (bgv_cfg.cu_split): its own context runs there,
         # the first bulk context leaves them free; 0 shares every CU.  Default:
@@ -970,6 +986,12 @@ class BlsGpuVerifier:
         if self.pair_merge:
             for d in self.devices:
                 d.pair_merge(True)
+        # sm_retry (bgv_sm_retry, off by default): every context localises the failing sets of a same-message
+        # call by subset checks (subs of 8, then the sets of the failing subs) instead of one-set jobs
+        self.sm_retry = bool(sm_retry)
+        if self.sm_retry:
+            for d in self._contexts():
+                d.sm_retry(1)
         if self.prio is not None:
             self._warm_priority()
         self._prio_lock = threading.Lock()
@@ -1445,8 +1467,10 @@ class BlsGpuSingleThreadVerifier:
     waits, as it does for blst on the main thread); can_accept_work() is always
     True.  Its pubkey table is its own replica."""
 
-    def __init__(self, device: int = 0, metrics: dict | None = None, pair_merge: bool = False):
+    def __init__(self, device: int = 0, metrics: dict | None = None, pair_merge: bool = False, sm_retry: bool = False):
         self.device = native.Device(device)
+        if sm_retry:  # bgv_sm_retry: the split retry of the same-message entries
+            self.device.sm_retry(1)
         if pair_merge:  # bgv_pair_merge: one pair per distinct root of a job in bulk-layout batches
             self.device.pair_merge(True)
         self.table = PubkeyTable([self.device])
@@ -1586,4 +1610,7 @@ def _new_metrics() -> dict:
         "same_message_aggregated_sigs": 0,
         "same_message_agg_sets_started": 0,
         "same_message_agg_retries": 0,
+        "sm_retry_subs": 0,
+        "sm_retry_leaves": 0,
+        "sm_retry_pairs": 0,
     }

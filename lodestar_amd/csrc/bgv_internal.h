@@ -1,5 +1,5 @@
 // Internal interface between the kernels (bgv_kernels.hip) and the host
-// orchestration behind the C ABI (bgv_api.hip).  Not installed.
+// orchestration behind the C ABI (the bgv_api*.hip units, bgv_host.h).  Not installed.
 #pragma once
 #include "pairing.h"
 #include "rng.h"
@@ -194,7 +194,7 @@ void launch_bench_mad(hipStream_t st, uint64_t* io, uint32_t lanes, uint32_t ite
 // Single-pubkey sets grouped by message; every group is cut into segments of
 // at most SM_SEG sets (msm_g1.h).  A segment is a job of the G2 bucket MSM
 // over the real sets and one set = one job of the virtual batch that runs the
-// Miller loops, folds and final exponentiations (bgv_api.hip).
+// Miller loops, folds and final exponentiations (bgv_api_sm.hip).
 enum : int32_t {
   C_SEG_DEAD = 10,   // no set of the segment survived: nothing to pair, nothing to retry
   C_SEG_RETRY = 11,  // sum r_i pk_i is the identity: the sets are decided on their own

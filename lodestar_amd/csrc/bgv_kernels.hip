@@ -1,7 +1,7 @@
 // HIP kernels of the gfx950 BLS12-381 batch verifier.
 //
 // One device batch flows through these stages on the context's stream
-// (host orchestration: bgv_api.hip).  Every stage is one lane per signature
+// (host orchestration: bgv_api.hip and the entry families beside it, bgv_api_*.hip).  Every stage is one lane per signature
 // set (or per job): the per-set work is a long chain of dependent 384-bit
 // Montgomery products on the integer VALU, so the lane is the natural unit
 // and sets are independent.

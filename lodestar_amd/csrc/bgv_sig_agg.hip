@@ -1,6 +1,6 @@
 // Kernels of bgv_verify_same_message_aggregate: the unweighted signature sum of
 // every group of a same-message batch, compressed (sig_agg.h has the rule and
-// the lane order; bgv_api.hip sm_back places the two launches on the pubkey
+// the lane order; bgv_api_sm.hip sm_level places the two launches on the pubkey
 // stream, beside the Miller, fold and final-exponentiation stages).
 //
 // A separate unit: two short, latency-bound kernels (at most four mixed

@@ -4,7 +4,7 @@
 // entries whose bit is set, in ascending position
 // (aggregationBits.intersectValues(committeeIndices) of the reference).
 // Everything here is BGV_HD: the kernels of bgv_bits.hip, the host-side
-// contract check of bgv_api.hip and the stand-alone host test
+// contract check of bgv_api_bits.hip and the stand-alone host test
 // (tests/native/hostcheck_bits.cpp) run the same code.
 #pragma once
 #include "bls_types.h"

@@ -40,7 +40,7 @@ def test_kernels_go_through_the_same_helpers():
     """the kernels and the host check call the header's functions, not copies of them"""
     csrc = os.path.join(os.path.dirname(HERE), "lodestar_amd", "csrc")
     kern = open(os.path.join(csrc, "bgv_bits.hip")).read()
-    api = open(os.path.join(csrc, "bgv_api.hip")).read()
+    api = open(os.path.join(csrc, "bgv_api_bits.hip")).read()
     for fn in ("bits_src_check", "bits_src_word", "bits_src_entry", "bits_words", "bits_popc"):
         assert fn + "(" in kern, fn
     for fn in ("bits_src_check", "bits_src_word", "bits_popc"):

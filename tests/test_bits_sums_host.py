@@ -180,7 +180,7 @@ def test_host_check_and_kernels_share_the_rule():
     csrc = os.path.join(ROOT, "lodestar_amd", "csrc")
     hdr = open(os.path.join(csrc, "bits_expand.h")).read()
     kern = open(os.path.join(csrc, "bgv_bits.hip")).read()
-    api = open(os.path.join(csrc, "bgv_api.hip")).read()
+    api = open(os.path.join(csrc, "bgv_api_bits.hip")).read()
     assert "BGV_HD bool bits_complement(" in hdr and "+ 2u < pop" in hdr
     for src in (kern, api):
         assert "bits_src_complement(" in src

@@ -18,7 +18,7 @@ from lodestar_amd.native import source_hash  # noqa: E402
 CSRC = os.path.join(ROOT, "lodestar_amd", "csrc")
 LIB = os.path.join(ROOT, "lodestar_amd", "libbgv.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-SOURCES = ["bgv_kernels.hip", "bgv_miller.hip", "bgv_latency.hip", "bgv_tail.hip", "bgv_gather.hip", "bgv_same_msg.hip", "bgv_sig_agg.hip", "bgv_bits.hip", "bgv_sums.hip", "bgv_dedup.hip", "bgv_pair_merge.hip", "bgv_api.hip"]
+SOURCES = ["bgv_kernels.hip", "bgv_miller.hip", "bgv_latency.hip", "bgv_tail.hip", "bgv_gather.hip", "bgv_same_msg.hip", "bgv_sig_agg.hip", "bgv_bits.hip", "bgv_sums.hip", "bgv_dedup.hip", "bgv_pair_merge.hip", "bgv_api.hip", "bgv_api_bits.hip", "bgv_api_sm.hip", "bgv_api_debug.hip"]
 
 
 def deps():

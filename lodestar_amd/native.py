@@ -219,14 +219,18 @@ class BgvSmbBatch(ctypes.Structure):
     ]
 
 
-class BgvSmStats(ctypes.Structure):
+class _Counters(ctypes.Structure):
+    """base of the structs of plain counters the library fills: uint32 fields (and bgv_sm_stats' float total_ms)"""
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_}  # ctypes hands back int for uint32, float for float
+
+
+class BgvSmStats(_Counters):
     """bgv_sm_stats (include/bgv.h): counters that show which path ran."""
     _fields_ = [(k, ctypes.c_uint32) for k in
                 ("n_sets", "n_groups", "n_segments", "hashes", "pairs", "groups_retried", "sets_retried")] + [
         ("total_ms", ctypes.c_float)]
-
-    def as_dict(self) -> dict:
-        return {k: (float(getattr(self, k)) if k == "total_ms" else int(getattr(self, k))) for k, _ in self._fields_}
 
 
 class BgvCfg(ctypes.Structure):
@@ -268,55 +272,37 @@ def source_files(root: str = ROOT) -> list[str]:
     return [os.path.join("lodestar_amd", "csrc", f) for f in names] + [os.path.join("include", "bgv.h")]
 
 
-class BgvBitsPath(ctypes.Structure):
+class BgvBitsPath(_Counters):
     """bgv_bits_path (include/bgv.h): path counters of the last bgv_verify_bits"""
     _fields_ = [("sets_complement", ctypes.c_uint32), ("keys_expanded", ctypes.c_uint32), ("keys_gathered", ctypes.c_uint32)]
 
-    def as_dict(self) -> dict:
-        return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
-
-class BgvHashPath(ctypes.Structure):
+class BgvHashPath(_Counters):
     """bgv_hash_path (include/bgv.h): hash_to_G2 evaluations of the last ordinary batch"""
     _fields_ = [("sets", ctypes.c_uint32), ("hashes", ctypes.c_uint32), ("dedup", ctypes.c_uint32)]
 
-    def as_dict(self) -> dict:
-        return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
-
-class BgvMillerPath(ctypes.Structure):
+class BgvMillerPath(_Counters):
     """bgv_miller_path (include/bgv.h): how the Miller stage of the last batch ran"""
     _fields_ = [("steps", ctypes.c_uint32), ("slice_sets", ctypes.c_uint32), ("items", ctypes.c_uint32)]
 
-    def as_dict(self) -> dict:
-        return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
-
-class BgvTailPath(ctypes.Structure):
+class BgvTailPath(_Counters):
     """bgv_tail_path (include/bgv.h): the tail the last ordinary batch ran"""
     _fields_ = [("batch_first", ctypes.c_uint32), ("retried", ctypes.c_uint32)]
 
-    def as_dict(self) -> dict:
-        return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
-
-class BgvPairPath(ctypes.Structure):
+class BgvPairPath(_Counters):
     """bgv_pair_path (include/bgv.h): the set pairs the Miller stage of the last ordinary batch ran"""
     _fields_ = [("sets", ctypes.c_uint32), ("pairs", ctypes.c_uint32), ("merged", ctypes.c_uint32),
                 ("fallback", ctypes.c_uint32)]
 
-    def as_dict(self) -> dict:
-        return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
-
-class BgvSmRetryPath(ctypes.Structure):
+class BgvSmRetryPath(_Counters):
     """bgv_sm_retry_path (include/bgv.h): the retry the last same-message call ran"""
     _fields_ = [("mode", ctypes.c_uint32), ("segments", ctypes.c_uint32), ("subs", ctypes.c_uint32),
                 ("subs_failed", ctypes.c_uint32), ("leaves", ctypes.c_uint32), ("pairs", ctypes.c_uint32),
                 ("hashes", ctypes.c_uint32)]
-
-    def as_dict(self) -> dict:
-        return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
 SM_SUB = 8  # BGV_SM_SUB
@@ -521,29 +507,51 @@ def _count(a, width: int = 1) -> int:
     return int(n) // width
 
 
+# The keys of `arrays` each batch struct cannot do without: a missing one raises KeyError.  Every other pointer
+# is NULL and every other count 0 when its key is absent, and the two derived counts default to their array's size.
+_REQUIRED = {
+    BgvBatch: ("n_sets", "n_jobs", "job_offsets", "pk_offsets", "pk_indices", "msgs"),
+    BgvSmBatch: ("n_sets", "n_groups", "group_offsets", "pk_indices", "msgs", "sigs", "sig_len"),
+    BgvSmaBatch: ("n_sets", "n_groups", "group_offsets", "pk_offsets", "pk_indices", "msgs", "sigs", "sig_len"),
+    BgvBitsBatch: ("n_sets", "n_jobs", "job_offsets", "src"),
+    BgvSmbBatch: ("n_sets", "n_groups", "group_offsets", "src"),
+}
+_DERIVED_COUNT = {"bits_len": "bits", "n_indices": "pk_indices"}
+
+
+def _fill(struct_cls, arrays: dict, on_device: bool, sync_inputs: bool):
+    """A batch struct of include/bgv.h from `arrays` (what the verifier.encode_* function of the same family
+    returns, as numpy arrays or, for an on_device batch, torch tensors), field by field in the struct's own order:
+    a pointer field takes its entry's address, a uint32 field its value.  An on_device batch waits for the
+    producers of its tensors unless sync_inputs is False (Device.make_batch says when that is safe)."""
+    b = struct_cls()
+    required = _REQUIRED[struct_cls]
+    for name, ctype in struct_cls._fields_:
+        if name == "on_device":
+            b.on_device = 1 if on_device else 0
+        elif ctype is ctypes.c_void_p:
+            setattr(b, name, _ptr(arrays[name] if name in required else arrays.get(name)))
+        elif name in _DERIVED_COUNT and name not in arrays:
+            setattr(b, name, _count(arrays.get(_DERIVED_COUNT[name])))
+        else:
+            setattr(b, name, int(arrays[name] if name in required else arrays.get(name, 0)))
+    if on_device and sync_inputs:
+        _sync_producers(arrays)
+    return b
+
+
+def _per_list(values, dtype, via=None) -> np.ndarray:
+    """one entry per index list from the caller's shorter sequence, zero for the lists it does not reach"""
+    out = np.zeros(MAX_INDEX_LISTS, dtype)
+    out[: len(values)] = np.asarray(values, via or dtype)
+    return out
+
+
 def make_bits_batch(arrays: dict, on_device: bool = False, sync_inputs: bool = True) -> BgvBitsBatch:
     """arrays as verifier.encode_jobs_bits returns them: src is a SET_SRC_DTYPE
     record array (or an (n_sets, 4) uint32 array / tensor), bits a uint8 array;
     bits_len and n_indices default to the arrays' sizes"""
-    b = BgvBitsBatch()
-    b.n_sets = int(arrays["n_sets"])
-    b.n_jobs = int(arrays["n_jobs"])
-    b.job_offsets = _ptr(arrays["job_offsets"])
-    b.src = _ptr(arrays["src"])
-    b.bits = _ptr(arrays.get("bits"))
-    b.bits_len = int(arrays["bits_len"]) if "bits_len" in arrays else _count(arrays.get("bits"))
-    b.pk_indices = _ptr(arrays.get("pk_indices"))
-    b.n_indices = int(arrays["n_indices"]) if "n_indices" in arrays else _count(arrays.get("pk_indices"))
-    b.raw_pks = _ptr(arrays.get("raw_pks"))
-    b.n_raw = int(arrays.get("n_raw", 0))
-    b.msgs = _ptr(arrays.get("msgs"))
-    b.sigs = _ptr(arrays.get("sigs"))
-    b.sig_len = _ptr(arrays.get("sig_len"))
-    b.scalars = _ptr(arrays.get("scalars"))
-    b.on_device = 1 if on_device else 0
-    if on_device and sync_inputs:
-        _sync_producers(arrays)
-    return b
+    return _fill(BgvBitsBatch, arrays, on_device, sync_inputs)
 
 
 def bits_check(arrays: dict, list_len, on_device: bool = False) -> tuple[int, str]:
@@ -552,8 +560,7 @@ def bits_check(arrays: dict, list_len, on_device: bool = False) -> tuple[int, st
     (status, bgv_last_error() text); the text is empty for BGV_OK."""
     lib = load_library()
     b = make_bits_batch(arrays, on_device, sync_inputs=False)
-    ll = np.zeros(MAX_INDEX_LISTS, np.uint32)
-    ll[: len(list_len)] = np.asarray(list_len, np.uint32)
+    ll = _per_list(list_len, np.uint32)
     st = lib.bgv_bits_check(ctypes.byref(b), ll.ctypes.data)
     return st, ("" if st == BGV_OK else lib.bgv_last_error().decode())
 
@@ -562,25 +569,7 @@ def make_smb_batch(arrays: dict, on_device: bool = False, sync_inputs: bool = Tr
     """arrays as verifier.encode_same_message_bits returns them: the groups of a
     same-message batch, the sources of a bits batch; bits_len and n_indices
     default to the arrays' sizes"""
-    b = BgvSmbBatch()
-    b.n_sets = int(arrays["n_sets"])
-    b.n_groups = int(arrays["n_groups"])
-    b.group_offsets = _ptr(arrays["group_offsets"])
-    b.src = _ptr(arrays["src"])
-    b.bits = _ptr(arrays.get("bits"))
-    b.bits_len = int(arrays["bits_len"]) if "bits_len" in arrays else _count(arrays.get("bits"))
-    b.pk_indices = _ptr(arrays.get("pk_indices"))
-    b.n_indices = int(arrays["n_indices"]) if "n_indices" in arrays else _count(arrays.get("pk_indices"))
-    b.raw_pks = _ptr(arrays.get("raw_pks"))
-    b.n_raw = int(arrays.get("n_raw", 0))
-    b.msgs = _ptr(arrays.get("msgs"))
-    b.sigs = _ptr(arrays.get("sigs"))
-    b.sig_len = _ptr(arrays.get("sig_len"))
-    b.scalars = _ptr(arrays.get("scalars"))
-    b.on_device = 1 if on_device else 0
-    if on_device and sync_inputs:
-        _sync_producers(arrays)
-    return b
+    return _fill(BgvSmbBatch, arrays, on_device, sync_inputs)
 
 
 def smb_check(arrays: dict, list_len, on_device: bool = False) -> tuple[int, str]:
@@ -589,8 +578,7 @@ def smb_check(arrays: dict, list_len, on_device: bool = False) -> tuple[int, str
     Returns (status, bgv_last_error() text); the text is empty for BGV_OK."""
     lib = load_library()
     b = make_smb_batch(arrays, on_device, sync_inputs=False)
-    ll = np.zeros(MAX_INDEX_LISTS, np.uint32)
-    ll[: len(list_len)] = np.asarray(list_len, np.uint32)
+    ll = _per_list(list_len, np.uint32)
     st = lib.bgv_smb_check(ctypes.byref(b), ll.ctypes.data)
     return st, ("" if st == BGV_OK else lib.bgv_last_error().decode())
 
@@ -603,11 +591,8 @@ def bits_plan(arrays: dict, list_len, list_has_sums=None, on_device: bool = Fals
     batch only."""
     lib = load_library()
     b = make_bits_batch(arrays, on_device, sync_inputs=False)
-    ll = np.zeros(MAX_INDEX_LISTS, np.uint32)
-    ll[: len(list_len)] = np.asarray(list_len, np.uint32)
-    hs = np.zeros(MAX_INDEX_LISTS, np.uint8)
-    if list_has_sums is not None:
-        hs[: len(list_has_sums)] = np.asarray(list_has_sums, bool)
+    ll = _per_list(list_len, np.uint32)
+    hs = _per_list(() if list_has_sums is None else list_has_sums, np.uint8, bool)
     path = np.zeros(max(b.n_sets, 1), np.uint8)
     kg = ctypes.c_uint64()
     st = lib.bgv_bits_plan(ctypes.byref(b), ll.ctypes.data, hs.ctypes.data, path.ctypes.data, ctypes.byref(kg))
@@ -639,6 +624,12 @@ class Device:
     def _check(self, st: int):
         if st != BGV_OK:
             raise BgvNativeError(st, self.lib.bgv_last_error().decode())
+
+    def _read(self, fn, struct_cls) -> dict:
+        """a counter struct of the context, read by the getter fn(ctx, out), as a dict"""
+        out = struct_cls()
+        self._check(fn(self.h, ctypes.byref(out)))
+        return out.as_dict()
 
     def stage_name(self, i: int) -> str:
         return self.lib.bgv_stage_name(i).decode()
@@ -691,22 +682,7 @@ class Device:
         inputs that are only read afterwards), and the per-call wait for torch's
         current stream is skipped; that wait can sit behind other contexts'
         kernels on a shared hardware queue."""
-        b = BgvBatch()
-        b.n_sets = int(arrays["n_sets"])
-        b.n_jobs = int(arrays["n_jobs"])
-        b.job_offsets = _ptr(arrays["job_offsets"])
-        b.pk_offsets = _ptr(arrays["pk_offsets"])
-        b.pk_indices = _ptr(arrays["pk_indices"])
-        b.raw_pks = _ptr(arrays.get("raw_pks"))
-        b.n_raw = int(arrays.get("n_raw", 0))
-        b.msgs = _ptr(arrays["msgs"])
-        b.sigs = _ptr(arrays.get("sigs"))
-        b.sig_len = _ptr(arrays.get("sig_len"))
-        b.scalars = _ptr(arrays.get("scalars"))
-        b.on_device = 1 if on_device else 0
-        if on_device and sync_inputs:
-            _sync_producers(arrays)
-        return b
+        return _fill(BgvBatch, arrays, on_device, sync_inputs)
 
     def verify(self, arrays: dict, on_device: bool = False, want_set_codes: bool = True, sync_inputs: bool = True):
         """returns (job_result int32[n_jobs], set_code int32[n_sets] | None)"""
@@ -720,32 +696,35 @@ class Device:
     @staticmethod
     def make_sm_batch(arrays: dict, on_device: bool = False, sync_inputs: bool = True) -> BgvSmBatch:
         """arrays as verifier.encode_same_message returns them"""
-        b = BgvSmBatch()
-        b.n_sets = int(arrays["n_sets"])
-        b.n_groups = int(arrays["n_groups"])
-        b.group_offsets = _ptr(arrays["group_offsets"])
-        b.pk_indices = _ptr(arrays["pk_indices"])
-        b.raw_pks = _ptr(arrays.get("raw_pks"))
-        b.n_raw = int(arrays.get("n_raw", 0))
-        b.msgs = _ptr(arrays["msgs"])
-        b.sigs = _ptr(arrays["sigs"])
-        b.sig_len = _ptr(arrays["sig_len"])
-        b.scalars = _ptr(arrays.get("scalars"))
-        b.on_device = 1 if on_device else 0
-        if on_device and sync_inputs:
-            _sync_producers(arrays)
-        return b
+        return _fill(BgvSmBatch, arrays, on_device, sync_inputs)
+
+    def _sm_call(self, fn, b, outs=(), agg=None) -> dict:
+        """One call of a same-message entry.  Allocates set_valid, set_code and the entry's own outputs `outs`
+        ((key, "n" or "G", row shape, dtype): one row per set or per group), resets last_sm_stats and calls
+        fn(ctx, batch, set_valid, set_code, stats, *outs); returns every buffer cut to the batch's n sets and G
+        groups, set_valid as bool.  agg: builds the bgv_sm_agg of the aggregate entry from the buffers, which then
+        carries `outs` to the library as the argument after the batch."""
+        rows = {"n": b.n_sets, "G": b.n_groups}
+        spec = (("set_valid", "n", (), np.uint8), ("set_code", "n", (), np.int32)) + tuple(outs)
+        buf = {k: np.zeros((max(rows[r], 1),) + shape, dt) for k, r, shape, dt in spec}
+        self.last_sm_stats = BgvSmStats()
+        a = agg(buf) if agg else None
+        self._check(fn(self.h, ctypes.byref(b), *((ctypes.byref(a),) if agg else ()), buf["set_valid"].ctypes.data,
+                       buf["set_code"].ctypes.data, ctypes.byref(self.last_sm_stats),
+                       *(() if agg else [buf[k].ctypes.data for k, *_ in outs])))
+        out = {k: buf[k][: rows[r]] for k, r, _shape, _dt in spec}
+        out["set_valid"] = out["set_valid"].astype(bool)
+        return out
+
+    # the per-group and per-set values the debug entries return beside the verdicts
+    _GROUP_OUTS = (("p_group", "G", (96,), np.uint8), ("s_group", "G", (192,), np.uint8), ("h_group", "G", (192,), np.uint8))
+    _PK_SET_OUT = ("pk_set", "n", (96,), np.uint8)
 
     def verify_same_message(self, arrays: dict, on_device: bool = False, sync_inputs: bool = True):
         """bgv_verify_same_message: (set_valid bool[n_sets], set_code int32[n_sets]);
         the counters of the call are left in last_sm_stats"""
-        b = self.make_sm_batch(arrays, on_device, sync_inputs)
-        ok = np.zeros(max(b.n_sets, 1), dtype=np.uint8)
-        sc = np.zeros(max(b.n_sets, 1), dtype=np.int32)
-        self.last_sm_stats = BgvSmStats()
-        self._check(self.lib.bgv_verify_same_message(self.h, ctypes.byref(b), ok.ctypes.data, sc.ctypes.data,
-                                                     ctypes.byref(self.last_sm_stats)))
-        return ok[: b.n_sets].astype(bool), sc[: b.n_sets]
+        o = self._sm_call(self.lib.bgv_verify_same_message, self.make_sm_batch(arrays, on_device, sync_inputs))
+        return o["set_valid"], o["set_code"]
 
     def verify_same_message_aggregate(self, arrays: dict, take=None, prev=None, on_device: bool = False,
                                       sync_inputs: bool = True) -> dict:
@@ -760,19 +739,11 @@ class Device:
             prev = None if prev is None else np.ascontiguousarray(prev, np.uint8)
         elif sync_inputs:
             _sync_producers(take, prev)
-        n, G = b.n_sets, b.n_groups
-        ok = np.zeros(max(n, 1), dtype=np.uint8)
-        sc = np.zeros(max(n, 1), dtype=np.int32)
-        sig = np.zeros((max(G, 1), 96), np.uint8)
-        cnt = np.zeros(max(G, 1), np.uint32)
-        code = np.zeros(max(G, 1), np.int32)
-        a = BgvSmAgg(take=_ptr(take), prev_sig96=_ptr(prev), agg_sig96=sig.ctypes.data, agg_count=cnt.ctypes.data,
-                     agg_code=code.ctypes.data)
-        self.last_sm_stats = BgvSmStats()
-        self._check(self.lib.bgv_verify_same_message_aggregate(self.h, ctypes.byref(b), ctypes.byref(a), ok.ctypes.data,
-                                                               sc.ctypes.data, ctypes.byref(self.last_sm_stats)))
-        return {"set_valid": ok[:n].astype(bool), "set_code": sc[:n], "agg_sig": sig[:G], "agg_count": cnt[:G],
-                "agg_code": code[:G], "stats": self.last_sm_stats.as_dict()}
+        outs = (("agg_sig", "G", (96,), np.uint8), ("agg_count", "G", (), np.uint32), ("agg_code", "G", (), np.int32))
+        o = self._sm_call(self.lib.bgv_verify_same_message_aggregate, b, outs, agg=lambda buf: BgvSmAgg(
+            take=_ptr(take), prev_sig96=_ptr(prev), agg_sig96=buf["agg_sig"].ctypes.data,
+            agg_count=buf["agg_count"].ctypes.data, agg_code=buf["agg_code"].ctypes.data))
+        return {**o, "stats": self.last_sm_stats.as_dict()}
 
     def sm_agg_ms(self) -> float:
         """bgv_sm_agg_ms: device time of the two sum kernels in the first pass of the last
@@ -783,100 +754,41 @@ class Device:
 
     def debug_same_message(self, arrays: dict, on_device: bool = False) -> dict:
         """bgv_debug_same_message (test only): the verdicts plus P_g, S_g and H(m_g) per group"""
-        b = self.make_sm_batch(arrays, on_device)
-        n, G = b.n_sets, b.n_groups
-        ok = np.zeros(max(n, 1), dtype=np.uint8)
-        sc = np.zeros(max(n, 1), dtype=np.int32)
-        pg = np.zeros((max(G, 1), 96), np.uint8)
-        sg = np.zeros((max(G, 1), 192), np.uint8)
-        hg = np.zeros((max(G, 1), 192), np.uint8)
-        self.last_sm_stats = BgvSmStats()
-        self._check(self.lib.bgv_debug_same_message(self.h, ctypes.byref(b), ok.ctypes.data, sc.ctypes.data,
-                                                    ctypes.byref(self.last_sm_stats), pg.ctypes.data, sg.ctypes.data,
-                                                    hg.ctypes.data))
-        return {"set_valid": ok[:n].astype(bool), "set_code": sc[:n], "p_group": pg[:G], "s_group": sg[:G],
-                "h_group": hg[:G], "stats": self.last_sm_stats.as_dict()}
+        o = self._sm_call(self.lib.bgv_debug_same_message, self.make_sm_batch(arrays, on_device), self._GROUP_OUTS)
+        return {**o, "stats": self.last_sm_stats.as_dict()}
 
     @staticmethod
     def make_sma_batch(arrays: dict, on_device: bool = False, sync_inputs: bool = True) -> BgvSmaBatch:
         """arrays as verifier.encode_same_message_agg returns them"""
-        b = BgvSmaBatch()
-        b.n_sets = int(arrays["n_sets"])
-        b.n_groups = int(arrays["n_groups"])
-        b.group_offsets = _ptr(arrays["group_offsets"])
-        b.pk_offsets = _ptr(arrays["pk_offsets"])
-        b.pk_indices = _ptr(arrays["pk_indices"])
-        b.raw_pks = _ptr(arrays.get("raw_pks"))
-        b.n_raw = int(arrays.get("n_raw", 0))
-        b.msgs = _ptr(arrays["msgs"])
-        b.sigs = _ptr(arrays["sigs"])
-        b.sig_len = _ptr(arrays["sig_len"])
-        b.scalars = _ptr(arrays.get("scalars"))
-        b.on_device = 1 if on_device else 0
-        if on_device and sync_inputs:
-            _sync_producers(arrays)
-        return b
+        return _fill(BgvSmaBatch, arrays, on_device, sync_inputs)
 
     def verify_same_message_agg(self, arrays: dict, on_device: bool = False, sync_inputs: bool = True):
         """bgv_verify_same_message_agg: (set_valid bool[n_sets], set_code int32[n_sets]);
         the counters of the call are left in last_sm_stats"""
-        b = self.make_sma_batch(arrays, on_device, sync_inputs)
-        ok = np.zeros(max(b.n_sets, 1), dtype=np.uint8)
-        sc = np.zeros(max(b.n_sets, 1), dtype=np.int32)
-        self.last_sm_stats = BgvSmStats()
-        self._check(self.lib.bgv_verify_same_message_agg(self.h, ctypes.byref(b), ok.ctypes.data, sc.ctypes.data,
-                                                         ctypes.byref(self.last_sm_stats)))
-        return ok[: b.n_sets].astype(bool), sc[: b.n_sets]
+        o = self._sm_call(self.lib.bgv_verify_same_message_agg, self.make_sma_batch(arrays, on_device, sync_inputs))
+        return o["set_valid"], o["set_code"]
 
     def debug_same_message_agg(self, arrays: dict, on_device: bool = False) -> dict:
         """bgv_debug_same_message_agg (test only): the verdicts plus PK_i per set and
         P_g, S_g and H(m_g) per group"""
-        b = self.make_sma_batch(arrays, on_device)
-        n, G = b.n_sets, b.n_groups
-        ok = np.zeros(max(n, 1), dtype=np.uint8)
-        sc = np.zeros(max(n, 1), dtype=np.int32)
-        ps = np.zeros((max(n, 1), 96), np.uint8)
-        pg = np.zeros((max(G, 1), 96), np.uint8)
-        sg = np.zeros((max(G, 1), 192), np.uint8)
-        hg = np.zeros((max(G, 1), 192), np.uint8)
-        self.last_sm_stats = BgvSmStats()
-        self._check(self.lib.bgv_debug_same_message_agg(self.h, ctypes.byref(b), ok.ctypes.data, sc.ctypes.data,
-                                                        ctypes.byref(self.last_sm_stats), ps.ctypes.data, pg.ctypes.data,
-                                                        sg.ctypes.data, hg.ctypes.data))
-        return {"set_valid": ok[:n].astype(bool), "set_code": sc[:n], "pk_set": ps[:n], "p_group": pg[:G],
-                "s_group": sg[:G], "h_group": hg[:G], "stats": self.last_sm_stats.as_dict()}
+        o = self._sm_call(self.lib.bgv_debug_same_message_agg, self.make_sma_batch(arrays, on_device),
+                          (self._PK_SET_OUT,) + self._GROUP_OUTS)
+        return {**o, "stats": self.last_sm_stats.as_dict()}
 
     make_smb_batch = staticmethod(make_smb_batch)
 
     def verify_same_message_bits(self, arrays: dict, on_device: bool = False, sync_inputs: bool = True):
         """bgv_verify_same_message_bits: (set_valid bool[n_sets], set_code int32[n_sets]);
         the counters of the call are left in last_sm_stats, its key counts in bits_path_stats()"""
-        b = make_smb_batch(arrays, on_device, sync_inputs)
-        ok = np.zeros(max(b.n_sets, 1), dtype=np.uint8)
-        sc = np.zeros(max(b.n_sets, 1), dtype=np.int32)
-        self.last_sm_stats = BgvSmStats()
-        self._check(self.lib.bgv_verify_same_message_bits(self.h, ctypes.byref(b), ok.ctypes.data, sc.ctypes.data,
-                                                          ctypes.byref(self.last_sm_stats)))
-        return ok[: b.n_sets].astype(bool), sc[: b.n_sets]
+        o = self._sm_call(self.lib.bgv_verify_same_message_bits, make_smb_batch(arrays, on_device, sync_inputs))
+        return o["set_valid"], o["set_code"]
 
     def debug_same_message_bits(self, arrays: dict, on_device: bool = False) -> dict:
         """bgv_debug_same_message_bits (test only): the outputs of debug_same_message_agg
         plus path uint8[n_sets] (1: complement path)"""
-        b = make_smb_batch(arrays, on_device)
-        n, G = b.n_sets, b.n_groups
-        ok = np.zeros(max(n, 1), dtype=np.uint8)
-        sc = np.zeros(max(n, 1), dtype=np.int32)
-        ps = np.zeros((max(n, 1), 96), np.uint8)
-        path = np.zeros(max(n, 1), np.uint8)
-        pg = np.zeros((max(G, 1), 96), np.uint8)
-        sg = np.zeros((max(G, 1), 192), np.uint8)
-        hg = np.zeros((max(G, 1), 192), np.uint8)
-        self.last_sm_stats = BgvSmStats()
-        self._check(self.lib.bgv_debug_same_message_bits(self.h, ctypes.byref(b), ok.ctypes.data, sc.ctypes.data,
-                                                         ctypes.byref(self.last_sm_stats), ps.ctypes.data, path.ctypes.data,
-                                                         pg.ctypes.data, sg.ctypes.data, hg.ctypes.data))
-        return {"set_valid": ok[:n].astype(bool), "set_code": sc[:n], "pk_set": ps[:n], "path": path[:n], "p_group": pg[:G],
-                "s_group": sg[:G], "h_group": hg[:G], "stats": self.last_sm_stats.as_dict()}
+        o = self._sm_call(self.lib.bgv_debug_same_message_bits, make_smb_batch(arrays, on_device),
+                          (self._PK_SET_OUT, ("path", "n", (), np.uint8)) + self._GROUP_OUTS)
+        return {**o, "stats": self.last_sm_stats.as_dict()}
 
     # ------------------------------------------- committee bitfields (bgv_verify_bits)
     def index_list_set(self, list_id: int, indices) -> None:
@@ -908,9 +820,7 @@ class Device:
         """bgv_hash_stats: {sets, hashes, dedup} of the last verify, verify_bits, partial or
         debug_stages on the context (hashes: the hash_to_G2 evaluations, the distinct signing
         roots when dedup is 1); zeros after a same-message call"""
-        out = BgvHashPath()
-        self._check(self.lib.bgv_hash_stats(self.h, ctypes.byref(out)))
-        return out.as_dict()
+        return self._read(self.lib.bgv_hash_stats, BgvHashPath)
 
     def pair_merge(self, on) -> None:
         """bgv_pair_merge: one Miller pair per distinct signing root of a job, from the next
@@ -921,9 +831,7 @@ class Device:
         """bgv_pair_stats: {sets, pairs, merged, fallback} of the last verify, verify_bits or
         partial on the context (pairs: the classes when merged is 1, else sets); zeros after
         any other entry"""
-        out = BgvPairPath()
-        self._check(self.lib.bgv_pair_stats(self.h, ctypes.byref(out)))
-        return out.as_dict()
+        return self._read(self.lib.bgv_pair_stats, BgvPairPath)
 
     def sm_retry(self, mode) -> None:
         """bgv_sm_retry: the retry of the same-message entries, from the next call on: 0 every
@@ -934,9 +842,7 @@ class Device:
     def sm_retry_stats(self) -> dict:
         """bgv_sm_retry_stats: {mode, segments, subs, subs_failed, leaves, pairs, hashes} of the
         retry of the last same-message call on the context"""
-        out = BgvSmRetryPath()
-        self._check(self.lib.bgv_sm_retry_stats(self.h, ctypes.byref(out)))
-        return out.as_dict()
+        return self._read(self.lib.bgv_sm_retry_stats, BgvSmRetryPath)
 
     def batch_tail(self, mode) -> None:
         """bgv_batch_tail: the batch-first tail of the steps path, from the next call on:
@@ -946,9 +852,7 @@ class Device:
     def tail_path(self) -> dict:
         """bgv_tail_stats: {batch_first, retried} of the last verify, verify_bits or partial
         (+ partial_finish) on the context"""
-        out = BgvTailPath()
-        self._check(self.lib.bgv_tail_stats(self.h, ctypes.byref(out)))
-        return out.as_dict()
+        return self._read(self.lib.bgv_tail_stats, BgvTailPath)
 
     def debug_pair_classes(self, arrays: dict, on_device: bool = False) -> dict:
         """bgv_debug_pair_classes (test only): verify through the merged path plus cls
@@ -971,16 +875,12 @@ class Device:
     def miller_path(self) -> dict:
         """bgv_miller_path_stats: {steps, slice_sets, items} of the last verify, verify_bits,
         partial or debug_stages on the context (steps 1: per-step line products, bgv_cfg.miller_steps)"""
-        out = BgvMillerPath()
-        self._check(self.lib.bgv_miller_path_stats(self.h, ctypes.byref(out)))
-        return out.as_dict()
+        return self._read(self.lib.bgv_miller_path_stats, BgvMillerPath)
 
     def bits_path_stats(self) -> dict:
         """bgv_bits_path_stats: {sets_complement, keys_expanded, keys_gathered} of the last
         verify_bits or verify_same_message_bits"""
-        out = BgvBitsPath()
-        self._check(self.lib.bgv_bits_path_stats(self.h, ctypes.byref(out)))
-        return out.as_dict()
+        return self._read(self.lib.bgv_bits_path_stats, BgvBitsPath)
 
     bits_plan = staticmethod(bits_plan)
 

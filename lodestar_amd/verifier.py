@@ -244,57 +244,97 @@ class PubkeyTable:
 
 
 # ------------------------------------------------------- batch marshalling
+class _SetArrays:
+    """What the five encoders share: the per-set arrays of a batch (include/bgv.h), filled one set at a time by
+    keys() or committee(), then signature().  Keys land in pk_indices (table rows, or bit 31 and a row of raw_pks,
+    every distinct raw key stored once); a set's keys are delimited by pk_offsets, or with `sources` by a bgv_set_src
+    record (an explicit run of pk_indices, or a committee over the packed bitfields)."""
+
+    def __init__(self, n_sets: int, offsets: bool = False, sources: bool = False):
+        self.n = 0  # sets finished: the row signature() fills next
+        self.idx: list[int] = []
+        self.raw: list[bytes] = []
+        self.raw_pos: dict[bytes, int] = {}
+        self.pk_off = [0] if offsets else None
+        self.src = np.zeros(max(n_sets, 1), dtype=native.SET_SRC_DTYPE) if sources else None
+        self.bits = bytearray()
+        self.sigs = np.zeros((max(n_sets, 1), 192), dtype=np.uint8)
+        self.sig_len = np.zeros(max(n_sets, 1), dtype=np.uint32)
+
+    def keys(self, pks) -> None:
+        """these keys (PublicKeys) for the current set; none raises like PublicKey.aggregate"""
+        if len(pks) == 0:
+            raise BlsError("EMPTY_AGGREGATE_ARRAY")
+        if self.src is not None:
+            self.src[self.n] = (native.SRC_EXPLICIT, len(self.idx), len(pks), 0)
+        for pk in pks:
+            if pk.index is not None:
+                self.idx.append(pk.index)
+            else:
+                r = pk.raw if len(pk.raw) == 96 else _decompress_raw48(pk.raw)
+                if r not in self.raw_pos:
+                    self.raw_pos[r] = len(self.raw)
+                    self.raw.append(r)
+                self.idx.append(0x80000000 | self.raw_pos[r])
+        if self.pk_off is not None:
+            self.pk_off.append(len(self.idx))
+
+    def committee(self, c: CommitteeRef, bits: bytes) -> None:
+        """this committee and bitfield for the current set"""
+        if len(bits) != (c.length + 7) // 8:
+            raise _bitfield_error(c, bits)
+        self.src[self.n] = (c.list_id, c.offset, c.length, len(self.bits))
+        self.bits += bits
+
+    def signature(self, sig: bytes) -> None:
+        """this signature, which ends the current set; a length other than 96 or 192 leaves the row zero"""
+        sl = len(sig)
+        self.sig_len[self.n] = sl
+        if sl in (96, 192):
+            self.sigs[self.n, :sl] = np.frombuffer(bytes(sig), dtype=np.uint8)
+        self.n += 1
+
+    def finish(self, msgs: np.ndarray, scalars) -> dict:
+        """the entries every encoder's result ends with, after its own head (counts and job or group offsets)"""
+        out = {}
+        if self.pk_off is not None:
+            out["pk_offsets"] = np.array(self.pk_off, dtype=np.uint32)
+        if self.src is not None:
+            out["src"] = self.src
+            out["bits"] = np.frombuffer(bytes(self.bits), dtype=np.uint8).copy() if self.bits else np.zeros(1, np.uint8)
+            out["bits_len"] = len(self.bits)
+        out["pk_indices"] = np.array(self.idx if self.idx else [0], dtype=np.uint32)
+        if self.src is not None:
+            out["n_indices"] = len(self.idx)
+        out["raw_pks"] = np.frombuffer(b"".join(self.raw), dtype=np.uint8).copy() if self.raw else None
+        out.update(n_raw=len(self.raw), msgs=msgs, sigs=self.sigs, sig_len=self.sig_len, scalars=scalars)
+        return out
+
+
+def _put_root(msgs: np.ndarray, row: int, root: bytes) -> None:
+    if len(root) != 32:
+        raise BlsError("signingRoot must be 32 bytes")
+    msgs[row] = np.frombuffer(bytes(root), dtype=np.uint8)
+
+
+def _set_keys(s: ISignatureSet) -> list:
+    return [s.pubkey] if s.type == SignatureSetType.single else s.pubkeys
+
+
 def encode_jobs(jobs: list[list[ISignatureSet]], scalars: np.ndarray | None = None) -> dict:
     """Flatten jobs of sets into the SoA arrays of bgv_batch (include/bgv.h).
     Raises BlsError("EMPTY_AGGREGATE_ARRAY") like PublicKey.aggregate."""
-    job_off = [0]
-    pk_off = [0]
-    idx: list[int] = []
-    raw: list[bytes] = []
-    raw_pos: dict[bytes, int] = {}
     n = sum(len(j) for j in jobs)
+    acc = _SetArrays(n, offsets=True)
     msgs = np.zeros((max(n, 1), 32), dtype=np.uint8)
-    sigs = np.zeros((max(n, 1), 192), dtype=np.uint8)
-    sig_len = np.zeros(max(n, 1), dtype=np.uint32)
-    i = 0
+    job_off = [0]
     for job in jobs:
         for s in job:
-            pks = [s.pubkey] if s.type == SignatureSetType.single else s.pubkeys
-            if len(pks) == 0:
-                raise BlsError("EMPTY_AGGREGATE_ARRAY")
-            for pk in pks:
-                if pk.index is not None:
-                    idx.append(pk.index)
-                else:
-                    r = pk.raw if len(pk.raw) == 96 else _decompress_raw48(pk.raw)
-                    if r not in raw_pos:
-                        raw_pos[r] = len(raw)
-                        raw.append(r)
-                    idx.append(0x80000000 | raw_pos[r])
-            pk_off.append(len(idx))
-            if len(s.signingRoot) != 32:
-                raise BlsError("signingRoot must be 32 bytes")
-            msgs[i] = np.frombuffer(s.signingRoot, dtype=np.uint8)
-            sl = len(s.signature)
-            sig_len[i] = sl
-            if sl in (96, 192):
-                sigs[i, :sl] = np.frombuffer(s.signature, dtype=np.uint8)
-            i += 1
-        job_off.append(i)
-    out = {
-        "n_sets": n,
-        "n_jobs": len(jobs),
-        "job_offsets": np.array(job_off, dtype=np.uint32),
-        "pk_offsets": np.array(pk_off, dtype=np.uint32),
-        "pk_indices": np.array(idx if idx else [0], dtype=np.uint32),
-        "raw_pks": np.frombuffer(b"".join(raw), dtype=np.uint8).copy() if raw else None,
-        "n_raw": len(raw),
-        "msgs": msgs,
-        "sigs": sigs,
-        "sig_len": sig_len,
-        "scalars": scalars,
-    }
-    return out
+            acc.keys(_set_keys(s))
+            _put_root(msgs, acc.n, s.signingRoot)
+            acc.signature(s.signature)
+        job_off.append(acc.n)
+    return {"n_sets": n, "n_jobs": len(jobs), "job_offsets": np.array(job_off, dtype=np.uint32), **acc.finish(msgs, scalars)}
 
 
 def has_committee_sets(jobs) -> bool:
@@ -305,64 +345,20 @@ def encode_jobs_bits(jobs: list[list[ISignatureSet]], scalars: np.ndarray | None
     """Flatten jobs of sets into the arrays of bgv_bits_batch (include/bgv.h):
     single and aggregate sets become explicit sources over pk_indices, committee
     sets list sources over the packed bitfields.  Raises BlsError like encode_jobs."""
-    job_off = [0]
-    idx: list[int] = []
-    raw: list[bytes] = []
-    raw_pos: dict[bytes, int] = {}
-    bits = bytearray()
     n = sum(len(j) for j in jobs)
-    src = np.zeros(max(n, 1), dtype=native.SET_SRC_DTYPE)
+    acc = _SetArrays(n, sources=True)
     msgs = np.zeros((max(n, 1), 32), dtype=np.uint8)
-    sigs = np.zeros((max(n, 1), 192), dtype=np.uint8)
-    sig_len = np.zeros(max(n, 1), dtype=np.uint32)
-    i = 0
+    job_off = [0]
     for job in jobs:
         for s in job:
             if s.type == SignatureSetType.committee:
-                c = s.committee
-                if len(s.bits) != (c.length + 7) // 8:
-                    raise BlsError(f"committee set: {len(s.bits)} bitfield bytes for {c.length} members")
-                src[i] = (c.list_id, c.offset, c.length, len(bits))
-                bits += s.bits
+                acc.committee(s.committee, s.bits)
             else:
-                pks = [s.pubkey] if s.type == SignatureSetType.single else s.pubkeys
-                if len(pks) == 0:
-                    raise BlsError("EMPTY_AGGREGATE_ARRAY")
-                src[i] = (native.SRC_EXPLICIT, len(idx), len(pks), 0)
-                for pk in pks:
-                    if pk.index is not None:
-                        idx.append(pk.index)
-                    else:
-                        r = pk.raw if len(pk.raw) == 96 else _decompress_raw48(pk.raw)
-                        if r not in raw_pos:
-                            raw_pos[r] = len(raw)
-                            raw.append(r)
-                        idx.append(0x80000000 | raw_pos[r])
-            if len(s.signingRoot) != 32:
-                raise BlsError("signingRoot must be 32 bytes")
-            msgs[i] = np.frombuffer(s.signingRoot, dtype=np.uint8)
-            sl = len(s.signature)
-            sig_len[i] = sl
-            if sl in (96, 192):
-                sigs[i, :sl] = np.frombuffer(s.signature, dtype=np.uint8)
-            i += 1
-        job_off.append(i)
-    return {
-        "n_sets": n,
-        "n_jobs": len(jobs),
-        "job_offsets": np.array(job_off, dtype=np.uint32),
-        "src": src,
-        "bits": np.frombuffer(bytes(bits), dtype=np.uint8).copy() if bits else np.zeros(1, np.uint8),
-        "bits_len": len(bits),
-        "pk_indices": np.array(idx if idx else [0], dtype=np.uint32),
-        "n_indices": len(idx),
-        "raw_pks": np.frombuffer(b"".join(raw), dtype=np.uint8).copy() if raw else None,
-        "n_raw": len(raw),
-        "msgs": msgs,
-        "sigs": sigs,
-        "sig_len": sig_len,
-        "scalars": scalars,
-    }
+                acc.keys(_set_keys(s))
+            _put_root(msgs, acc.n, s.signingRoot)
+            acc.signature(s.signature)
+        job_off.append(acc.n)
+    return {"n_sets": n, "n_jobs": len(jobs), "job_offsets": np.array(job_off, dtype=np.uint32), **acc.finish(msgs, scalars)}
 
 
 def encode_device_batch(jobs: list[list[ISignatureSet]], scalars: np.ndarray | None = None) -> tuple[bool, dict]:
@@ -385,6 +381,31 @@ def _decompress_raw48(b: bytes) -> bytes:
     raise BlsError("raw compressed pubkeys must be added to the table (PubkeyTable.add_pubkey)")
 
 
+def _check_key(pk) -> None:
+    """the caller-side checks of one key: it exists, a raw key is a 96-byte uncompressed point (compressed keys
+    live in the table), an index fits the 31 bits pk_indices leaves it"""
+    if pk is None:
+        raise BlsError("EMPTY_AGGREGATE_ARRAY")
+    if pk.index is None and len(pk.raw) != 96:
+        _decompress_raw48(pk.raw)
+    if pk.index is not None and not (0 <= pk.index < 0x80000000):
+        raise BlsError(f"pubkey index {pk.index} out of range")
+
+
+def _bitfield_error(c: CommitteeRef, bits: bytes) -> BlsError:
+    return BlsError(f"committee set: {len(bits)} bitfield bytes for {c.length} members")
+
+
+def _check_committee(c: CommitteeRef | None, bits: bytes | None) -> None:
+    """the caller-side checks of a committee and its participation bits"""
+    if c is None or bits is None or not (0 <= c.list_id < native.MAX_INDEX_LISTS):
+        raise BlsError("committee set without a committee, bits or a valid list id")
+    if c.offset < 0 or c.length < 0 or c.offset + c.length > 0xFFFFFFFF or len(bits) != (c.length + 7) // 8:
+        raise _bitfield_error(c, bits)
+    if not any(bits):  # intersectValues gives no index: PublicKey.aggregate throws
+        raise BlsError("EMPTY_AGGREGATE_ARRAY")
+
+
 def check_sets(sets: list[ISignatureSet]) -> None:
     """Caller-side checks of one verifySignatureSets call: PublicKey.aggregate
     throws EMPTY_AGGREGATE_ARRAY (chain/bls/utils.ts:11); a raw key must be a
@@ -393,26 +414,13 @@ def check_sets(sets: list[ISignatureSet]) -> None:
     the device (BGV_INDEX_RANGE rejects only that job)."""
     for s in sets:
         if s.type == SignatureSetType.committee:
-            c = s.committee
-            if c is None or s.bits is None or not (0 <= c.list_id < native.MAX_INDEX_LISTS):
-                raise BlsError("committee set without a committee, bits or a valid list id")
-            if c.offset < 0 or c.length < 0 or c.offset + c.length > 0xFFFFFFFF or len(s.bits) != (c.length + 7) // 8:
-                raise BlsError(f"committee set: {len(s.bits)} bitfield bytes for {c.length} members")
-            if not any(s.bits):  # intersectValues gives no index: PublicKey.aggregate throws
+            _check_committee(s.committee, s.bits)
+        else:
+            pks = _set_keys(s)
+            if s.type == SignatureSetType.aggregate and len(pks) == 0:
                 raise BlsError("EMPTY_AGGREGATE_ARRAY")
-            if len(s.signingRoot) != 32:
-                raise BlsError("signingRoot must be 32 bytes")
-            continue
-        pks = [s.pubkey] if s.type == SignatureSetType.single else s.pubkeys
-        if s.type == SignatureSetType.aggregate and len(pks) == 0:
-            raise BlsError("EMPTY_AGGREGATE_ARRAY")
-        for pk in pks:
-            if pk is None:
-                raise BlsError("EMPTY_AGGREGATE_ARRAY")
-            if pk.index is None and len(pk.raw) != 96:
-                _decompress_raw48(pk.raw)
-            if pk.index is not None and not (0 <= pk.index < 0x80000000):
-                raise BlsError(f"pubkey index {pk.index} out of range")
+            for pk in pks:
+                _check_key(pk)
         if len(s.signingRoot) != 32:
             raise BlsError("signingRoot must be 32 bytes")
 
@@ -425,12 +433,14 @@ def check_same_message(sets, message: bytes) -> None:
     if len(message) != 32:
         raise BlsError("signingRoot must be 32 bytes")
     for pk, _sig in sets:
-        if pk is None:
-            raise BlsError("EMPTY_AGGREGATE_ARRAY")
-        if pk.index is None and len(pk.raw) != 96:
-            _decompress_raw48(pk.raw)
-        if pk.index is not None and not (0 <= pk.index < 0x80000000):
-            raise BlsError(f"pubkey index {pk.index} out of range")
+        _check_key(pk)
+
+
+def _group_head(msgs: np.ndarray, g: int, message: bytes, sets) -> None:
+    """what the group encoders check of a group before its sets, and its row of msgs"""
+    if len(sets) == 0:
+        raise BlsError("Empty signature set", 10)
+    _put_root(msgs, g, message)
 
 
 def encode_same_message(groups, scalars: np.ndarray | None = None) -> dict:
@@ -438,48 +448,16 @@ def encode_same_message(groups, scalars: np.ndarray | None = None) -> dict:
     arrays of bgv_sm_batch (include/bgv.h): one message per group, one key and
     one signature per set.  An empty group is refused (the library would)."""
     n = sum(len(g[1]) for g in groups)
-    G = len(groups)
+    acc = _SetArrays(n)
+    msgs = np.zeros((max(len(groups), 1), 32), dtype=np.uint8)
     off = [0]
-    idx: list[int] = []
-    raw: list[bytes] = []
-    raw_pos: dict[bytes, int] = {}
-    msgs = np.zeros((max(G, 1), 32), dtype=np.uint8)
-    sigs = np.zeros((max(n, 1), 192), dtype=np.uint8)
-    sig_len = np.zeros(max(n, 1), dtype=np.uint32)
-    i = 0
     for g, (message, sets) in enumerate(groups):
-        if len(sets) == 0:
-            raise BlsError("Empty signature set", 10)
-        if len(message) != 32:
-            raise BlsError("signingRoot must be 32 bytes")
-        msgs[g] = np.frombuffer(bytes(message), dtype=np.uint8)
+        _group_head(msgs, g, message, sets)
         for pk, sig in sets:
-            if pk.index is not None:
-                idx.append(pk.index)
-            else:
-                r = pk.raw if len(pk.raw) == 96 else _decompress_raw48(pk.raw)
-                if r not in raw_pos:
-                    raw_pos[r] = len(raw)
-                    raw.append(r)
-                idx.append(0x80000000 | raw_pos[r])
-            sl = len(sig)
-            sig_len[i] = sl
-            if sl in (96, 192):
-                sigs[i, :sl] = np.frombuffer(bytes(sig), dtype=np.uint8)
-            i += 1
-        off.append(i)
-    return {
-        "n_sets": n,
-        "n_groups": G,
-        "group_offsets": np.array(off, dtype=np.uint32),
-        "pk_indices": np.array(idx if idx else [0], dtype=np.uint32),
-        "raw_pks": np.frombuffer(b"".join(raw), dtype=np.uint8).copy() if raw else None,
-        "n_raw": len(raw),
-        "msgs": msgs,
-        "sigs": sigs,
-        "sig_len": sig_len,
-        "scalars": scalars,
-    }
+            acc.keys((pk,))
+            acc.signature(sig)
+        off.append(acc.n)
+    return {"n_sets": n, "n_groups": len(groups), "group_offsets": np.array(off, dtype=np.uint32), **acc.finish(msgs, scalars)}
 
 
 @dataclass(frozen=True)
@@ -539,6 +517,10 @@ def merge_same_message(calls):
     return groups, where
 
 
+def _add(metrics: dict, key: str, value) -> None:
+    metrics[key] = metrics.get(key, 0) + value
+
+
 def record_sm_retry(device, metrics: dict) -> None:
     """the retry of the device's last same-message call (bgv_sm_retry_stats) into sm_retry_subs / _leaves / _pairs:
     the subs a split retry formed, the sets decided by a check of their own, and the Miller pairs of the retry"""
@@ -547,7 +529,21 @@ def record_sm_retry(device, metrics: dict) -> None:
         return
     path = stats()
     for k in ("subs", "leaves", "pairs"):
-        metrics["sm_retry_" + k] = metrics.get("sm_retry_" + k, 0) + int(path[k])
+        _add(metrics, "sm_retry_" + k, int(path[k]))
+
+
+def _record_sm_call(device, metrics: dict, prefix: str, n_sets: int) -> None:
+    """one same-message device call into <prefix>_sets_started, <prefix>_retries and the sm_retry_* counters; a
+    device stand-in without last_sm_stats or sm_retry_stats reports no retry"""
+    st = getattr(device, "last_sm_stats", None)
+    _add(metrics, prefix + "_sets_started", n_sets)
+    _add(metrics, prefix + "_retries", int(st.groups_retried) if st is not None else 0)
+    record_sm_retry(device, metrics)
+
+
+def _per_call(ok, where) -> list:
+    ok = [bool(x) for x in ok]
+    return [ok[w] for w in where]
 
 
 def run_same_message_calls(device, calls, scalars_for=None, metrics: dict | None = None) -> list:
@@ -560,12 +556,8 @@ def run_same_message_calls(device, calls, scalars_for=None, metrics: dict | None
     arrays = encode_same_message(groups, scalars_for(n) if scalars_for else None)
     ok, _codes = device.verify_same_message(arrays)
     if metrics is not None:
-        st = getattr(device, "last_sm_stats", None)
-        metrics["same_message_sets_started"] = metrics.get("same_message_sets_started", 0) + n
-        metrics["same_message_retries"] = metrics.get("same_message_retries", 0) + (int(st.groups_retried) if st is not None else 0)
-        record_sm_retry(device, metrics)
-    ok = [bool(x) for x in ok]
-    return [ok[w] for w in where]
+        _record_sm_call(device, metrics, "same_message", n)
+    return _per_call(ok, where)
 
 
 def check_aggregate_request(sets, agg: AggregateRequest) -> None:
@@ -574,6 +566,18 @@ def check_aggregate_request(sets, agg: AggregateRequest) -> None:
         raise BlsError("BLST_ERROR: BLST_INVALID_SIZE", 8)
     if agg.take is not None and len(agg.take) != len(sets):
         raise BlsError("take must have one entry per set")
+
+
+def _aggregate_request(sets, message: bytes, previous, take) -> tuple:
+    """What both verify_and_aggregate_same_message methods do first: (sets as a list, their AggregateRequest, the
+    call's result when there is no set to verify, else None), after the caller-side checks of the request and sets."""
+    sets = list(sets)
+    agg = AggregateRequest(None if previous is None else bytes(previous), None if take is None else tuple(bool(t) for t in take))
+    check_aggregate_request(sets, agg)
+    if not sets:  # no device call: nothing is added, `previous` comes back as it is
+        return sets, agg, SameMessageAggregate([], agg.previous or IDENTITY_SIG_96, 0)
+    check_same_message(sets, message)
+    return sets, agg, None
 
 
 def run_same_message_aggregate_calls(device, calls, scalars_for=None, metrics: dict | None = None) -> list:
@@ -609,11 +613,8 @@ def run_same_message_aggregate_calls(device, calls, scalars_for=None, metrics: d
         added += int(out["agg_count"][g])
         res.append(SameMessageAggregate(ok[where[k]], out["agg_sig"][g].tobytes(), int(out["agg_count"][g])))
     if metrics is not None:
-        st = getattr(device, "last_sm_stats", None)
-        metrics["same_message_sets_started"] = metrics.get("same_message_sets_started", 0) + n
-        metrics["same_message_retries"] = metrics.get("same_message_retries", 0) + (int(st.groups_retried) if st is not None else 0)
-        record_sm_retry(device, metrics)
-        metrics["same_message_aggregated_sigs"] = metrics.get("same_message_aggregated_sigs", 0) + added
+        _record_sm_call(device, metrics, "same_message", n)
+        _add(metrics, "same_message_aggregated_sigs", added)
     return res
 
 
@@ -736,26 +737,13 @@ def check_aggregate_same_message(sets, message: bytes) -> None:
     if len(message) != 32:
         raise BlsError("signingRoot must be 32 bytes")
     for pks, _sig in sets:
-        if isinstance(pks, CommitteeKeys):  # the checks of a committee set in check_sets
-            c = pks.committee
-            if c is None or pks.bits is None or not (0 <= c.list_id < native.MAX_INDEX_LISTS):
-                raise BlsError("committee set without a committee, bits or a valid list id")
-            if c.offset < 0 or c.length < 0 or c.offset + c.length > 0xFFFFFFFF or len(pks.bits) != (c.length + 7) // 8:
-                raise BlsError(f"committee set: {len(pks.bits)} bitfield bytes for {c.length} members")
-            if not any(pks.bits):
-                raise BlsError("EMPTY_AGGREGATE_ARRAY")
+        if isinstance(pks, CommitteeKeys):
+            _check_committee(pks.committee, pks.bits)
             continue
         if pks is None or len(pks) == 0:
             raise BlsError("EMPTY_AGGREGATE_ARRAY")
         for pk in pks:
-            if pk is None:
-                raise BlsError("EMPTY_AGGREGATE_ARRAY")
-            if not isinstance(pk, PublicKey):
-                pk = PublicKey(index=int(pk))
-            if pk.index is None and len(pk.raw) != 96:
-                _decompress_raw48(pk.raw)
-            if pk.index is not None and not (0 <= pk.index < 0x80000000):
-                raise BlsError(f"pubkey index {pk.index} out of range")
+            _check_key(pk if pk is None or isinstance(pk, PublicKey) else PublicKey(index=int(pk)))
 
 
 def encode_same_message_agg(groups, scalars: np.ndarray | None = None) -> dict:
@@ -764,54 +752,16 @@ def encode_same_message_agg(groups, scalars: np.ndarray | None = None) -> dict:
     and one signature per set.  `pubkeys` holds PublicKeys or validator indices,
     as encode_jobs takes them from an aggregate set."""
     n = sum(len(g[1]) for g in groups)
-    G = len(groups)
+    acc = _SetArrays(n, offsets=True)
+    msgs = np.zeros((max(len(groups), 1), 32), dtype=np.uint8)
     off = [0]
-    pk_off = [0]
-    idx: list[int] = []
-    raw: list[bytes] = []
-    raw_pos: dict[bytes, int] = {}
-    msgs = np.zeros((max(G, 1), 32), dtype=np.uint8)
-    sigs = np.zeros((max(n, 1), 192), dtype=np.uint8)
-    sig_len = np.zeros(max(n, 1), dtype=np.uint32)
-    i = 0
     for g, (message, sets) in enumerate(groups):
-        if len(sets) == 0:
-            raise BlsError("Empty signature set", 10)
-        if len(message) != 32:
-            raise BlsError("signingRoot must be 32 bytes")
-        msgs[g] = np.frombuffer(bytes(message), dtype=np.uint8)
+        _group_head(msgs, g, message, sets)
         for pks, sig in sets:
-            if len(pks) == 0:
-                raise BlsError("EMPTY_AGGREGATE_ARRAY")
-            for pk in _as_pubkeys(pks):
-                if pk.index is not None:
-                    idx.append(pk.index)
-                else:
-                    r = pk.raw if len(pk.raw) == 96 else _decompress_raw48(pk.raw)
-                    if r not in raw_pos:
-                        raw_pos[r] = len(raw)
-                        raw.append(r)
-                    idx.append(0x80000000 | raw_pos[r])
-            pk_off.append(len(idx))
-            sl = len(sig)
-            sig_len[i] = sl
-            if sl in (96, 192):
-                sigs[i, :sl] = np.frombuffer(bytes(sig), dtype=np.uint8)
-            i += 1
-        off.append(i)
-    return {
-        "n_sets": n,
-        "n_groups": G,
-        "group_offsets": np.array(off, dtype=np.uint32),
-        "pk_offsets": np.array(pk_off, dtype=np.uint32),
-        "pk_indices": np.array(idx if idx else [0], dtype=np.uint32),
-        "raw_pks": np.frombuffer(b"".join(raw), dtype=np.uint8).copy() if raw else None,
-        "n_raw": len(raw),
-        "msgs": msgs,
-        "sigs": sigs,
-        "sig_len": sig_len,
-        "scalars": scalars,
-    }
+            acc.keys(_as_pubkeys(pks))
+            acc.signature(sig)
+        off.append(acc.n)
+    return {"n_sets": n, "n_groups": len(groups), "group_offsets": np.array(off, dtype=np.uint32), **acc.finish(msgs, scalars)}
 
 
 def has_committee_keys(groups) -> bool:
@@ -824,65 +774,19 @@ def encode_same_message_bits(groups, scalars: np.ndarray | None = None) -> dict:
     over the packed bitfields) or a pubkey list as encode_same_message_agg takes
     it (a BGV_SRC_EXPLICIT run of pk_indices)."""
     n = sum(len(g[1]) for g in groups)
-    G = len(groups)
+    acc = _SetArrays(n, sources=True)
+    msgs = np.zeros((max(len(groups), 1), 32), dtype=np.uint8)
     off = [0]
-    idx: list[int] = []
-    raw: list[bytes] = []
-    raw_pos: dict[bytes, int] = {}
-    bits = bytearray()
-    src = np.zeros(max(n, 1), dtype=native.SET_SRC_DTYPE)
-    msgs = np.zeros((max(G, 1), 32), dtype=np.uint8)
-    sigs = np.zeros((max(n, 1), 192), dtype=np.uint8)
-    sig_len = np.zeros(max(n, 1), dtype=np.uint32)
-    i = 0
     for g, (message, sets) in enumerate(groups):
-        if len(sets) == 0:
-            raise BlsError("Empty signature set", 10)
-        if len(message) != 32:
-            raise BlsError("signingRoot must be 32 bytes")
-        msgs[g] = np.frombuffer(bytes(message), dtype=np.uint8)
+        _group_head(msgs, g, message, sets)
         for pks, sig in sets:
             if isinstance(pks, CommitteeKeys):
-                c = pks.committee
-                if len(pks.bits) != (c.length + 7) // 8:
-                    raise BlsError(f"committee set: {len(pks.bits)} bitfield bytes for {c.length} members")
-                src[i] = (c.list_id, c.offset, c.length, len(bits))
-                bits += pks.bits
+                acc.committee(pks.committee, pks.bits)
             else:
-                if len(pks) == 0:
-                    raise BlsError("EMPTY_AGGREGATE_ARRAY")
-                src[i] = (native.SRC_EXPLICIT, len(idx), len(pks), 0)
-                for pk in _as_pubkeys(pks):
-                    if pk.index is not None:
-                        idx.append(pk.index)
-                    else:
-                        r = pk.raw if len(pk.raw) == 96 else _decompress_raw48(pk.raw)
-                        if r not in raw_pos:
-                            raw_pos[r] = len(raw)
-                            raw.append(r)
-                        idx.append(0x80000000 | raw_pos[r])
-            sl = len(sig)
-            sig_len[i] = sl
-            if sl in (96, 192):
-                sigs[i, :sl] = np.frombuffer(bytes(sig), dtype=np.uint8)
-            i += 1
-        off.append(i)
-    return {
-        "n_sets": n,
-        "n_groups": G,
-        "group_offsets": np.array(off, dtype=np.uint32),
-        "src": src,
-        "bits": np.frombuffer(bytes(bits), dtype=np.uint8).copy() if bits else np.zeros(1, np.uint8),
-        "bits_len": len(bits),
-        "pk_indices": np.array(idx if idx else [0], dtype=np.uint32),
-        "n_indices": len(idx),
-        "raw_pks": np.frombuffer(b"".join(raw), dtype=np.uint8).copy() if raw else None,
-        "n_raw": len(raw),
-        "msgs": msgs,
-        "sigs": sigs,
-        "sig_len": sig_len,
-        "scalars": scalars,
-    }
+                acc.keys(_as_pubkeys(pks))
+            acc.signature(sig)
+        off.append(acc.n)
+    return {"n_sets": n, "n_groups": len(groups), "group_offsets": np.array(off, dtype=np.uint32), **acc.finish(msgs, scalars)}
 
 
 def run_same_message_agg_calls(device, calls, scalars_for=None, metrics: dict | None = None) -> list:
@@ -894,30 +798,15 @@ def run_same_message_agg_calls(device, calls, scalars_for=None, metrics: dict | 
     the path it took before (encode_same_message_agg, Device.verify_same_message_agg)."""
     groups, where = merge_same_message(calls)
     n = sum(len(g[1]) for g in groups)
-    if has_committee_keys(groups):
-        arrays = encode_same_message_bits(groups, scalars_for(n) if scalars_for else None)
-        ok, _codes = device.verify_same_message_bits(arrays)
-        if metrics is not None:
-            st = getattr(device, "last_sm_stats", None)
-            metrics["same_message_agg_sets_started"] = metrics.get("same_message_agg_sets_started", 0) + n
-            metrics["same_message_agg_retries"] = (metrics.get("same_message_agg_retries", 0)
-                                                   + (int(st.groups_retried) if st is not None else 0))
-            record_sm_retry(device, metrics)
-            metrics["aggregated_pubkeys_total"] = (metrics.get("aggregated_pubkeys_total", 0)
-                                                   + int(device.bits_path_stats()["keys_expanded"]))
-        ok = [bool(x) for x in ok]
-        return [ok[w] for w in where]
-    arrays = encode_same_message_agg(groups, scalars_for(n) if scalars_for else None)
-    ok, _codes = device.verify_same_message_agg(arrays)
+    bits = has_committee_keys(groups)
+    encode = encode_same_message_bits if bits else encode_same_message_agg
+    arrays = encode(groups, scalars_for(n) if scalars_for else None)
+    ok, _codes = (device.verify_same_message_bits if bits else device.verify_same_message_agg)(arrays)
     if metrics is not None:
-        st = getattr(device, "last_sm_stats", None)
-        metrics["same_message_agg_sets_started"] = metrics.get("same_message_agg_sets_started", 0) + n
-        metrics["same_message_agg_retries"] = (metrics.get("same_message_agg_retries", 0)
-                                               + (int(st.groups_retried) if st is not None else 0))
-        record_sm_retry(device, metrics)
-        metrics["aggregated_pubkeys_total"] = metrics.get("aggregated_pubkeys_total", 0) + int(arrays["pk_offsets"][-1])
-    ok = [bool(x) for x in ok]
-    return [ok[w] for w in where]
+        _record_sm_call(device, metrics, "same_message_agg", n)
+        _add(metrics, "aggregated_pubkeys_total",
+             int(device.bits_path_stats()["keys_expanded"]) if bits else int(arrays["pk_offsets"][-1]))
+    return _per_call(ok, where)
 
 
 # ----------------------------------------------------------------- verifier
@@ -1071,12 +960,9 @@ class BlsGpuVerifier:
         (bgv_verify_same_message_aggregate).  A `previous` that does not decode
         rejects this call alone with BLST_ERROR: BLST_<NAME>."""
         opts = opts or VerifySignatureOpts()
-        sets = list(sets)
-        agg = AggregateRequest(None if previous is None else bytes(previous), None if take is None else tuple(bool(t) for t in take))
-        check_aggregate_request(sets, agg)
-        if not sets:  # no device call: nothing is added, `previous` comes back as it is
-            return SameMessageAggregate([], agg.previous or IDENTITY_SIG_96, 0)
-        check_same_message(sets, message)
+        sets, agg, nothing = _aggregate_request(sets, message, previous, take)
+        if nothing is not None:
+            return nothing
         if self._closed:
             raise QueueError(QueueErrorCode.QUEUE_ABORTED)
         return await self._sm.submit(sets, message, opts.batchable, agg)
@@ -1262,12 +1148,12 @@ class BlsGpuVerifier:
         context with pair_merge met repeated roots inside a job."""
         for h in hs:
             if h:
-                self.metrics["hash_to_g2_sets"] = self.metrics.get("hash_to_g2_sets", 0) + int(h["sets"])
-                self.metrics["hash_to_g2_evaluated"] = self.metrics.get("hash_to_g2_evaluated", 0) + int(h["hashes"])
+                _add(self.metrics, "hash_to_g2_sets", int(h["sets"]))
+                _add(self.metrics, "hash_to_g2_evaluated", int(h["hashes"]))
                 pp = h.get("pair")
                 if pp:
-                    self.metrics["miller_pairs_sets"] = self.metrics.get("miller_pairs_sets", 0) + int(pp["sets"])
-                    self.metrics["miller_pairs_evaluated"] = self.metrics.get("miller_pairs_evaluated", 0) + int(pp["pairs"])
+                    _add(self.metrics, "miller_pairs_sets", int(pp["sets"]))
+                    _add(self.metrics, "miller_pairs_evaluated", int(pp["pairs"]))
 
     @staticmethod
     def _hash_stats(dev) -> dict | None:
@@ -1330,26 +1216,22 @@ class BlsGpuVerifier:
             self.metrics["main_thread_calls"] += 1
         return self._verdict(int(jr[0]))
 
-    def _run_same_message(self, calls) -> list:
-        """the merged same-message calls on one bulk context (no sharding)"""
+    def _run_on_bulk_context(self, runner, calls) -> list:
+        """runner (run_same_message_calls or run_same_message_agg_calls) for the merged calls on the first idle
+        bulk context, or on the first one when none is idle (no sharding)"""
         idle = [k for k, f in enumerate(self._idle) if f]
         d = idle[0] if idle else 0
         with self._dev_locks[d]:
             t0 = time.perf_counter()
-            out = run_same_message_calls(self.devices[d], calls, self._scalars if self._rng is not None else None, self.metrics)
-            self.metrics["device_time_s"] = self.metrics.get("device_time_s", 0.0) + time.perf_counter() - t0
+            out = runner(self.devices[d], calls, self._scalars if self._rng is not None else None, self.metrics)
+            _add(self.metrics, "device_time_s", time.perf_counter() - t0)
         return out
 
+    def _run_same_message(self, calls) -> list:
+        return self._run_on_bulk_context(run_same_message_calls, calls)
+
     def _run_same_message_agg(self, calls) -> list:
-        """the merged same-message calls of aggregate sets on one bulk context"""
-        idle = [k for k, f in enumerate(self._idle) if f]
-        d = idle[0] if idle else 0
-        with self._dev_locks[d]:
-            t0 = time.perf_counter()
-            out = run_same_message_agg_calls(self.devices[d], calls, self._scalars if self._rng is not None else None,
-                                             self.metrics)
-            self.metrics["device_time_s"] = self.metrics.get("device_time_s", 0.0) + time.perf_counter() - t0
-        return out
+        return self._run_on_bulk_context(run_same_message_agg_calls, calls)
 
     def _run_device_batch(self, jobs: list[list[ISignatureSet]], devs: list[int] | None = None) -> list:
         """Verify a list of jobs on the devices `devs` (default: all); returns
@@ -1505,12 +1387,9 @@ class BlsGpuSingleThreadVerifier:
     async def verify_and_aggregate_same_message(self, sets, message: bytes, opts: VerifySignatureOpts | None = None,
                                                 previous: bytes | None = None, take=None) -> SameMessageAggregate:
         """verify_and_aggregate_same_message in the calling thread: one device call, one group"""
-        sets = list(sets)
-        agg = AggregateRequest(None if previous is None else bytes(previous), None if take is None else tuple(bool(t) for t in take))
-        check_aggregate_request(sets, agg)
-        if not sets:  # no device call: nothing is added, `previous` comes back as it is
-            return SameMessageAggregate([], agg.previous or IDENTITY_SIG_96, 0)
-        check_same_message(sets, message)
+        sets, agg, nothing = _aggregate_request(sets, message, previous, take)
+        if nothing is not None:
+            return nothing
         r = run_same_message_calls(self.device, [(sets, message, agg)], None, self.metrics)[0]
         if isinstance(r, Exception):
             raise r

@@ -126,6 +126,28 @@ static addon_ctx* get_ctx(napi_env env, napi_value v) {
   return c;
 }
 
+/* the prologue of every (ctx, ...) entry: up to *argc arguments into a[], and the open context of a[0] */
+static addon_ctx* ctx_args(napi_env env, napi_callback_info info, size_t* argc, napi_value* a) {
+  if (napi_get_cb_info(env, info, argc, a, NULL, NULL) != napi_ok) {
+    napi_throw_error(env, NULL, "bgv addon: N-API call failed: napi_get_cb_info(env, info, &argc, a, NULL, NULL)");
+    return NULL;
+  }
+  return get_ctx(env, a[0]);
+}
+#define CTX_ARGS(n)                                  \
+  size_t argc = (n);                                 \
+  napi_value a[n];                                   \
+  addon_ctx* c = ctx_args(env, info, &argc, a);      \
+  if (!c) return NULL
+
+/* one library call under the context's mutex (it waits for the context's batch in flight) */
+#define LOCKED(c, st, call)           \
+  do {                                \
+    pthread_mutex_lock(&(c)->mu);     \
+    (st) = (call);                    \
+    pthread_mutex_unlock(&(c)->mu);   \
+  } while (0)
+
 /* typed-array view: data pointer and element count; -1 on type error */
 static int typed(napi_env env, napi_value v, napi_typedarray_type want, void** data, size_t* len) {
   bool is = false;
@@ -135,6 +157,39 @@ static int typed(napi_env env, napi_value v, napi_typedarray_type want, void** d
   size_t off;
   if (napi_get_typedarray_info(env, v, &t, len, data, &ab, &off) != napi_ok || t != want) return -1;
   return 0;
+}
+
+/* a typed array of n elements of `elem` bytes over a copy of src */
+static napi_value new_typed_array(napi_env env, napi_typedarray_type t, size_t elem, const void* src, size_t n) {
+  void* dst = NULL;
+  napi_value ab, arr;
+  NAPI_CALL(env, napi_create_arraybuffer(env, elem * n, &dst, &ab));
+  if (n) memcpy(dst, src, elem * n);
+  NAPI_CALL(env, napi_create_typedarray(env, t, n, ab, 0, &arr));
+  return arr;
+}
+
+/* sets o's named uint32 properties (o == NULL: on a new object); NULL after a throw */
+typedef struct {
+  const char* name;
+  uint32_t val;
+} named_u32;
+
+static napi_value set_u32s(napi_env env, napi_value o, const named_u32* u, size_t n) {
+  napi_value v;
+  if (!o) NAPI_CALL(env, napi_create_object(env, &o));
+  for (size_t k = 0; k < n; k++) {
+    NAPI_CALL(env, napi_create_uint32(env, u[k].val, &v));
+    NAPI_CALL(env, napi_set_named_property(env, o, u[k].name, v));
+  }
+  return o;
+}
+#define SET_U32S(env, o, ...) set_u32s(env, o, (const named_u32[]){__VA_ARGS__}, sizeof((const named_u32[]){__VA_ARGS__}) / sizeof(named_u32))
+
+static void set_double(napi_env env, napi_value o, const char* name, double x) {
+  napi_value v;
+  napi_create_double(env, x, &v);
+  napi_set_named_property(env, o, name, v);
 }
 
 /* ------------------------------------------------------------------ sync */
@@ -203,11 +258,16 @@ static napi_value Open(napi_env env, napi_callback_info info) {
       return NULL;
     }
   }
-  bgv_ctx* ctx = NULL;
-  const int st = bgv_open_cfg(dev, &cfg, &ctx);
-  if (st != BGV_OK) return throw_bgv(env, st);
   addon_ctx* c = (addon_ctx*)calloc(1, sizeof *c);
-  c->ctx = ctx;
+  if (!c) {
+    napi_throw_error(env, NULL, "out of memory");
+    return NULL;
+  }
+  const int st = bgv_open_cfg(dev, &cfg, &c->ctx);
+  if (st != BGV_OK) {
+    free(c);
+    return throw_bgv(env, st);
+  }
   pthread_mutex_init(&c->mu, NULL);
   napi_value r;
   NAPI_CALL(env, napi_create_external(env, c, ctx_finalize, NULL, &r));
@@ -215,11 +275,7 @@ static napi_value Open(napi_env env, napi_callback_info info) {
 }
 
 static napi_value Close(napi_env env, napi_callback_info info) {
-  size_t argc = 1;
-  napi_value a[1];
-  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, a, NULL, NULL));
-  addon_ctx* c = get_ctx(env, a[0]);
-  if (!c) return NULL;
+  CTX_ARGS(1);
   pthread_mutex_lock(&c->mu);  /* waits for in-flight work */
   c->closed = 1;
   bgv_close(c->ctx);
@@ -228,11 +284,7 @@ static napi_value Close(napi_env env, napi_callback_info info) {
 }
 
 static napi_value PubkeysSet(napi_env env, napi_callback_info info) {
-  size_t argc = 4;
-  napi_value a[4];
-  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, a, NULL, NULL));
-  addon_ctx* c = get_ctx(env, a[0]);
-  if (!c) return NULL;
+  CTX_ARGS(4);
   uint32_t first = 0, fmt = 0;
   NAPI_CALL(env, napi_get_value_uint32(env, a[1], &first));
   NAPI_CALL(env, napi_get_value_uint32(env, a[3], &fmt));
@@ -243,44 +295,25 @@ static napi_value PubkeysSet(napi_env env, napi_callback_info info) {
     return NULL;
   }
   const size_t w = fmt == BGV_PK_UNCOMPRESSED_96 ? 96 : 48;
-  pthread_mutex_lock(&c->mu);
-  const int st = bgv_pubkeys_set(c->ctx, first, (uint32_t)(len / w), (const uint8_t*)data, fmt);
-  pthread_mutex_unlock(&c->mu);
+  int st;
+  LOCKED(c, st, bgv_pubkeys_set(c->ctx, first, (uint32_t)(len / w), (const uint8_t*)data, fmt));
   if (st != BGV_OK) return throw_bgv(env, st);
   return NULL;
 }
 
 static napi_value PubkeysCount(napi_env env, napi_callback_info info) {
-  size_t argc = 1;
-  napi_value a[1];
-  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, a, NULL, NULL));
-  addon_ctx* c = get_ctx(env, a[0]);
-  if (!c) return NULL;
+  CTX_ARGS(1);
   uint32_t n = 0;
-  pthread_mutex_lock(&c->mu);
-  const int st = bgv_pubkeys_count(c->ctx, &n);
-  pthread_mutex_unlock(&c->mu);
+  int st;
+  LOCKED(c, st, bgv_pubkeys_count(c->ctx, &n));
   if (st != BGV_OK) return throw_bgv(env, st);
   napi_value r;
   NAPI_CALL(env, napi_create_uint32(env, n, &r));
   return r;
 }
 
-static napi_value new_int32_array(napi_env env, const int32_t* src, size_t n) {
-  void* dst = NULL;
-  napi_value ab, arr;
-  NAPI_CALL(env, napi_create_arraybuffer(env, 4 * n, &dst, &ab));
-  if (n) memcpy(dst, src, 4 * n);
-  NAPI_CALL(env, napi_create_typedarray(env, napi_int32_array, n, ab, 0, &arr));
-  return arr;
-}
-
 static napi_value PubkeysValidate(napi_env env, napi_callback_info info) {
-  size_t argc = 2;
-  napi_value a[2];
-  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, a, NULL, NULL));
-  addon_ctx* c = get_ctx(env, a[0]);
-  if (!c) return NULL;
+  CTX_ARGS(2);
   void* data;
   size_t len;
   if (typed(env, a[1], napi_uint8_array, &data, &len)) {
@@ -289,328 +322,231 @@ static napi_value PubkeysValidate(napi_env env, napi_callback_info info) {
   }
   const uint32_t n = (uint32_t)(len / 48);
   int32_t* codes = (int32_t*)calloc(n ? n : 1, 4);
-  pthread_mutex_lock(&c->mu);
-  const int st = bgv_pubkeys_validate(c->ctx, (const uint8_t*)data, n, codes);
-  pthread_mutex_unlock(&c->mu);
-  if (st != BGV_OK) {
-    free(codes);
-    return throw_bgv(env, st);
+  if (!codes) {
+    napi_throw_error(env, NULL, "out of memory");
+    return NULL;
   }
-  napi_value r = new_int32_array(env, codes, n);
+  int st;
+  LOCKED(c, st, bgv_pubkeys_validate(c->ctx, (const uint8_t*)data, n, codes));
+  napi_value r = st == BGV_OK ? new_typed_array(env, napi_int32_array, 4, codes, n) : throw_bgv(env, st);
   free(codes);
   return r;
 }
 
-/* ----------------------------------------------------------------- verify */
-enum { F_JOB, F_PKO, F_PKI, F_MSG, F_SIG, F_LEN, F_RAW, N_FIELDS };
-static const char* FIELD[N_FIELDS] = {"jobOffsets", "pkOffsets", "pkIndices", "msgs", "sigs", "sigLen", "rawPks"};
-static const napi_typedarray_type FIELD_T[N_FIELDS] = {napi_uint32_array, napi_uint32_array, napi_uint32_array,
-                                                       napi_uint8_array,  napi_uint8_array,  napi_uint32_array,
-                                                       napi_uint8_array};
+/* ------------------------------------------------------------ batch fields
+ * Every typed array a batch object can carry, whichever entry reads it: its name, its element type, whether a
+ * batch may leave it out (FIELD_OPTIONAL: absent; FIELD_NULLABLE: absent, null or undefined), and whether it is
+ * copied when the call is made (the offsets and the sources: every length is checked against the copy) or pinned
+ * by a reference until the work completes.  An entry kind names its fields by a list of these rows. */
+enum { F_JOB, F_GRP, F_PKO, F_SRC, F_BITS, F_PKI, F_MSG, F_SIG, F_LEN, F_RAW, F_TAKE, F_PREV, N_FIELDS, F_END = N_FIELDS };
+enum { FIELD_REQUIRED, FIELD_OPTIONAL, FIELD_NULLABLE };
+static const struct {
+  const char* name;
+  napi_typedarray_type type;
+  size_t elem;
+  int need;
+  int copied;
+} FIELD[N_FIELDS] = {
+    [F_JOB] = {"jobOffsets", napi_uint32_array, 4, FIELD_REQUIRED, 1},
+    [F_GRP] = {"groupOffsets", napi_uint32_array, 4, FIELD_REQUIRED, 1},
+    [F_PKO] = {"pkOffsets", napi_uint32_array, 4, FIELD_REQUIRED, 1},
+    [F_SRC] = {"src", napi_uint32_array, 4, FIELD_REQUIRED, 1},
+    [F_BITS] = {"bits", napi_uint8_array, 1, FIELD_REQUIRED, 0},
+    [F_PKI] = {"pkIndices", napi_uint32_array, 4, FIELD_REQUIRED, 0},
+    [F_MSG] = {"msgs", napi_uint8_array, 1, FIELD_REQUIRED, 0},
+    [F_SIG] = {"sigs", napi_uint8_array, 1, FIELD_REQUIRED, 0},
+    [F_LEN] = {"sigLen", napi_uint32_array, 4, FIELD_REQUIRED, 0},
+    [F_RAW] = {"rawPks", napi_uint8_array, 1, FIELD_OPTIONAL, 0},
+    [F_TAKE] = {"take", napi_uint8_array, 1, FIELD_NULLABLE, 0},
+    [F_PREV] = {"prevSigs", napi_uint8_array, 1, FIELD_NULLABLE, 0},
+};
+static const uint8_t VERIFY_FIELDS[] = {F_JOB, F_PKO, F_PKI, F_MSG, F_SIG, F_LEN, F_RAW, F_END};
+static const uint8_t BITS_FIELDS[] = {F_JOB, F_SRC, F_BITS, F_PKI, F_MSG, F_SIG, F_LEN, F_RAW, F_END};
+static const uint8_t SM_FIELDS[] = {F_GRP, F_PKI, F_MSG, F_SIG, F_LEN, F_RAW, F_END};
+static const uint8_t SMA_FIELDS[] = {F_GRP, F_PKI, F_MSG, F_SIG, F_LEN, F_RAW, F_PKO, F_END};
+static const uint8_t SMB_FIELDS[] = {F_GRP, F_PKI, F_MSG, F_SIG, F_LEN, F_RAW, F_SRC, F_BITS, F_END};
+static const uint8_t TAKE_FIELD[] = {F_TAKE, F_END}, PREV_FIELD[] = {F_PREV, F_END};
 
-enum { K_VERIFY, K_PARTIAL, K_FINISH, K_COMBINE, K_BITS };
-/* bgv_bits_batch fields (K_BITS) */
-enum { B_JOB, B_SRC, B_BITS, B_PKI, B_MSG, B_SIG, B_LEN, B_RAW, NB_FIELDS };
+/* ------------------------------------------------------------------- jobs
+ * One job struct for every entry that runs a device call, on the libuv pool or on the calling thread. */
+typedef enum {
+  K_VERIFY,
+  K_PARTIAL,
+  K_BITS,
+  K_FINISH,       /* partialFinish: no batch, results sized on the worker from the pending partial */
+  K_COMBINE,      /* combineFinal: a copy of the partials, a boolean */
+  K_SM,           /* verifySameMessage */
+  K_SM_AGGREGATE, /* verifySameMessageAggregate: K_SM plus take / prevSigs and the groups' aggregates */
+  K_SMA,          /* verifySameMessageAgg */
+  K_SMB,          /* verifySameMessageBits */
+  N_KINDS
+} job_kind;
+enum { O_JOBS, O_VALID, O_CODES, O_AGG_SIGS, O_AGG_COUNT, O_AGG_CODE, O_PARTS, N_OWNED };
 
 typedef struct {
-  int kind;
   addon_ctx* c;
-  bgv_batch b;
-  bgv_bits_batch bb;    /* K_BITS (b.n_jobs / b.n_sets mirror its counts) */
-  uint32_t* src_copy;   /* K_BITS: the sources, copied at call time like the offsets */
-  napi_ref brefs[NB_FIELDS];
-  uint8_t miller[576];  /* K_PARTIAL */
-  int32_t ok;           /* K_PARTIAL: no job rejected; K_COMBINE: the product is 1 in GT */
-  uint8_t* parts;       /* K_COMBINE: a copy of the partials */
-  uint32_t n_parts;
-  uint32_t* job_off; /* copies made at call time (the library reads these) */
-  uint32_t* pk_off;
-  int32_t* job_result;
+  job_kind kind;
+  void* ptr[N_FIELDS];    /* the batch's arrays: the copy of a copied field, else the caller's memory */
+  size_t len[N_FIELDS];   /* element counts */
+  void* copy[N_FIELDS];   /* copies made at call time (the library reads these) */
+  napi_ref refs[N_FIELDS]; /* async: the pinned arrays */
+  void* own[N_OWNED];     /* outputs (and K_COMBINE's copy of the partials), freed with the job */
+  uint32_t n_jobs, n_sets, n_groups, n_parts;
+  union {
+    bgv_batch b;
+    bgv_bits_batch bits;
+    bgv_sm_batch sm;
+    bgv_sma_batch sma;
+    bgv_smb_batch smb;
+  } u;
+  bgv_sm_agg ag;          /* K_SM_AGGREGATE */
+  uint8_t miller[576];    /* K_PARTIAL */
+  int32_t ok;             /* K_PARTIAL: no job rejected; K_COMBINE: the product is 1 in GT */
   bgv_stats stats;
+  bgv_sm_stats sm_stats;
   bgv_hash_path hash_path; /* K_VERIFY, K_BITS, K_PARTIAL: read under the context's lock */
   bgv_pair_path pair_path; /* likewise */
+  bgv_bits_path bits_path; /* K_SMB: likewise */
   double t_start_ms, t_end_ms;
   int status;
   char err[512];
-  napi_ref refs[N_FIELDS];
   napi_ref ctx_ref;
   napi_async_work work;
   napi_deferred deferred;
-} verify_job;
+} job;
 
-static void free_job_arrays(verify_job* j) {
-  free(j->job_off);
-  free(j->pk_off);
-  free(j->job_result);
-  free(j->parts);
-  free(j->src_copy);
-  j->src_copy = NULL;
-  j->job_off = j->pk_off = NULL;
-  j->job_result = NULL;
-  j->parts = NULL;
+static int oom(napi_env env) {
+  napi_throw_error(env, NULL, "out of memory");
+  return -1;
 }
 
-/* reads the batch object into j->b; copies the offsets; pins the other arrays when pin != 0 */
-static int read_batch(napi_env env, napi_value obj, verify_job* j, int pin) {
-  void* p[N_FIELDS] = {0};
-  size_t n[N_FIELDS] = {0};
-  napi_value v[N_FIELDS];
+static void job_free(napi_env env, job* j) {
   for (int k = 0; k < N_FIELDS; k++) {
+    if (j->refs[k]) napi_delete_reference(env, j->refs[k]); /* unpin the inputs */
+    free(j->copy[k]);
+  }
+  for (int k = 0; k < N_OWNED; k++) free(j->own[k]);
+  if (j->ctx_ref) napi_delete_reference(env, j->ctx_ref);
+}
+
+/* zeroed output of n elements (at least one); -1 after throwing */
+static int job_alloc(napi_env env, job* j, int slot, size_t n, size_t elem) {
+  j->own[slot] = calloc(n ? n : 1, elem);
+  return j->own[slot] ? 0 : oom(env);
+}
+
+/* the two refusals of a reader's own wording: a required field left out, a field of another type */
+typedef struct {
+  const char* missing;
+  const char* wrong_type;
+} field_refusals;
+static const field_refusals BATCH_REFUSALS = {"batch field missing", "batch field has the wrong typed-array type"};
+static const field_refusals BITS_REFUSALS = {"bits batch field missing", "bits batch field has the wrong typed-array type"};
+static const field_refusals SUMS_REFUSALS = {NULL /* both rows are nullable */, "take / prevSigs must be a Uint8Array"};
+
+/* THE reader: the listed fields of obj into j->ptr / j->len.  A field is looked up, type-checked, then copied or
+ * (pin != 0) pinned; `say` words the refusals.  -1 after throwing. */
+static int read_fields(napi_env env, napi_value obj, job* j, const uint8_t* fields, const field_refusals* say, int pin) {
+  for (; *fields != F_END; fields++) {
+    const int k = *fields;
     bool has = false;
-    napi_has_named_property(env, obj, FIELD[k], &has);
+    napi_value v;
+    napi_has_named_property(env, obj, FIELD[k].name, &has);
     if (!has) {
-      if (k == F_RAW) continue;
-      napi_throw_type_error(env, NULL, "batch field missing");
+      if (FIELD[k].need != FIELD_REQUIRED) continue;
+      napi_throw_type_error(env, NULL, say->missing);
       return -1;
     }
-    napi_get_named_property(env, obj, FIELD[k], &v[k]);
-    if (typed(env, v[k], FIELD_T[k], &p[k], &n[k])) {
-      napi_throw_type_error(env, NULL, "batch field has the wrong typed-array type");
+    napi_get_named_property(env, obj, FIELD[k].name, &v);
+    if (FIELD[k].need == FIELD_NULLABLE) {
+      napi_valuetype vt;
+      napi_typeof(env, v, &vt);
+      if (vt == napi_undefined || vt == napi_null) continue;
+    }
+    if (typed(env, v, FIELD[k].type, &j->ptr[k], &j->len[k])) {
+      napi_throw_type_error(env, NULL, say->wrong_type);
+      j->ptr[k] = NULL;
+      j->len[k] = 0;
       return -1;
     }
+    if (FIELD[k].copied) {
+      const size_t bytes = FIELD[k].elem * j->len[k];
+      j->copy[k] = malloc(bytes ? bytes : 1);
+      if (!j->copy[k]) return oom(env);
+      if (bytes) memcpy(j->copy[k], j->ptr[k], bytes);
+      j->ptr[k] = j->copy[k];
+    } else if (pin) {
+      napi_create_reference(env, v, 1, &j->refs[k]);
+    }
   }
-  if (n[F_JOB] < 1 || n[F_PKO] < 1) {
-    napi_throw_range_error(env, NULL, "jobOffsets / pkOffsets need at least one entry");
-    return -1;
-  }
-  memset(&j->b, 0, sizeof j->b);
-  j->b.n_jobs = (uint32_t)(n[F_JOB] - 1);
-  j->b.n_sets = (uint32_t)(n[F_PKO] - 1);
-  j->job_off = (uint32_t*)malloc(4 * n[F_JOB]);
-  j->pk_off = (uint32_t*)malloc(4 * n[F_PKO]);
-  if (!j->job_off || !j->pk_off) {
-    napi_throw_error(env, NULL, "out of memory");
-    return -1;
-  }
-  memcpy(j->job_off, p[F_JOB], 4 * n[F_JOB]);
-  memcpy(j->pk_off, p[F_PKO], 4 * n[F_PKO]);
-  const uint32_t n_sets = j->b.n_sets;
-  if (n[F_MSG] < 32ull * n_sets || n[F_SIG] < 192ull * n_sets || n[F_LEN] < n_sets) {
-    napi_throw_range_error(env, NULL, "msgs / sigs / sigLen shorter than the set count");
-    return -1;
-  }
-  if (n[F_PKI] < (size_t)j->pk_off[n_sets]) {
-    napi_throw_range_error(env, NULL, "pkIndices shorter than pkOffsets[n_sets]");
-    return -1;
-  }
-  if (pin)
-    for (int k = 0; k < N_FIELDS; k++)
-      if (p[k] && k != F_JOB && k != F_PKO) napi_create_reference(env, v[k], 1, &j->refs[k]);
-  j->b.job_offsets = j->job_off;
-  j->b.pk_offsets = j->pk_off;
-  j->b.pk_indices = (const uint32_t*)p[F_PKI];
-  j->b.msgs = (const uint8_t*)p[F_MSG];
-  j->b.sigs = (const uint8_t*)p[F_SIG];
-  j->b.sig_len = (const uint32_t*)p[F_LEN];
-  j->b.raw_pks = (const uint8_t*)p[F_RAW];
-  j->b.n_raw = (uint32_t)(n[F_RAW] / 96);
-  j->b.scalars = NULL; /* drawn inside the library (device ChaCha20 keyed by getrandom) */
-  j->b.on_device = 0;
   return 0;
 }
 
-static double now_ms(void) {
-  struct timespec t;
-  clock_gettime(CLOCK_MONOTONIC, &t);
-  return (double)t.tv_sec * 1e3 + (double)t.tv_nsec * 1e-6;
+static int refuse_range(napi_env env, const char* msg) {
+  napi_throw_range_error(env, NULL, msg);
+  return -1;
 }
 
-static void run_verify(verify_job* j) {
-  pthread_mutex_lock(&j->c->mu);
-  j->t_start_ms = now_ms();
-  if (j->c->closed) {
-    j->status = BGV_E_INVALID_ARG;
-    snprintf(j->err, sizeof j->err, "QUEUE_ERROR_QUEUE_ABORTED");
-  } else {
-    switch (j->kind) {
-      case K_PARTIAL:
-        j->status = bgv_partial(j->c->ctx, &j->b, j->miller, NULL, j->job_result, &j->ok);
-        j->c->partial_jobs = j->b.n_jobs;
-        if (j->status == BGV_OK) {
-          j->status = bgv_last_stats(j->c->ctx, &j->stats);
-          j->stats.pubkeys_aggregated = j->b.n_sets ? j->pk_off[j->b.n_sets] : 0;
-        }
-        break;
-      case K_FINISH:
-        j->b.n_jobs = j->c->partial_jobs;
-        j->job_result = (int32_t*)calloc(j->b.n_jobs ? j->b.n_jobs : 1, 4);
-        j->status = j->job_result ? bgv_partial_finish(j->c->ctx, j->job_result, &j->stats) : BGV_E_INVALID_ARG;
-        break;
-      case K_COMBINE: j->status = bgv_combine_final(j->c->ctx, j->parts, j->n_parts, &j->ok); break;
-      case K_BITS: j->status = bgv_verify_bits(j->c->ctx, &j->bb, j->job_result, NULL, &j->stats); break;
-      default: j->status = bgv_verify(j->c->ctx, &j->b, j->job_result, NULL, &j->stats); break;
-    }
-    /* under the same lock: this call's evaluations, not a later call's */
-    if (j->status == BGV_OK && (j->kind == K_VERIFY || j->kind == K_BITS || j->kind == K_PARTIAL))
-      j->status = bgv_hash_stats(j->c->ctx, &j->hash_path);
-    if (j->status == BGV_OK && (j->kind == K_VERIFY || j->kind == K_BITS || j->kind == K_PARTIAL))
-      j->status = bgv_pair_stats(j->c->ctx, &j->pair_path);
-    if (j->status != BGV_OK) snprintf(j->err, sizeof j->err, "bgv error %d: %s", j->status, bgv_last_error());
-  }
-  j->t_end_ms = now_ms();
-  pthread_mutex_unlock(&j->c->mu);
+/* what every bgv_*_batch holds per set, and what the two bitfield batches add; scalars stay NULL (drawn inside the
+ * library: device ChaCha20 keyed by getrandom) and on_device 0 */
+#define FILL_SETS(b, j)                                   \
+  do {                                                    \
+    (b).n_sets = (j)->n_sets;                             \
+    (b).pk_indices = (const uint32_t*)(j)->ptr[F_PKI];    \
+    (b).raw_pks = (const uint8_t*)(j)->ptr[F_RAW];        \
+    (b).n_raw = (uint32_t)((j)->len[F_RAW] / 96);         \
+    (b).msgs = (const uint8_t*)(j)->ptr[F_MSG];           \
+    (b).sigs = (const uint8_t*)(j)->ptr[F_SIG];           \
+    (b).sig_len = (const uint32_t*)(j)->ptr[F_LEN];       \
+  } while (0)
+#define FILL_SOURCES(b, j)                                \
+  do {                                                    \
+    FILL_SETS(b, j);                                      \
+    (b).src = (const bgv_set_src*)(j)->ptr[F_SRC];        \
+    (b).bits = (const uint8_t*)(j)->ptr[F_BITS];          \
+    (b).bits_len = (uint32_t)(j)->len[F_BITS];            \
+    (b).n_indices = (uint32_t)(j)->len[F_PKI];            \
+  } while (0)
+
+/* K_VERIFY, K_PARTIAL: batch = {jobOffsets, pkOffsets, pkIndices, msgs, sigs, sigLen, rawPks?} */
+static int read_verify(napi_env env, napi_value obj, job* j, int pin) {
+  const size_t* n = j->len;
+  if (read_fields(env, obj, j, VERIFY_FIELDS, &BATCH_REFUSALS, pin)) return -1;
+  if (n[F_JOB] < 1 || n[F_PKO] < 1) return refuse_range(env, "jobOffsets / pkOffsets need at least one entry");
+  j->n_jobs = (uint32_t)(n[F_JOB] - 1);
+  j->n_sets = (uint32_t)(n[F_PKO] - 1);
+  if (n[F_MSG] < 32ull * j->n_sets || n[F_SIG] < 192ull * j->n_sets || n[F_LEN] < j->n_sets)
+    return refuse_range(env, "msgs / sigs / sigLen shorter than the set count");
+  if (n[F_PKI] < (size_t)((const uint32_t*)j->ptr[F_PKO])[j->n_sets]) return refuse_range(env, "pkIndices shorter than pkOffsets[n_sets]");
+  FILL_SETS(j->u.b, j);
+  j->u.b.n_jobs = j->n_jobs;
+  j->u.b.job_offsets = (const uint32_t*)j->ptr[F_JOB];
+  j->u.b.pk_offsets = (const uint32_t*)j->ptr[F_PKO];
+  return job_alloc(env, j, O_JOBS, j->n_jobs, 4);
 }
 
-/* {results, batchRetries, batchSigsSuccess, pubkeysAggregated, deviceMs, workerStartMs, workerEndMs} */
-static napi_value result_object(napi_env env, const verify_job* j) {
-  napi_value o, v;
-  if (napi_create_object(env, &o) != napi_ok) return NULL;
-  v = new_int32_array(env, j->job_result, j->b.n_jobs);
-  if (!v) return NULL;
-  napi_set_named_property(env, o, "results", v);
-  napi_create_uint32(env, j->stats.batch_retries, &v);
-  napi_set_named_property(env, o, "batchRetries", v);
-  napi_create_uint32(env, j->stats.batch_sigs_success, &v);
-  napi_set_named_property(env, o, "batchSigsSuccess", v);
-  napi_create_double(env, (double)j->stats.pubkeys_aggregated, &v);
-  napi_set_named_property(env, o, "pubkeysAggregated", v);
-  napi_create_double(env, (double)j->stats.total_ms, &v);
-  napi_set_named_property(env, o, "deviceMs", v);
-  napi_create_double(env, j->t_start_ms, &v);
-  napi_set_named_property(env, o, "workerStartMs", v);
-  napi_create_double(env, j->t_end_ms, &v);
-  napi_set_named_property(env, o, "workerEndMs", v);
-  if (j->kind == K_VERIFY || j->kind == K_BITS || j->kind == K_PARTIAL) {
-    napi_create_uint32(env, j->hash_path.hashes, &v);
-    napi_set_named_property(env, o, "hashes", v);
-    napi_create_uint32(env, j->pair_path.pairs, &v);
-    napi_set_named_property(env, o, "millerPairs", v);
-  }
-  if (j->kind == K_PARTIAL) {
-    void* dst = NULL;
-    napi_value ab;
-    if (napi_create_arraybuffer(env, 576, &dst, &ab) != napi_ok) return NULL;
-    memcpy(dst, j->miller, 576);
-    napi_create_typedarray(env, napi_uint8_array, 576, ab, 0, &v);
-    napi_set_named_property(env, o, "miller", v);
-    napi_get_boolean(env, j->ok != 0, &v);
-    napi_set_named_property(env, o, "ok", v);
-  }
-  return o;
-}
-
-static void exec_verify(napi_env env, void* data) { /* libuv worker thread */
-  (void)env;
-  run_verify((verify_job*)data);
-}
-
-static void done_verify(napi_env env, napi_status st, void* data) { /* main thread */
-  verify_job* j = (verify_job*)data;
-  if (st != napi_ok && j->status == BGV_OK) {
-    j->status = BGV_E_INVALID_ARG;
-    snprintf(j->err, sizeof j->err, "async work cancelled");
-  }
-  if (j->status != BGV_OK) {
-    napi_value msg, err;
-    napi_create_string_utf8(env, j->err, NAPI_AUTO_LENGTH, &msg);
-    napi_create_error(env, NULL, msg, &err);
-    napi_reject_deferred(env, j->deferred, err);
-  } else if (j->kind == K_COMBINE) {
-    napi_value b;
-    napi_get_boolean(env, j->ok != 0, &b);
-    napi_resolve_deferred(env, j->deferred, b);
-  } else {
-    napi_resolve_deferred(env, j->deferred, result_object(env, j));
-  }
-  for (int k = 0; k < N_FIELDS; k++)
-    if (j->refs[k]) napi_delete_reference(env, j->refs[k]); /* unpin the inputs */
-  for (int k = 0; k < NB_FIELDS; k++)
-    if (j->brefs[k]) napi_delete_reference(env, j->brefs[k]);
-  if (j->ctx_ref) napi_delete_reference(env, j->ctx_ref);
-  napi_delete_async_work(env, j->work);
-  free_job_arrays(j);
-  free(j);
-}
-
-/* queue j on the libuv pool; the promise settles in done_verify */
-static napi_value queue_job(napi_env env, napi_value ctx_val, verify_job* j, const char* label) {
-  napi_create_reference(env, ctx_val, 1, &j->ctx_ref); /* the context outlives its queued work */
-  napi_value promise, name;
-  NAPI_CALL(env, napi_create_promise(env, &j->deferred, &promise));
-  NAPI_CALL(env, napi_create_string_utf8(env, label, NAPI_AUTO_LENGTH, &name));
-  NAPI_CALL(env, napi_create_async_work(env, NULL, name, exec_verify, done_verify, j, &j->work));
-  NAPI_CALL(env, napi_queue_async_work(env, j->work));
-  return promise;
-}
-
-static napi_value queue_batch(napi_env env, napi_callback_info info, int kind, const char* label) {
-  size_t argc = 2;
-  napi_value a[2];
-  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, a, NULL, NULL));
-  addon_ctx* c = get_ctx(env, a[0]);
-  if (!c) return NULL;
-  verify_job* j = (verify_job*)calloc(1, sizeof *j);
-  j->c = c;
-  j->kind = kind;
-  if (read_batch(env, a[1], j, 1)) {
-    for (int k = 0; k < N_FIELDS; k++)
-      if (j->refs[k]) napi_delete_reference(env, j->refs[k]);
-    free_job_arrays(j);
-    free(j);
-    return NULL;
-  }
-  j->job_result = (int32_t*)calloc(j->b.n_jobs ? j->b.n_jobs : 1, 4);
-  return queue_job(env, a[0], j, label);
-}
-
-static napi_value Verify(napi_env env, napi_callback_info info) { return queue_batch(env, info, K_VERIFY, "bgv_verify"); }
-
-static napi_value Partial(napi_env env, napi_callback_info info) { return queue_batch(env, info, K_PARTIAL, "bgv_partial"); }
-
-/* partialFinish(ctx): the shard left by the last partial() on the context */
-static napi_value PartialFinish(napi_env env, napi_callback_info info) {
-  size_t argc = 1;
-  napi_value a[1];
-  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, a, NULL, NULL));
-  addon_ctx* c = get_ctx(env, a[0]);
-  if (!c) return NULL;
-  verify_job* j = (verify_job*)calloc(1, sizeof *j);
-  j->c = c;
-  j->kind = K_FINISH; /* results sized on the pool thread from the pending partial */
-  return queue_job(env, a[0], j, "bgv_partial_finish");
-}
-
-static napi_value CombineFinal(napi_env env, napi_callback_info info) {
-  size_t argc = 2;
-  napi_value a[2];
-  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, a, NULL, NULL));
-  addon_ctx* c = get_ctx(env, a[0]);
-  if (!c) return NULL;
-  void* data;
-  size_t len;
-  if (argc < 2 || typed(env, a[1], napi_uint8_array, &data, &len) || len % 576) {
-    napi_throw_type_error(env, NULL, "combineFinal(ctx, Uint8Array of 576-byte partials)");
-    return NULL;
-  }
-  verify_job* j = (verify_job*)calloc(1, sizeof *j);
-  j->c = c;
-  j->kind = K_COMBINE;
-  j->n_parts = (uint32_t)(len / 576);
-  j->parts = (uint8_t*)malloc(len ? len : 1); /* copied: the caller may reuse its buffer */
-  if (len) memcpy(j->parts, data, len);
-  return queue_job(env, a[0], j, "bgv_combine_final");
-}
-
-static napi_value VerifySync(napi_env env, napi_callback_info info) {
-  size_t argc = 2;
-  napi_value a[2];
-  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, a, NULL, NULL));
-  addon_ctx* c = get_ctx(env, a[0]);
-  if (!c) return NULL;
-  verify_job j;
-  memset(&j, 0, sizeof j);
-  j.c = c;
-  if (read_batch(env, a[1], &j, 0)) {
-    free_job_arrays(&j);
-    return NULL;
-  }
-  j.job_result = (int32_t*)calloc(j.b.n_jobs ? j.b.n_jobs : 1, 4);
-  run_verify(&j);
-  napi_value r = NULL;
-  if (j.status != BGV_OK) napi_throw_error(env, NULL, j.err);
-  else r = result_object(env, &j);
-  free_job_arrays(&j);
-  return r;
+/* ------------------------------------------------------- committee bitfields
+ * verifyBits(ctx, batch) -> Promise<result>, verifyBitsSync(ctx, batch) -> result (bgv_verify_bits).
+ * batch = {jobOffsets: Uint32Array, src: Uint32Array (4 per set: list, off, len, bitsOff; list 0xffffffff = an
+ * explicit run pkIndices[off .. off + len)), bits: Uint8Array (all bitfields, byte-packed, SSZ bit order),
+ * pkIndices: Uint32Array (keys of the explicit sets), msgs, sigs, sigLen, rawPks? as for verify}.
+ * result as for verify.  jobOffsets and src are copied at call time; the library stages every array into pinned
+ * memory and checks the copy against the lengths taken here, so a caller that mutates its arrays while the work
+ * is queued cannot make the device read past them. */
+static int read_bits(napi_env env, napi_value obj, job* j, int pin) {
+  const size_t* n = j->len;
+  if (read_fields(env, obj, j, BITS_FIELDS, &BITS_REFUSALS, pin)) return -1;
+  if (n[F_JOB] < 1 || n[F_SRC] % 4) return refuse_range(env, "jobOffsets needs at least one entry, src four entries per set");
+  const size_t n_sets = n[F_SRC] / 4;
+  if (n[F_MSG] < 32ull * n_sets || n[F_SIG] < 192ull * n_sets || n[F_LEN] < n_sets)
+    return refuse_range(env, "msgs / sigs / sigLen shorter than the set count");
+  if (n_sets > 0xffffffffull || n[F_BITS] > 0xffffffffull || n[F_PKI] > 0xffffffffull) return refuse_range(env, "bits batch too large");
+  j->n_jobs = (uint32_t)(n[F_JOB] - 1);
+  j->n_sets = (uint32_t)n_sets;
+  FILL_SOURCES(j->u.bits, j);
+  j->u.bits.n_jobs = j->n_jobs;
+  j->u.bits.job_offsets = (const uint32_t*)j->ptr[F_JOB];
+  return job_alloc(env, j, O_JOBS, j->n_jobs, 4);
 }
 
 /* ------------------------------------------------------- same-message batches
@@ -629,180 +565,55 @@ static napi_value VerifySync(napi_env env, napi_callback_info info) {
  * verifySameMessage plus take?: Uint8Array (one per set, 0 keeps a valid set out of its group's aggregate) and
  * prevSigs?: Uint8Array (96 B per GROUP, the running aggregates, compressed); the result gains aggSigs: Uint8Array
  * (96 B per group), aggCount: Uint32Array and aggCode: Int32Array (bgv_sm_agg). */
-enum { S_GRP, S_PKI, S_MSG, S_SIG, S_LEN, S_RAW, S_PKO, S_SRC, S_BITS, S_FIELDS }; /* S_SRC on: verifySameMessageBits only */
-static const char* SM_FIELD[S_FIELDS] = {"groupOffsets", "pkIndices", "msgs", "sigs", "sigLen", "rawPks", "pkOffsets", "src", "bits"};
-static const napi_typedarray_type SM_FIELD_T[S_FIELDS] = {napi_uint32_array, napi_uint32_array, napi_uint8_array,
-                                                          napi_uint8_array,  napi_uint32_array, napi_uint8_array,
-                                                          napi_uint32_array, napi_uint32_array, napi_uint8_array};
-
-typedef struct {
-  addon_ctx* c;
-  bgv_sm_batch b;
-  int agg;          /* 1: the sets' keys are aggregates: `ba` is the batch, `b` keeps the counts;
-                       2: ... given as committee sets: `bb` is the batch (verifySameMessageBits) */
-  bgv_sma_batch ba;
-  bgv_smb_batch bb;
-  uint32_t* src_copy;
-  bgv_bits_path path; /* agg == 2: the path counters of the call */
-  int with_sums;      /* verifySameMessageAggregate (agg == 0): `ag` and its three outputs */
-  bgv_sm_agg ag;
-  uint8_t* agg_sigs;
-  uint32_t* agg_count;
-  int32_t* agg_code;
-  napi_ref sum_refs[2]; /* take, prevSigs */
-  uint32_t* pk_off;
-  uint32_t* group_off;
-  uint8_t* valid;
-  int32_t* codes;
-  bgv_sm_stats stats;
-  double t_start_ms, t_end_ms;
-  int status;
-  char err[512];
-  napi_ref refs[S_FIELDS];
-  napi_ref ctx_ref;
-  napi_async_work work;
-  napi_deferred deferred;
-} sm_job;
-
-static void sm_free(napi_env env, sm_job* j) {
-  for (int k = 0; k < S_FIELDS; k++)
-    if (j->refs[k]) napi_delete_reference(env, j->refs[k]);
-  if (j->ctx_ref) napi_delete_reference(env, j->ctx_ref);
-  free(j->group_off);
-  free(j->pk_off);
-  free(j->src_copy);
-  free(j->valid);
-  free(j->codes);
-  for (int k = 0; k < 2; k++)
-    if (j->sum_refs[k]) napi_delete_reference(env, j->sum_refs[k]);
-  free(j->agg_sigs);
-  free(j->agg_count);
-  free(j->agg_code);
+static int alloc_set_outputs(napi_env env, job* j) {
+  return job_alloc(env, j, O_VALID, j->n_sets, 1) || job_alloc(env, j, O_CODES, j->n_sets, 4) ? -1 : 0;
 }
 
-static int sm_read_batch(napi_env env, napi_value obj, sm_job* j, int pin) {
-  void* p[S_FIELDS] = {0};
-  size_t n[S_FIELDS] = {0};
-  napi_value v[S_FIELDS];
-  for (int k = 0; k < S_SRC; k++) {
-    bool has = false;
-    if (k == S_PKO && !j->agg) continue;
-    napi_has_named_property(env, obj, SM_FIELD[k], &has);
-    if (!has) {
-      if (k == S_RAW) continue;
-      napi_throw_type_error(env, NULL, "batch field missing");
-      return -1;
-    }
-    napi_get_named_property(env, obj, SM_FIELD[k], &v[k]);
-    if (typed(env, v[k], SM_FIELD_T[k], &p[k], &n[k])) {
-      napi_throw_type_error(env, NULL, "batch field has the wrong typed-array type");
-      return -1;
-    }
+/* K_SM_AGGREGATE, after the batch of K_SM: take and prevSigs, one after the other, and the groups' outputs */
+static int read_sums(napi_env env, napi_value obj, job* j, int pin) {
+  const size_t need[2] = {j->n_sets, 96ull * j->n_groups};
+  const uint8_t* row[2] = {TAKE_FIELD, PREV_FIELD};
+  for (int k = 0; k < 2; k++) {
+    if (read_fields(env, obj, j, row[k], &SUMS_REFUSALS, pin)) return -1;
+    if (j->ptr[row[k][0]] && j->len[row[k][0]] < need[k]) return refuse_range(env, "take / prevSigs shorter than the set / group count");
   }
-  if (n[S_GRP] < 1) {
-    napi_throw_range_error(env, NULL, "groupOffsets needs at least one entry");
+  if (job_alloc(env, j, O_AGG_SIGS, j->n_groups, 96) || job_alloc(env, j, O_AGG_COUNT, j->n_groups, 4) ||
+      job_alloc(env, j, O_AGG_CODE, j->n_groups, 4))
     return -1;
-  }
-  memset(&j->b, 0, sizeof j->b);
-  j->b.n_groups = (uint32_t)(n[S_GRP] - 1);
-  j->group_off = (uint32_t*)malloc(4 * n[S_GRP]);
-  if (!j->group_off) {
-    napi_throw_error(env, NULL, "out of memory");
-    return -1;
-  }
-  memcpy(j->group_off, p[S_GRP], 4 * n[S_GRP]);
-  const uint32_t n_sets = j->group_off[j->b.n_groups];
-  j->b.n_sets = n_sets;
-  size_t n_keys = n_sets;
-  if (j->agg) {
-    if (n[S_PKO] < (size_t)n_sets + 1) {
-      napi_throw_range_error(env, NULL, "pkOffsets shorter than the set count + 1");
-      return -1;
-    }
-    j->pk_off = (uint32_t*)malloc(4 * ((size_t)n_sets + 1));
-    if (!j->pk_off) {
-      napi_throw_error(env, NULL, "out of memory");
-      return -1;
-    }
-    memcpy(j->pk_off, p[S_PKO], 4 * ((size_t)n_sets + 1));
-    n_keys = j->pk_off[n_sets];
-  }
-  if (n[S_MSG] < 32ull * j->b.n_groups || n[S_SIG] < 192ull * n_sets || n[S_LEN] < n_sets || n[S_PKI] < n_keys) {
-    napi_throw_range_error(env, NULL, "msgs / sigs / sigLen / pkIndices shorter than the group, set or key count");
-    return -1;
-  }
-  j->valid = (uint8_t*)calloc(n_sets ? n_sets : 1, 1);
-  j->codes = (int32_t*)calloc(n_sets ? n_sets : 1, 4);
-  if (!j->valid || !j->codes) {
-    napi_throw_error(env, NULL, "out of memory");
-    return -1;
-  }
-  if (pin)
-    for (int k = 0; k < S_SRC; k++)
-      if (p[k] && k != S_GRP && k != S_PKO) napi_create_reference(env, v[k], 1, &j->refs[k]);
-  j->b.group_offsets = j->group_off;
-  j->b.pk_indices = (const uint32_t*)p[S_PKI];
-  j->b.msgs = (const uint8_t*)p[S_MSG];
-  j->b.sigs = (const uint8_t*)p[S_SIG];
-  j->b.sig_len = (const uint32_t*)p[S_LEN];
-  j->b.raw_pks = (const uint8_t*)p[S_RAW];
-  j->b.n_raw = (uint32_t)(n[S_RAW] / 96);
-  j->b.scalars = NULL; /* drawn inside the library */
-  j->b.on_device = 0;
-  if (j->with_sums) {
-    static const char* name[2] = {"take", "prevSigs"};
-    const size_t need[2] = {n_sets, 96ull * j->b.n_groups};
-    const void* q[2] = {NULL, NULL};
-    for (int k = 0; k < 2; k++) {
-      bool has = false;
-      napi_value val;
-      napi_valuetype vt;
-      size_t len = 0;
-      void* ptr = NULL;
-      napi_has_named_property(env, obj, name[k], &has);
-      if (!has) continue;
-      napi_get_named_property(env, obj, name[k], &val);
-      napi_typeof(env, val, &vt);
-      if (vt == napi_undefined || vt == napi_null) continue;
-      if (typed(env, val, napi_uint8_array, &ptr, &len)) {
-        napi_throw_type_error(env, NULL, "take / prevSigs must be a Uint8Array");
-        return -1;
-      }
-      if (len < need[k]) {
-        napi_throw_range_error(env, NULL, "take / prevSigs shorter than the set / group count");
-        return -1;
-      }
-      q[k] = ptr;
-      if (pin) napi_create_reference(env, val, 1, &j->sum_refs[k]);
-    }
-    const size_t G = j->b.n_groups ? j->b.n_groups : 1;
-    j->agg_sigs = (uint8_t*)calloc(G, 96);
-    j->agg_count = (uint32_t*)calloc(G, 4);
-    j->agg_code = (int32_t*)calloc(G, 4);
-    if (!j->agg_sigs || !j->agg_count || !j->agg_code) {
-      napi_throw_error(env, NULL, "out of memory");
-      return -1;
-    }
-    j->ag.take = (const uint8_t*)q[0];
-    j->ag.prev_sig96 = (const uint8_t*)q[1];
-    j->ag.agg_sig96 = j->agg_sigs;
-    j->ag.agg_count = j->agg_count;
-    j->ag.agg_code = j->agg_code;
-  }
-  if (j->agg) {
-    memset(&j->ba, 0, sizeof j->ba);
-    j->ba.n_sets = n_sets;
-    j->ba.n_groups = j->b.n_groups;
-    j->ba.group_offsets = j->group_off;
-    j->ba.pk_offsets = j->pk_off;
-    j->ba.pk_indices = j->b.pk_indices;
-    j->ba.raw_pks = j->b.raw_pks;
-    j->ba.n_raw = j->b.n_raw;
-    j->ba.msgs = j->b.msgs;
-    j->ba.sigs = j->b.sigs;
-    j->ba.sig_len = j->b.sig_len;
-  }
+  j->ag.take = (const uint8_t*)j->ptr[F_TAKE];
+  j->ag.prev_sig96 = (const uint8_t*)j->ptr[F_PREV];
+  j->ag.agg_sig96 = (uint8_t*)j->own[O_AGG_SIGS];
+  j->ag.agg_count = (uint32_t*)j->own[O_AGG_COUNT];
+  j->ag.agg_code = (int32_t*)j->own[O_AGG_CODE];
   return 0;
+}
+
+/* K_SM, K_SM_AGGREGATE, K_SMA: the set count is the last group offset; K_SMA's key count the last key offset */
+static int read_sm(napi_env env, napi_value obj, job* j, int pin) {
+  const size_t* n = j->len;
+  if (read_fields(env, obj, j, j->kind == K_SMA ? SMA_FIELDS : SM_FIELDS, &BATCH_REFUSALS, pin)) return -1;
+  if (n[F_GRP] < 1) return refuse_range(env, "groupOffsets needs at least one entry");
+  j->n_groups = (uint32_t)(n[F_GRP] - 1);
+  j->n_sets = ((const uint32_t*)j->ptr[F_GRP])[j->n_groups];
+  size_t n_keys = j->n_sets;
+  if (j->kind == K_SMA) {
+    if (n[F_PKO] < (size_t)j->n_sets + 1) return refuse_range(env, "pkOffsets shorter than the set count + 1");
+    n_keys = ((const uint32_t*)j->ptr[F_PKO])[j->n_sets];
+  }
+  if (n[F_MSG] < 32ull * j->n_groups || n[F_SIG] < 192ull * j->n_sets || n[F_LEN] < j->n_sets || n[F_PKI] < n_keys)
+    return refuse_range(env, "msgs / sigs / sigLen / pkIndices shorter than the group, set or key count");
+  if (alloc_set_outputs(env, j)) return -1;
+  if (j->kind == K_SMA) {
+    FILL_SETS(j->u.sma, j);
+    j->u.sma.n_groups = j->n_groups;
+    j->u.sma.group_offsets = (const uint32_t*)j->ptr[F_GRP];
+    j->u.sma.pk_offsets = (const uint32_t*)j->ptr[F_PKO];
+    return 0;
+  }
+  FILL_SETS(j->u.sm, j);
+  j->u.sm.n_groups = j->n_groups;
+  j->u.sm.group_offsets = (const uint32_t*)j->ptr[F_GRP];
+  return j->kind == K_SM_AGGREGATE ? read_sums(env, obj, j, pin) : 0;
 }
 
 /* verifySameMessageBits(ctx, batch) -> Promise<result>, verifySameMessageBitsSync(ctx, batch) -> result
@@ -811,154 +622,168 @@ static int sm_read_batch(napi_env env, napi_value obj, sm_job* j, int pin) {
  * result as verifySameMessageAgg plus pubkeysAggregated, the participating keys from the call's path counters
  * (the caller holds no index lists to count them from).  Ownership as for verifyBits: groupOffsets and src are
  * copied at call time, the other typed arrays are pinned until completion. */
-static int smb_read_batch(napi_env env, napi_value obj, sm_job* j, int pin) {
-  void* p[S_FIELDS] = {0};
-  size_t n[S_FIELDS] = {0};
-  napi_value v[S_FIELDS];
-  for (int k = 0; k < S_FIELDS; k++) {
-    bool has = false;
-    if (k == S_PKO) continue;
-    napi_has_named_property(env, obj, SM_FIELD[k], &has);
-    if (!has) {
-      if (k == S_RAW) continue;
-      napi_throw_type_error(env, NULL, "batch field missing");
-      return -1;
-    }
-    napi_get_named_property(env, obj, SM_FIELD[k], &v[k]);
-    if (typed(env, v[k], SM_FIELD_T[k], &p[k], &n[k])) {
-      napi_throw_type_error(env, NULL, "batch field has the wrong typed-array type");
-      return -1;
-    }
-  }
-  if (n[S_GRP] < 1 || n[S_SRC] % 4) {
-    napi_throw_range_error(env, NULL, "groupOffsets needs at least one entry, src four entries per set");
-    return -1;
-  }
-  const size_t n_sets = n[S_SRC] / 4;
-  if (n_sets > 0xffffffffull || n[S_BITS] > 0xffffffffull || n[S_PKI] > 0xffffffffull) {
-    napi_throw_range_error(env, NULL, "bits batch too large");
-    return -1;
-  }
-  memset(&j->b, 0, sizeof j->b);
-  j->b.n_groups = (uint32_t)(n[S_GRP] - 1);
-  j->b.n_sets = (uint32_t)n_sets;
-  j->group_off = (uint32_t*)malloc(4 * n[S_GRP]);
-  j->src_copy = (uint32_t*)malloc(n[S_SRC] ? 4 * n[S_SRC] : 4);
-  if (!j->group_off || !j->src_copy) {
-    napi_throw_error(env, NULL, "out of memory");
-    return -1;
-  }
-  memcpy(j->group_off, p[S_GRP], 4 * n[S_GRP]);
-  if (n[S_SRC]) memcpy(j->src_copy, p[S_SRC], 4 * n[S_SRC]);
-  if (j->group_off[j->b.n_groups] != n_sets) {
-    napi_throw_range_error(env, NULL, "groupOffsets must end at the set count of src");
-    return -1;
-  }
-  if (n[S_MSG] < 32ull * j->b.n_groups || n[S_SIG] < 192ull * n_sets || n[S_LEN] < n_sets) {
-    napi_throw_range_error(env, NULL, "msgs / sigs / sigLen shorter than the group or set count");
-    return -1;
-  }
-  j->valid = (uint8_t*)calloc(n_sets ? n_sets : 1, 1);
-  j->codes = (int32_t*)calloc(n_sets ? n_sets : 1, 4);
-  if (!j->valid || !j->codes) {
-    napi_throw_error(env, NULL, "out of memory");
-    return -1;
-  }
-  if (pin)
-    for (int k = 0; k < S_FIELDS; k++)
-      if (p[k] && k != S_GRP && k != S_SRC) napi_create_reference(env, v[k], 1, &j->refs[k]);
-  memset(&j->bb, 0, sizeof j->bb);
-  j->bb.n_sets = (uint32_t)n_sets;
-  j->bb.n_groups = j->b.n_groups;
-  j->bb.group_offsets = j->group_off;
-  j->bb.src = (const bgv_set_src*)j->src_copy;
-  j->bb.bits = (const uint8_t*)p[S_BITS];
-  j->bb.bits_len = (uint32_t)n[S_BITS];
-  j->bb.pk_indices = (const uint32_t*)p[S_PKI];
-  j->bb.n_indices = (uint32_t)n[S_PKI];
-  j->bb.raw_pks = (const uint8_t*)p[S_RAW];
-  j->bb.n_raw = (uint32_t)(n[S_RAW] / 96);
-  j->bb.msgs = (const uint8_t*)p[S_MSG];
-  j->bb.sigs = (const uint8_t*)p[S_SIG];
-  j->bb.sig_len = (const uint32_t*)p[S_LEN];
-  j->bb.scalars = NULL; /* drawn inside the library */
-  j->bb.on_device = 0;
+static int read_smb(napi_env env, napi_value obj, job* j, int pin) {
+  const size_t* n = j->len;
+  if (read_fields(env, obj, j, SMB_FIELDS, &BATCH_REFUSALS, pin)) return -1;
+  if (n[F_GRP] < 1 || n[F_SRC] % 4) return refuse_range(env, "groupOffsets needs at least one entry, src four entries per set");
+  const size_t n_sets = n[F_SRC] / 4;
+  if (n_sets > 0xffffffffull || n[F_BITS] > 0xffffffffull || n[F_PKI] > 0xffffffffull) return refuse_range(env, "bits batch too large");
+  j->n_groups = (uint32_t)(n[F_GRP] - 1);
+  j->n_sets = (uint32_t)n_sets;
+  if (((const uint32_t*)j->ptr[F_GRP])[j->n_groups] != n_sets) return refuse_range(env, "groupOffsets must end at the set count of src");
+  if (n[F_MSG] < 32ull * j->n_groups || n[F_SIG] < 192ull * n_sets || n[F_LEN] < n_sets)
+    return refuse_range(env, "msgs / sigs / sigLen shorter than the group or set count");
+  FILL_SOURCES(j->u.smb, j);
+  j->u.smb.n_groups = j->n_groups;
+  j->u.smb.group_offsets = (const uint32_t*)j->ptr[F_GRP];
+  return alloc_set_outputs(env, j);
+}
+
+/* ---------------------------------------------------------------- results */
+/* the kinds whose hash and pair counters are read with the call and reported with its result */
+static int counted(job_kind k) { return k == K_VERIFY || k == K_BITS || k == K_PARTIAL; }
+
+/* deviceMs, workerStartMs, workerEndMs: what the pool's timing metrics are fed from */
+static void set_times(napi_env env, napi_value o, const job* j, float device_ms) {
+  set_double(env, o, "deviceMs", (double)device_ms);
+  set_double(env, o, "workerStartMs", j->t_start_ms);
+  set_double(env, o, "workerEndMs", j->t_end_ms);
+}
+
+static int set_array(napi_env env, napi_value o, const char* name, napi_typedarray_type t, size_t elem, const void* src, size_t n) {
+  napi_value v = new_typed_array(env, t, elem, src, n);
+  if (!v) return -1;
+  napi_set_named_property(env, o, name, v);
   return 0;
 }
 
-static void sm_run(sm_job* j) {
+/* {results, batchRetries, batchSigsSuccess, pubkeysAggregated, deviceMs, workerStartMs, workerEndMs}; verify, verifyBits
+ * and partial add {hashes, millerPairs}, partial {miller, ok} */
+static napi_value result_object(napi_env env, const job* j) {
+  napi_value o, v;
+  if (napi_create_object(env, &o) != napi_ok) return NULL;
+  if (set_array(env, o, "results", napi_int32_array, 4, j->own[O_JOBS], j->n_jobs)) return NULL;
+  if (!SET_U32S(env, o, {"batchRetries", j->stats.batch_retries}, {"batchSigsSuccess", j->stats.batch_sigs_success})) return NULL;
+  set_double(env, o, "pubkeysAggregated", (double)j->stats.pubkeys_aggregated);
+  set_times(env, o, j, j->stats.total_ms);
+  if (counted(j->kind) && !SET_U32S(env, o, {"hashes", j->hash_path.hashes}, {"millerPairs", j->pair_path.pairs})) return NULL;
+  if (j->kind == K_PARTIAL) {
+    if (set_array(env, o, "miller", napi_uint8_array, 1, j->miller, 576)) return NULL;
+    napi_get_boolean(env, j->ok != 0, &v);
+    napi_set_named_property(env, o, "ok", v);
+  }
+  return o;
+}
+
+/* {valid, codes, segments, hashes, pairs, groupsRetried, setsRetried, deviceMs, workerStartMs, workerEndMs}; K_SMB adds
+ * pubkeysAggregated, K_SM_AGGREGATE {aggSigs, aggCount, aggCode} */
+static napi_value sm_result(napi_env env, const job* j) {
+  napi_value o;
+  const bgv_sm_stats* s = &j->sm_stats;
+  if (napi_create_object(env, &o) != napi_ok) return NULL;
+  if (set_array(env, o, "valid", napi_uint8_array, 1, j->own[O_VALID], j->n_sets) ||
+      set_array(env, o, "codes", napi_int32_array, 4, j->own[O_CODES], j->n_sets))
+    return NULL;
+  if (!SET_U32S(env, o, {"segments", s->n_segments}, {"hashes", s->hashes}, {"pairs", s->pairs}, {"groupsRetried", s->groups_retried},
+                {"setsRetried", s->sets_retried}))
+    return NULL;
+  if (j->kind == K_SMB && !SET_U32S(env, o, {"pubkeysAggregated", j->bits_path.keys_expanded})) return NULL;
+  if (j->kind == K_SM_AGGREGATE) {
+    const size_t G = j->n_sets ? j->n_groups : 0; /* an empty batch writes nothing */
+    if (set_array(env, o, "aggSigs", napi_uint8_array, 1, j->own[O_AGG_SIGS], 96 * G) ||
+        set_array(env, o, "aggCount", napi_uint32_array, 4, j->own[O_AGG_COUNT], G) ||
+        set_array(env, o, "aggCode", napi_int32_array, 4, j->own[O_AGG_CODE], G))
+      return NULL;
+  }
+  set_times(env, o, j, s->total_ms);
+  return o;
+}
+
+static napi_value combine_result(napi_env env, const job* j) {
+  napi_value b;
+  napi_get_boolean(env, j->ok != 0, &b);
+  return b;
+}
+
+/* per kind: the reader of its batch (none: the entry fills the job itself), the result it settles with, the label
+ * of its async work and the arguments its entry takes */
+static const struct {
+  int (*read)(napi_env, napi_value, job*, int pin);
+  napi_value (*result)(napi_env, const job*);
+  const char* label;
+  size_t arity;
+} KIND[N_KINDS] = {
+    [K_VERIFY] = {read_verify, result_object, "bgv_verify", 2},
+    [K_PARTIAL] = {read_verify, result_object, "bgv_partial", 2},
+    [K_BITS] = {read_bits, result_object, "bgv_verify_bits", 2},
+    [K_FINISH] = {NULL, result_object, "bgv_partial_finish", 1},
+    [K_COMBINE] = {NULL, combine_result, "bgv_combine_final", 2},
+    [K_SM] = {read_sm, sm_result, "bgv_verify_same_message", 2},
+    [K_SM_AGGREGATE] = {read_sm, sm_result, "bgv_verify_same_message_aggregate", 2},
+    [K_SMA] = {read_sm, sm_result, "bgv_verify_same_message_agg", 2},
+    [K_SMB] = {read_smb, sm_result, "bgv_verify_same_message_bits", 2},
+};
+
+/* ------------------------------------------------------------ running a job */
+static double now_ms(void) {
+  struct timespec t;
+  clock_gettime(CLOCK_MONOTONIC, &t);
+  return (double)t.tv_sec * 1e3 + (double)t.tv_nsec * 1e-6;
+}
+
+static int job_call(job* j) {
+  bgv_ctx* x = j->c->ctx;
+  int st;
+  switch (j->kind) {
+    case K_VERIFY: return bgv_verify(x, &j->u.b, (int32_t*)j->own[O_JOBS], NULL, &j->stats);
+    case K_BITS: return bgv_verify_bits(x, &j->u.bits, (int32_t*)j->own[O_JOBS], NULL, &j->stats);
+    case K_PARTIAL:
+      st = bgv_partial(x, &j->u.b, j->miller, NULL, (int32_t*)j->own[O_JOBS], &j->ok);
+      j->c->partial_jobs = j->n_jobs;
+      if (st != BGV_OK) return st;
+      st = bgv_last_stats(x, &j->stats);
+      j->stats.pubkeys_aggregated = j->n_sets ? j->u.b.pk_offsets[j->n_sets] : 0;
+      return st;
+    case K_FINISH:
+      j->n_jobs = j->c->partial_jobs;
+      j->own[O_JOBS] = calloc(j->n_jobs ? j->n_jobs : 1, 4);
+      return j->own[O_JOBS] ? bgv_partial_finish(x, (int32_t*)j->own[O_JOBS], &j->stats) : BGV_E_INVALID_ARG;
+    case K_COMBINE: return bgv_combine_final(x, (const uint8_t*)j->own[O_PARTS], j->n_parts, &j->ok);
+    case K_SM: return bgv_verify_same_message(x, &j->u.sm, (uint8_t*)j->own[O_VALID], (int32_t*)j->own[O_CODES], &j->sm_stats);
+    case K_SM_AGGREGATE:
+      return bgv_verify_same_message_aggregate(x, &j->u.sm, &j->ag, (uint8_t*)j->own[O_VALID], (int32_t*)j->own[O_CODES], &j->sm_stats);
+    case K_SMA: return bgv_verify_same_message_agg(x, &j->u.sma, (uint8_t*)j->own[O_VALID], (int32_t*)j->own[O_CODES], &j->sm_stats);
+    case K_SMB:
+      st = bgv_verify_same_message_bits(x, &j->u.smb, (uint8_t*)j->own[O_VALID], (int32_t*)j->own[O_CODES], &j->sm_stats);
+      return st == BGV_OK ? bgv_bits_path_stats(x, &j->bits_path) : st; /* under the same lock: this call's */
+    default: return BGV_E_INVALID_ARG;
+  }
+}
+
+static void job_run(job* j) {
   pthread_mutex_lock(&j->c->mu);
   j->t_start_ms = now_ms();
   if (j->c->closed) {
     j->status = BGV_E_INVALID_ARG;
     snprintf(j->err, sizeof j->err, "QUEUE_ERROR_QUEUE_ABORTED");
   } else {
-    if (j->agg == 2) {
-      j->status = bgv_verify_same_message_bits(j->c->ctx, &j->bb, j->valid, j->codes, &j->stats);
-      if (j->status == BGV_OK) j->status = bgv_bits_path_stats(j->c->ctx, &j->path); /* under the same lock: this call's */
-    } else {
-      j->status = j->agg         ? bgv_verify_same_message_agg(j->c->ctx, &j->ba, j->valid, j->codes, &j->stats)
-                  : j->with_sums ? bgv_verify_same_message_aggregate(j->c->ctx, &j->b, &j->ag, j->valid, j->codes, &j->stats)
-                                 : bgv_verify_same_message(j->c->ctx, &j->b, j->valid, j->codes, &j->stats);
-    }
+    j->status = job_call(j);
+    /* under the same lock: this call's evaluations, not a later call's */
+    if (j->status == BGV_OK && counted(j->kind)) j->status = bgv_hash_stats(j->c->ctx, &j->hash_path);
+    if (j->status == BGV_OK && counted(j->kind)) j->status = bgv_pair_stats(j->c->ctx, &j->pair_path);
     if (j->status != BGV_OK) snprintf(j->err, sizeof j->err, "bgv error %d: %s", j->status, bgv_last_error());
   }
   j->t_end_ms = now_ms();
   pthread_mutex_unlock(&j->c->mu);
 }
 
-static napi_value sm_result(napi_env env, const sm_job* j) {
-  napi_value o, v, ab;
-  void* dst = NULL;
-  if (napi_create_object(env, &o) != napi_ok) return NULL;
-  if (napi_create_arraybuffer(env, j->b.n_sets, &dst, &ab) != napi_ok) return NULL;
-  if (j->b.n_sets) memcpy(dst, j->valid, j->b.n_sets);
-  napi_create_typedarray(env, napi_uint8_array, j->b.n_sets, ab, 0, &v);
-  napi_set_named_property(env, o, "valid", v);
-  v = new_int32_array(env, j->codes, j->b.n_sets);
-  if (!v) return NULL;
-  napi_set_named_property(env, o, "codes", v);
-  const struct { const char* name; uint32_t val; } u[] = {
-      {"segments", j->stats.n_segments}, {"hashes", j->stats.hashes}, {"pairs", j->stats.pairs},
-      {"groupsRetried", j->stats.groups_retried}, {"setsRetried", j->stats.sets_retried}};
-  for (size_t k = 0; k < sizeof u / sizeof u[0]; k++) {
-    napi_create_uint32(env, u[k].val, &v);
-    napi_set_named_property(env, o, u[k].name, v);
-  }
-  if (j->agg == 2) {
-    napi_create_uint32(env, j->path.keys_expanded, &v);
-    napi_set_named_property(env, o, "pubkeysAggregated", v);
-  }
-  if (j->with_sums) {
-    const size_t G = j->b.n_sets ? j->b.n_groups : 0; /* an empty batch writes nothing */
-    if (napi_create_arraybuffer(env, 96 * G, &dst, &ab) != napi_ok) return NULL;
-    if (G) memcpy(dst, j->agg_sigs, 96 * G);
-    napi_create_typedarray(env, napi_uint8_array, 96 * G, ab, 0, &v);
-    napi_set_named_property(env, o, "aggSigs", v);
-    if (napi_create_arraybuffer(env, 4 * G, &dst, &ab) != napi_ok) return NULL;
-    if (G) memcpy(dst, j->agg_count, 4 * G);
-    napi_create_typedarray(env, napi_uint32_array, G, ab, 0, &v);
-    napi_set_named_property(env, o, "aggCount", v);
-    v = new_int32_array(env, j->agg_code, G);
-    if (!v) return NULL;
-    napi_set_named_property(env, o, "aggCode", v);
-  }
-  napi_create_double(env, (double)j->stats.total_ms, &v);
-  napi_set_named_property(env, o, "deviceMs", v);
-  napi_create_double(env, j->t_start_ms, &v);
-  napi_set_named_property(env, o, "workerStartMs", v);
-  napi_create_double(env, j->t_end_ms, &v);
-  napi_set_named_property(env, o, "workerEndMs", v);
-  return o;
-}
-
-static void sm_exec(napi_env env, void* data) { /* libuv worker thread */
+static void job_exec(napi_env env, void* data) { /* libuv worker thread */
   (void)env;
-  sm_run((sm_job*)data);
+  job_run((job*)data);
 }
 
-static void sm_done(napi_env env, napi_status st, void* data) { /* main thread */
-  sm_job* j = (sm_job*)data;
+static void job_done(napi_env env, napi_status st, void* data) { /* main thread */
+  job* j = (job*)data;
   if (st != napi_ok && j->status == BGV_OK) {
     j->status = BGV_E_INVALID_ARG;
     snprintf(j->err, sizeof j->err, "async work cancelled");
@@ -969,194 +794,95 @@ static void sm_done(napi_env env, napi_status st, void* data) { /* main thread *
     napi_create_error(env, NULL, msg, &err);
     napi_reject_deferred(env, j->deferred, err);
   } else {
-    napi_resolve_deferred(env, j->deferred, sm_result(env, j));
+    napi_resolve_deferred(env, j->deferred, KIND[j->kind].result(env, j));
   }
   napi_delete_async_work(env, j->work);
-  sm_free(env, j);
+  job_free(env, j);
   free(j);
 }
 
-static napi_value sm_async(napi_env env, napi_callback_info info, int agg) {
-  size_t argc = 2;
-  napi_value a[2];
-  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, a, NULL, NULL));
-  addon_ctx* c = get_ctx(env, a[0]);
-  if (!c) return NULL;
-  sm_job* j = (sm_job*)calloc(1, sizeof *j);
-  j->c = c;
-  j->with_sums = agg == 3;
-  if (agg == 3) agg = 0;
-  j->agg = agg;
-  if (agg == 2 ? smb_read_batch(env, a[1], j, 1) : sm_read_batch(env, a[1], j, 1)) {
-    sm_free(env, j);
-    free(j);
-    return NULL;
-  }
-  napi_create_reference(env, a[0], 1, &j->ctx_ref); /* the context outlives its queued work */
+/* queues j on the libuv pool; the promise settles in job_done.  A job that cannot be queued is freed here. */
+static napi_value job_queue(napi_env env, napi_value ctx_val, job* j) {
   napi_value promise, name;
-  NAPI_CALL(env, napi_create_promise(env, &j->deferred, &promise));
-  NAPI_CALL(env, napi_create_string_utf8(env, agg == 2 ? "bgv_verify_same_message_bits" : agg ? "bgv_verify_same_message_agg" : j->with_sums ? "bgv_verify_same_message_aggregate" : "bgv_verify_same_message",
-                                         NAPI_AUTO_LENGTH, &name));
-  NAPI_CALL(env, napi_create_async_work(env, NULL, name, sm_exec, sm_done, j, &j->work));
-  NAPI_CALL(env, napi_queue_async_work(env, j->work));
-  return promise;
+  const char* failed = NULL;
+  if (napi_create_reference(env, ctx_val, 1, &j->ctx_ref) != napi_ok) failed = "napi_create_reference"; /* the context outlives its queued work */
+  else if (napi_create_promise(env, &j->deferred, &promise) != napi_ok) failed = "napi_create_promise";
+  else if (napi_create_string_utf8(env, KIND[j->kind].label, NAPI_AUTO_LENGTH, &name) != napi_ok) failed = "napi_create_string_utf8";
+  else if (napi_create_async_work(env, NULL, name, job_exec, job_done, j, &j->work) != napi_ok) failed = "napi_create_async_work";
+  else if (napi_queue_async_work(env, j->work) != napi_ok) failed = "napi_queue_async_work";
+  if (!failed) return promise;
+  char msg[96];
+  snprintf(msg, sizeof msg, "bgv addon: N-API call failed: %s", failed);
+  if (j->work) napi_delete_async_work(env, j->work);
+  job_free(env, j);
+  free(j);
+  napi_throw_error(env, NULL, msg);
+  return NULL;
 }
 
-static napi_value sm_sync(napi_env env, napi_callback_info info, int agg) {
-  size_t argc = 2;
-  napi_value a[2];
-  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, a, NULL, NULL));
-  addon_ctx* c = get_ctx(env, a[0]);
+/* runs j on the calling thread */
+static napi_value job_sync(napi_env env, job* j) {
+  job_run(j);
+  if (j->status == BGV_OK) return KIND[j->kind].result(env, j);
+  napi_throw_error(env, NULL, j->err);
+  return NULL;
+}
+
+/* every entry that runs a device call: (ctx, batch) read by the kind's reader, then on the pool (the arrays that
+ * are not copied pinned) or, sync, on this thread (nothing pinned: the call returns before the caller runs again) */
+static napi_value job_entry(napi_env env, napi_callback_info info, job_kind kind, int sync) {
+  size_t argc = KIND[kind].arity;
+  napi_value a[2], r = NULL;
+  addon_ctx* c = ctx_args(env, info, &argc, a);
   if (!c) return NULL;
-  sm_job j;
-  memset(&j, 0, sizeof j);
-  j.c = c;
-  j.with_sums = agg == 3;
-  if (agg == 3) agg = 0;
-  j.agg = agg;
-  napi_value r = NULL;
-  if (!(agg == 2 ? smb_read_batch(env, a[1], &j, 0) : sm_read_batch(env, a[1], &j, 0))) {
-    sm_run(&j);
-    if (j.status != BGV_OK) napi_throw_error(env, NULL, j.err);
-    else r = sm_result(env, &j);
+  job* j = (job*)calloc(1, sizeof *j);
+  if (!j) {
+    oom(env);
+    return NULL;
   }
-  sm_free(env, &j);
-  return r;
-}
-
-static napi_value VerifySameMessage(napi_env env, napi_callback_info info) { return sm_async(env, info, 0); }
-static napi_value VerifySameMessageSync(napi_env env, napi_callback_info info) { return sm_sync(env, info, 0); }
-static napi_value VerifySameMessageAgg(napi_env env, napi_callback_info info) { return sm_async(env, info, 1); }
-static napi_value VerifySameMessageAggSync(napi_env env, napi_callback_info info) { return sm_sync(env, info, 1); }
-static napi_value VerifySameMessageAggregate(napi_env env, napi_callback_info info) { return sm_async(env, info, 3); }
-static napi_value VerifySameMessageAggregateSync(napi_env env, napi_callback_info info) { return sm_sync(env, info, 3); }
-static napi_value VerifySameMessageBits(napi_env env, napi_callback_info info) { return sm_async(env, info, 2); }
-static napi_value VerifySameMessageBitsSync(napi_env env, napi_callback_info info) { return sm_sync(env, info, 2); }
-
-/* ------------------------------------------------------- committee bitfields
- * verifyBits(ctx, batch) -> Promise<result>, verifyBitsSync(ctx, batch) -> result (bgv_verify_bits).
- * batch = {jobOffsets: Uint32Array, src: Uint32Array (4 per set: list, off, len, bitsOff; list 0xffffffff = an
- * explicit run pkIndices[off .. off + len)), bits: Uint8Array (all bitfields, byte-packed, SSZ bit order),
- * pkIndices: Uint32Array (keys of the explicit sets), msgs, sigs, sigLen, rawPks? as for verify}.
- * result as for verify.  jobOffsets and src are copied at call time; the library stages every array into pinned
- * memory and checks the copy against the lengths taken here, so a caller that mutates its arrays while the work
- * is queued cannot make the device read past them. */
-static const char* BFIELD[NB_FIELDS] = {"jobOffsets", "src", "bits", "pkIndices", "msgs", "sigs", "sigLen", "rawPks"};
-static const napi_typedarray_type BFIELD_T[NB_FIELDS] = {napi_uint32_array, napi_uint32_array, napi_uint8_array,  napi_uint32_array,
-                                                         napi_uint8_array,  napi_uint8_array,  napi_uint32_array, napi_uint8_array};
-
-static int read_bits_batch(napi_env env, napi_value obj, verify_job* j, int pin) {
-  void* p[NB_FIELDS] = {0};
-  size_t n[NB_FIELDS] = {0};
-  napi_value v[NB_FIELDS];
-  for (int k = 0; k < NB_FIELDS; k++) {
-    bool has = false;
-    napi_has_named_property(env, obj, BFIELD[k], &has);
-    if (!has) {
-      if (k == B_RAW) continue;
-      napi_throw_type_error(env, NULL, "bits batch field missing");
-      return -1;
-    }
-    napi_get_named_property(env, obj, BFIELD[k], &v[k]);
-    if (typed(env, v[k], BFIELD_T[k], &p[k], &n[k])) {
-      napi_throw_type_error(env, NULL, "bits batch field has the wrong typed-array type");
-      return -1;
-    }
-  }
-  if (n[B_JOB] < 1 || n[B_SRC] % 4) {
-    napi_throw_range_error(env, NULL, "jobOffsets needs at least one entry, src four entries per set");
-    return -1;
-  }
-  const size_t n_sets = n[B_SRC] / 4;
-  if (n[B_MSG] < 32ull * n_sets || n[B_SIG] < 192ull * n_sets || n[B_LEN] < n_sets) {
-    napi_throw_range_error(env, NULL, "msgs / sigs / sigLen shorter than the set count");
-    return -1;
-  }
-  if (n_sets > 0xffffffffull || n[B_BITS] > 0xffffffffull || n[B_PKI] > 0xffffffffull) {
-    napi_throw_range_error(env, NULL, "bits batch too large");
-    return -1;
-  }
-  j->job_off = (uint32_t*)malloc(4 * n[B_JOB]);
-  j->src_copy = (uint32_t*)malloc(n[B_SRC] ? 4 * n[B_SRC] : 4);
-  if (!j->job_off || !j->src_copy) {
-    napi_throw_error(env, NULL, "out of memory");
-    return -1;
-  }
-  memcpy(j->job_off, p[B_JOB], 4 * n[B_JOB]);
-  if (n[B_SRC]) memcpy(j->src_copy, p[B_SRC], 4 * n[B_SRC]);
-  if (pin)
-    for (int k = 0; k < NB_FIELDS; k++)
-      if (p[k] && k != B_JOB && k != B_SRC) napi_create_reference(env, v[k], 1, &j->brefs[k]);
-  memset(&j->bb, 0, sizeof j->bb);
-  j->bb.n_sets = (uint32_t)n_sets;
-  j->bb.n_jobs = (uint32_t)(n[B_JOB] - 1);
-  j->bb.job_offsets = j->job_off;
-  j->bb.src = (const bgv_set_src*)j->src_copy;
-  j->bb.bits = (const uint8_t*)p[B_BITS];
-  j->bb.bits_len = (uint32_t)n[B_BITS];
-  j->bb.pk_indices = (const uint32_t*)p[B_PKI];
-  j->bb.n_indices = (uint32_t)n[B_PKI];
-  j->bb.raw_pks = (const uint8_t*)p[B_RAW];
-  j->bb.n_raw = (uint32_t)(n[B_RAW] / 96);
-  j->bb.msgs = (const uint8_t*)p[B_MSG];
-  j->bb.sigs = (const uint8_t*)p[B_SIG];
-  j->bb.sig_len = (const uint32_t*)p[B_LEN];
-  j->bb.scalars = NULL; /* drawn inside the library */
-  j->bb.on_device = 0;
-  j->b.n_jobs = j->bb.n_jobs; /* result_object sizes `results` from it */
-  j->b.n_sets = j->bb.n_sets;
-  return 0;
-}
-
-static napi_value VerifyBits(napi_env env, napi_callback_info info) {
-  size_t argc = 2;
-  napi_value a[2];
-  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, a, NULL, NULL));
-  addon_ctx* c = get_ctx(env, a[0]);
-  if (!c) return NULL;
-  verify_job* j = (verify_job*)calloc(1, sizeof *j);
   j->c = c;
-  j->kind = K_BITS;
-  if (read_bits_batch(env, a[1], j, 1)) {
-    for (int k = 0; k < NB_FIELDS; k++)
-      if (j->brefs[k]) napi_delete_reference(env, j->brefs[k]);
-    free_job_arrays(j);
-    free(j);
-    return NULL;
+  j->kind = kind;
+  if (kind == K_COMBINE) {
+    void* data;
+    size_t len;
+    if (argc < 2 || typed(env, a[1], napi_uint8_array, &data, &len) || len % 576) {
+      napi_throw_type_error(env, NULL, "combineFinal(ctx, Uint8Array of 576-byte partials)");
+    } else if (!(j->own[O_PARTS] = malloc(len ? len : 1))) { /* copied: the caller may reuse its buffer */
+      oom(env);
+    } else {
+      if (len) memcpy(j->own[O_PARTS], data, len);
+      j->n_parts = (uint32_t)(len / 576);
+      return job_queue(env, a[0], j);
+    }
+  } else if (!KIND[kind].read || !KIND[kind].read(env, a[1], j, !sync)) {
+    if (!sync) return job_queue(env, a[0], j);
+    r = job_sync(env, j);
   }
-  j->job_result = (int32_t*)calloc(j->b.n_jobs ? j->b.n_jobs : 1, 4);
-  return queue_job(env, a[0], j, "bgv_verify_bits");
-}
-
-static napi_value VerifyBitsSync(napi_env env, napi_callback_info info) {
-  size_t argc = 2;
-  napi_value a[2];
-  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, a, NULL, NULL));
-  addon_ctx* c = get_ctx(env, a[0]);
-  if (!c) return NULL;
-  verify_job j;
-  memset(&j, 0, sizeof j);
-  j.c = c;
-  j.kind = K_BITS;
-  if (read_bits_batch(env, a[1], &j, 0)) {
-    free_job_arrays(&j);
-    return NULL;
-  }
-  j.job_result = (int32_t*)calloc(j.b.n_jobs ? j.b.n_jobs : 1, 4);
-  run_verify(&j);
-  napi_value r = NULL;
-  if (j.status != BGV_OK) napi_throw_error(env, NULL, j.err);
-  else r = result_object(env, &j);
-  free_job_arrays(&j);
+  job_free(env, j);
+  free(j);
   return r;
 }
 
+static napi_value Verify(napi_env env, napi_callback_info info) { return job_entry(env, info, K_VERIFY, 0); }
+static napi_value VerifySync(napi_env env, napi_callback_info info) { return job_entry(env, info, K_VERIFY, 1); }
+static napi_value Partial(napi_env env, napi_callback_info info) { return job_entry(env, info, K_PARTIAL, 0); }
+/* partialFinish(ctx): the shard left by the last partial() on the context */
+static napi_value PartialFinish(napi_env env, napi_callback_info info) { return job_entry(env, info, K_FINISH, 0); }
+static napi_value CombineFinal(napi_env env, napi_callback_info info) { return job_entry(env, info, K_COMBINE, 0); }
+static napi_value VerifyBits(napi_env env, napi_callback_info info) { return job_entry(env, info, K_BITS, 0); }
+static napi_value VerifyBitsSync(napi_env env, napi_callback_info info) { return job_entry(env, info, K_BITS, 1); }
+static napi_value VerifySameMessage(napi_env env, napi_callback_info info) { return job_entry(env, info, K_SM, 0); }
+static napi_value VerifySameMessageSync(napi_env env, napi_callback_info info) { return job_entry(env, info, K_SM, 1); }
+static napi_value VerifySameMessageAgg(napi_env env, napi_callback_info info) { return job_entry(env, info, K_SMA, 0); }
+static napi_value VerifySameMessageAggSync(napi_env env, napi_callback_info info) { return job_entry(env, info, K_SMA, 1); }
+static napi_value VerifySameMessageAggregate(napi_env env, napi_callback_info info) { return job_entry(env, info, K_SM_AGGREGATE, 0); }
+static napi_value VerifySameMessageAggregateSync(napi_env env, napi_callback_info info) { return job_entry(env, info, K_SM_AGGREGATE, 1); }
+static napi_value VerifySameMessageBits(napi_env env, napi_callback_info info) { return job_entry(env, info, K_SMB, 0); }
+static napi_value VerifySameMessageBitsSync(napi_env env, napi_callback_info info) { return job_entry(env, info, K_SMB, 1); }
+
+/* ------------------------------------------------- index lists and counters */
 static napi_value SetIndexList(napi_env env, napi_callback_info info) {
-  size_t argc = 3;
-  napi_value a[3];
-  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, a, NULL, NULL));
-  addon_ctx* c = get_ctx(env, a[0]);
-  if (!c) return NULL;
+  CTX_ARGS(3);
   uint32_t id = 0;
   void* data = NULL;
   size_t len = 0;
@@ -1165,24 +891,18 @@ static napi_value SetIndexList(napi_env env, napi_callback_info info) {
     napi_throw_type_error(env, NULL, "setIndexList(ctx, id, Uint32Array)");
     return NULL;
   }
-  pthread_mutex_lock(&c->mu); /* waits for the context's batch in flight */
-  const int st = bgv_index_list_set(c->ctx, id, (const uint32_t*)data, (uint32_t)len);
-  pthread_mutex_unlock(&c->mu);
+  int st;
+  LOCKED(c, st, bgv_index_list_set(c->ctx, id, (const uint32_t*)data, (uint32_t)len));
   if (st != BGV_OK) return throw_bgv(env, st);
   return NULL;
 }
 
 static napi_value IndexListLen(napi_env env, napi_callback_info info) {
-  size_t argc = 2;
-  napi_value a[2];
-  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, a, NULL, NULL));
-  addon_ctx* c = get_ctx(env, a[0]);
-  if (!c) return NULL;
+  CTX_ARGS(2);
   uint32_t id = 0, n = 0;
   NAPI_CALL(env, napi_get_value_uint32(env, a[1], &id));
-  pthread_mutex_lock(&c->mu);
-  const int st = bgv_index_list_len(c->ctx, id, &n);
-  pthread_mutex_unlock(&c->mu);
+  int st;
+  LOCKED(c, st, bgv_index_list_len(c->ctx, id, &n));
   if (st != BGV_OK) return throw_bgv(env, st);
   napi_value r;
   NAPI_CALL(env, napi_create_uint32(env, n, &r));
@@ -1190,35 +910,25 @@ static napi_value IndexListLen(napi_env env, napi_callback_info info) {
 }
 
 static napi_value SetIndexListSums(napi_env env, napi_callback_info info) {
-  size_t argc = 3;
-  napi_value a[3];
-  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, a, NULL, NULL));
-  addon_ctx* c = get_ctx(env, a[0]);
-  if (!c) return NULL;
+  CTX_ARGS(3);
   uint32_t id = 0;
   bool enable = false;
   if (argc < 3 || napi_get_value_uint32(env, a[1], &id) != napi_ok || napi_get_value_bool(env, a[2], &enable) != napi_ok) {
     napi_throw_type_error(env, NULL, "setIndexListSums(ctx, id, boolean)");
     return NULL;
   }
-  pthread_mutex_lock(&c->mu); /* waits for the context's batch in flight */
-  const int st = bgv_index_list_sums(c->ctx, id, enable ? 1u : 0u);
-  pthread_mutex_unlock(&c->mu);
+  int st;
+  LOCKED(c, st, bgv_index_list_sums(c->ctx, id, enable ? 1u : 0u));
   if (st != BGV_OK) return throw_bgv(env, st);
   return NULL;
 }
 
 static napi_value IndexListHasSums(napi_env env, napi_callback_info info) {
-  size_t argc = 2;
-  napi_value a[2];
-  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, a, NULL, NULL));
-  addon_ctx* c = get_ctx(env, a[0]);
-  if (!c) return NULL;
+  CTX_ARGS(2);
   uint32_t id = 0, has = 0;
   NAPI_CALL(env, napi_get_value_uint32(env, a[1], &id));
-  pthread_mutex_lock(&c->mu);
-  const int st = bgv_index_list_has_sums(c->ctx, id, &has);
-  pthread_mutex_unlock(&c->mu);
+  int st;
+  LOCKED(c, st, bgv_index_list_has_sums(c->ctx, id, &has));
   if (st != BGV_OK) return throw_bgv(env, st);
   napi_value r;
   NAPI_CALL(env, napi_get_boolean(env, has != 0, &r));
@@ -1227,83 +937,47 @@ static napi_value IndexListHasSums(napi_env env, napi_callback_info info) {
 
 /* hashStats(ctx): bgv_hash_stats of the context's last ordinary batch (the sync paths read it after the call) */
 static napi_value HashStats(napi_env env, napi_callback_info info) {
-  size_t argc = 1;
-  napi_value a[1];
-  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, a, NULL, NULL));
-  addon_ctx* c = get_ctx(env, a[0]);
-  if (!c) return NULL;
+  CTX_ARGS(1);
   bgv_hash_path p;
-  pthread_mutex_lock(&c->mu);
-  const int st = bgv_hash_stats(c->ctx, &p);
-  pthread_mutex_unlock(&c->mu);
+  int st;
+  LOCKED(c, st, bgv_hash_stats(c->ctx, &p));
   if (st != BGV_OK) return throw_bgv(env, st);
-  napi_value r, v;
-  NAPI_CALL(env, napi_create_object(env, &r));
-  NAPI_CALL(env, napi_create_uint32(env, p.sets, &v));
-  NAPI_CALL(env, napi_set_named_property(env, r, "sets", v));
-  NAPI_CALL(env, napi_create_uint32(env, p.hashes, &v));
-  NAPI_CALL(env, napi_set_named_property(env, r, "hashes", v));
-  NAPI_CALL(env, napi_create_uint32(env, p.dedup, &v));
-  NAPI_CALL(env, napi_set_named_property(env, r, "dedup", v));
-  return r;
-}
-
-/* pairMerge(ctx, on): bgv_pair_merge (a boolean, or 0 / 1; any other number is refused by the library) */
-static napi_value PairMerge(napi_env env, napi_callback_info info) {
-  size_t argc = 2;
-  napi_value a[2];
-  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, a, NULL, NULL));
-  addon_ctx* c = get_ctx(env, a[0]);
-  if (!c) return NULL;
-  int32_t mode = 0;
-  napi_valuetype t = napi_undefined;
-  if (argc >= 2) NAPI_CALL(env, napi_typeof(env, a[1], &t));
-  if (t == napi_boolean) {
-    bool on = false;
-    NAPI_CALL(env, napi_get_value_bool(env, a[1], &on));
-    mode = on ? 1 : 0;
-  } else {
-    NAPI_CALL(env, napi_get_value_int32(env, a[1], &mode));
-  }
-  pthread_mutex_lock(&c->mu);
-  const int st = bgv_pair_merge(c->ctx, mode);
-  pthread_mutex_unlock(&c->mu);
-  if (st != BGV_OK) return throw_bgv(env, st);
-  return NULL;
+  return SET_U32S(env, NULL, {"sets", p.sets}, {"hashes", p.hashes}, {"dedup", p.dedup});
 }
 
 /* pairStats(ctx): bgv_pair_stats of the context's last ordinary batch */
 static napi_value PairStats(napi_env env, napi_callback_info info) {
-  size_t argc = 1;
-  napi_value a[1];
-  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, a, NULL, NULL));
-  addon_ctx* c = get_ctx(env, a[0]);
-  if (!c) return NULL;
+  CTX_ARGS(1);
   bgv_pair_path p;
-  pthread_mutex_lock(&c->mu);
-  const int st = bgv_pair_stats(c->ctx, &p);
-  pthread_mutex_unlock(&c->mu);
+  int st;
+  LOCKED(c, st, bgv_pair_stats(c->ctx, &p));
   if (st != BGV_OK) return throw_bgv(env, st);
-  napi_value r, v;
-  NAPI_CALL(env, napi_create_object(env, &r));
-  NAPI_CALL(env, napi_create_uint32(env, p.sets, &v));
-  NAPI_CALL(env, napi_set_named_property(env, r, "sets", v));
-  NAPI_CALL(env, napi_create_uint32(env, p.pairs, &v));
-  NAPI_CALL(env, napi_set_named_property(env, r, "pairs", v));
-  NAPI_CALL(env, napi_create_uint32(env, p.merged, &v));
-  NAPI_CALL(env, napi_set_named_property(env, r, "merged", v));
-  NAPI_CALL(env, napi_create_uint32(env, p.fallback, &v));
-  NAPI_CALL(env, napi_set_named_property(env, r, "fallback", v));
-  return r;
+  return SET_U32S(env, NULL, {"sets", p.sets}, {"pairs", p.pairs}, {"merged", p.merged}, {"fallback", p.fallback});
 }
 
-/* smRetry(ctx, mode): bgv_sm_retry (a boolean, or 0 / 1; any other number is refused by the library) */
-static napi_value SmRetry(napi_env env, napi_callback_info info) {
-  size_t argc = 2;
-  napi_value a[2];
-  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, a, NULL, NULL));
-  addon_ctx* c = get_ctx(env, a[0]);
-  if (!c) return NULL;
+/* smRetryStats(ctx): bgv_sm_retry_stats of the context's last same-message call */
+static napi_value SmRetryStats(napi_env env, napi_callback_info info) {
+  CTX_ARGS(1);
+  bgv_sm_retry_path p;
+  int st;
+  LOCKED(c, st, bgv_sm_retry_stats(c->ctx, &p));
+  if (st != BGV_OK) return throw_bgv(env, st);
+  return SET_U32S(env, NULL, {"mode", p.mode}, {"segments", p.segments}, {"subs", p.subs}, {"subsFailed", p.subs_failed},
+                  {"leaves", p.leaves}, {"pairs", p.pairs}, {"hashes", p.hashes});
+}
+
+static napi_value BitsPathStats(napi_env env, napi_callback_info info) {
+  CTX_ARGS(1);
+  bgv_bits_path p;
+  int st;
+  LOCKED(c, st, bgv_bits_path_stats(c->ctx, &p));
+  if (st != BGV_OK) return throw_bgv(env, st);
+  return SET_U32S(env, NULL, {"setsComplement", p.sets_complement}, {"keysExpanded", p.keys_expanded}, {"keysGathered", p.keys_gathered});
+}
+
+/* (ctx, mode) for a library switch: a boolean, or 0 / 1; any other number is refused by the library */
+static napi_value set_mode(napi_env env, napi_callback_info info, int (*apply)(bgv_ctx*, int32_t)) {
+  CTX_ARGS(2);
   int32_t mode = 0;
   napi_valuetype t = napi_undefined;
   if (argc >= 2) NAPI_CALL(env, napi_typeof(env, a[1], &t));
@@ -1314,58 +988,16 @@ static napi_value SmRetry(napi_env env, napi_callback_info info) {
   } else {
     NAPI_CALL(env, napi_get_value_int32(env, a[1], &mode));
   }
-  pthread_mutex_lock(&c->mu);
-  const int st = bgv_sm_retry(c->ctx, mode);
-  pthread_mutex_unlock(&c->mu);
+  int st;
+  LOCKED(c, st, apply(c->ctx, mode));
   if (st != BGV_OK) return throw_bgv(env, st);
   return NULL;
 }
 
-/* smRetryStats(ctx): bgv_sm_retry_stats of the context's last same-message call */
-static napi_value SmRetryStats(napi_env env, napi_callback_info info) {
-  size_t argc = 1;
-  napi_value a[1];
-  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, a, NULL, NULL));
-  addon_ctx* c = get_ctx(env, a[0]);
-  if (!c) return NULL;
-  bgv_sm_retry_path p;
-  pthread_mutex_lock(&c->mu);
-  const int st = bgv_sm_retry_stats(c->ctx, &p);
-  pthread_mutex_unlock(&c->mu);
-  if (st != BGV_OK) return throw_bgv(env, st);
-  const struct { const char* name; uint32_t val; } u[] = {
-      {"mode", p.mode}, {"segments", p.segments}, {"subs", p.subs}, {"subsFailed", p.subs_failed},
-      {"leaves", p.leaves}, {"pairs", p.pairs}, {"hashes", p.hashes}};
-  napi_value r, v;
-  NAPI_CALL(env, napi_create_object(env, &r));
-  for (size_t k = 0; k < sizeof u / sizeof u[0]; k++) {
-    NAPI_CALL(env, napi_create_uint32(env, u[k].val, &v));
-    NAPI_CALL(env, napi_set_named_property(env, r, u[k].name, v));
-  }
-  return r;
-}
-
-static napi_value BitsPathStats(napi_env env, napi_callback_info info) {
-  size_t argc = 1;
-  napi_value a[1];
-  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, a, NULL, NULL));
-  addon_ctx* c = get_ctx(env, a[0]);
-  if (!c) return NULL;
-  bgv_bits_path p;
-  pthread_mutex_lock(&c->mu);
-  const int st = bgv_bits_path_stats(c->ctx, &p);
-  pthread_mutex_unlock(&c->mu);
-  if (st != BGV_OK) return throw_bgv(env, st);
-  napi_value r, v;
-  NAPI_CALL(env, napi_create_object(env, &r));
-  NAPI_CALL(env, napi_create_uint32(env, p.sets_complement, &v));
-  NAPI_CALL(env, napi_set_named_property(env, r, "setsComplement", v));
-  NAPI_CALL(env, napi_create_uint32(env, p.keys_expanded, &v));
-  NAPI_CALL(env, napi_set_named_property(env, r, "keysExpanded", v));
-  NAPI_CALL(env, napi_create_uint32(env, p.keys_gathered, &v));
-  NAPI_CALL(env, napi_set_named_property(env, r, "keysGathered", v));
-  return r;
-}
+/* pairMerge(ctx, on): bgv_pair_merge */
+static napi_value PairMerge(napi_env env, napi_callback_info info) { return set_mode(env, info, bgv_pair_merge); }
+/* smRetry(ctx, mode): bgv_sm_retry */
+static napi_value SmRetry(napi_env env, napi_callback_info info) { return set_mode(env, info, bgv_sm_retry); }
 
 static napi_value Init(napi_env env, napi_value exports) {
   napi_property_descriptor d[] = {

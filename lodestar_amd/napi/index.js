@@ -129,23 +129,29 @@ function chunkifyMaximizeChunkSize(arr, minPerChunk) {
   return out;
 }
 
+// the bitfield-length refusal of a committee set, made by the caller-side checks and again by the encoders
+function bitfieldLengthError(s) {
+  return Error(`committee set: ${s.bits.length} bitfield bytes for ${s.committee.length} members`);
+}
+
+// the caller-side checks of one committee set ({committee: {list, offset, length}, bits, ...})
+function checkCommitteeSet(s) {
+  const c = s.committee;
+  if (!c || !s.bits || !(c.list >= 0 && c.list < MAX_INDEX_LISTS)) throw Error("committee set without a committee, bits or a valid list id");
+  if (!(c.offset >= 0) || !(c.length >= 0) || c.offset + c.length > 0xffffffff || s.bits.length !== ((c.length + 7) >> 3)) throw bitfieldLengthError(s);
+  if (!s.bits.some((b) => b !== 0)) throw Error("EMPTY_AGGREGATE_ARRAY"); // intersectValues gives no index
+}
+
 // the caller-side checks of getAggregatedPubkey (chain/bls/utils.ts:5-16),
 // made before queueing so a bad call cannot fail a batch it shares
 function checkSets(sets) {
   for (const s of sets) {
-    if (s.type === "committee") {
-      const c = s.committee;
-      if (!c || !s.bits || !(c.list >= 0 && c.list < MAX_INDEX_LISTS)) throw Error("committee set without a committee, bits or a valid list id");
-      if (!(c.offset >= 0) || !(c.length >= 0) || c.offset + c.length > 0xffffffff || s.bits.length !== ((c.length + 7) >> 3)) {
-        throw Error(`committee set: ${s.bits.length} bitfield bytes for ${c.length} members`);
-      }
-      if (!s.bits.some((b) => b !== 0)) throw Error("EMPTY_AGGREGATE_ARRAY"); // intersectValues gives no index
-      if (!s.signingRoot || s.signingRoot.length !== 32) throw Error("signingRoot must be 32 bytes");
-      continue;
+    if (s.type === "committee") checkCommitteeSet(s);
+    else {
+      const pks = s.type === "single" ? [s.pubkey] : s.pubkeys;
+      if (!pks || pks.length === 0 || pks.some((pk) => !pk)) throw Error("EMPTY_AGGREGATE_ARRAY");
+      for (const pk of pks) if (pk.raw && pk.raw.length !== 96) throw Error("raw pubkeys must be 96-byte uncompressed");
     }
-    const pks = s.type === "single" ? [s.pubkey] : s.pubkeys;
-    if (!pks || pks.length === 0 || pks.some((pk) => !pk)) throw Error("EMPTY_AGGREGATE_ARRAY");
-    for (const pk of pks) if (pk.raw && pk.raw.length !== 96) throw Error("raw pubkeys must be 96-byte uncompressed");
     if (!s.signingRoot || s.signingRoot.length !== 32) throw Error("signingRoot must be 32 bytes");
   }
 }
@@ -180,55 +186,152 @@ function hasCommitteeSets(jobs) {
   return jobs.some((j) => j.some((s) => s.type === "committee"));
 }
 
-// jobs -> the arrays of include/bgv.h bgv_bits_batch: single and aggregate sets
-// become explicit sources over pkIndices, committee sets
-// ({type: "committee", committee: {list, offset, length}, bits, signingRoot, signature})
-// list sources over the byte-packed bitfields.  src holds 4 words per set:
-// list, off, len, bitsOff.
-function encodeJobsBits(jobs) {
-  let n = 0, nIdx = 0, nRaw = 0, nBits = 0;
-  for (const j of jobs) {
-    n += j.length;
-    for (const s of j) {
-      if (s.type === "committee") { nBits += s.bits.length; continue; }
-      const pks = s.type === "single" ? [s.pubkey] : s.pubkeys;
-      if (!pks || pks.length === 0) throw Error("EMPTY_AGGREGATE_ARRAY");
-      nIdx += pks.length;
-      for (const pk of pks) if (pk.raw) nRaw++;
+// The one encoder behind the five encode* functions: the typed arrays of a bgv_*_batch (include/bgv.h) from a walk
+// over the caller's sets.  The walk runs twice, first to count, then, over arrays allocated once, to fill: a 2^17-set
+// batch allocates its arrays once instead of growing JS arrays of up to ~17M indices, which kept the main thread in
+// the garbage collector.  outer names the offsets that close a job or a group; keys says how a set names its keys:
+// "single" (one key per set), "offsets" (a run of pkIndices closed by pkOffsets) or "sources" (src: 4 words per set,
+// list, off, len, bitsOff: an explicit run of pkIndices, or a list source over the byte-packed bitfields).
+class BatchWriter {
+  constructor(outer, keys) {
+    this.outer = outer;
+    this.keys = keys;
+    this.filling = false;
+    this.n = this.nOuter = this.nMsgs = this.nKeys = this.nRaw = this.nBits = 0;
+    this.offsets = this.pkOffsets = this.src = this.bits = this.pkIndices = this.msgs = this.sigs = this.sigLen = this.rawPks = null;
+  }
+
+  allocate() {
+    // zero sizes are padded to one entry, except the arrays only the "sources" layout measures by its own counts
+    const some = (x) => Math.max(x, 1);
+    const sources = this.keys === "sources";
+    this.offsets = new Uint32Array(this.nOuter + 1);
+    this.pkOffsets = this.keys === "offsets" ? new Uint32Array(this.n + 1) : null;
+    this.src = sources ? new Uint32Array(4 * this.n) : null;
+    this.bits = sources ? new Uint8Array(this.nBits) : null;
+    this.pkIndices = new Uint32Array(sources ? this.nKeys : some(this.nKeys));
+    this.msgs = new Uint8Array(some(this.nMsgs) * 32);
+    this.sigs = new Uint8Array(some(this.n) * 192);
+    this.sigLen = new Uint32Array(some(this.n));
+    this.rawPks = new Uint8Array(some(this.nRaw) * 96);
+    this.n = this.nOuter = this.nMsgs = this.nKeys = this.nRaw = this.nBits = 0;
+    this.filling = true;
+  }
+
+  // the four src words of the current set
+  source(list, off, len, bitsOff) {
+    const src = this.src;
+    const o = 4 * this.n;
+    src[o] = list;
+    src[o + 1] = off;
+    src[o + 2] = len;
+    src[o + 3] = bitsOff;
+  }
+
+  // one key of the current set: {index}, {raw}, or (numbers: the two publicKeys encoders only) a validator index
+  key(pk, numbers) {
+    const number = numbers && typeof pk === "number";
+    const raw = !number && pk.raw;
+    if (!this.filling) {
+      this.nKeys++;
+      if (raw) this.nRaw++;
+    } else if (raw) {
+      this.pkIndices[this.nKeys++] = (RAW_BIT | this.nRaw) >>> 0;
+      this.rawPks.set(raw, 96 * this.nRaw++);
+    } else {
+      this.pkIndices[this.nKeys++] = (number ? pk : pk.index) >>> 0;
     }
   }
-  const jobOffsets = new Uint32Array(jobs.length + 1);
-  const src = new Uint32Array(4 * n);
-  const bits = new Uint8Array(nBits);
-  const pkIndices = new Uint32Array(nIdx);
-  const rawPks = new Uint8Array(Math.max(nRaw, 1) * 96);
-  const msgs = new Uint8Array(Math.max(n, 1) * 32);
-  const sigs = new Uint8Array(Math.max(n, 1) * 192);
-  const sigLen = new Uint32Array(Math.max(n, 1));
-  let i = 0, x = 0, r = 0, b = 0;
-  jobs.forEach((job, k) => {
-    for (const s of job) {
-      if (s.type === "committee") {
-        const c = s.committee;
-        if (s.bits.length !== ((c.length + 7) >> 3)) throw Error(`committee set: ${s.bits.length} bitfield bytes for ${c.length} members`);
-        src.set([c.list, c.offset, c.length, b], 4 * i);
-        bits.set(s.bits, b);
-        b += s.bits.length;
-      } else {
-        const pks = s.type === "single" ? [s.pubkey] : s.pubkeys;
-        src.set([SRC_EXPLICIT, x, pks.length, 0], 4 * i);
-        for (const pk of pks) {
-          if (pk.raw) { pkIndices[x++] = (RAW_BIT | r) >>> 0; rawPks.set(pk.raw, 96 * r++); } else pkIndices[x++] = pk.index >>> 0;
-        }
-      }
-      msgs.set(s.signingRoot, 32 * i);
-      sigLen[i] = s.signature.length;
-      if (s.signature.length === 96 || s.signature.length === 192) sigs.set(s.signature, 192 * i);
-      i++;
+
+  // a set's run of keys
+  run(pks, numbers) {
+    if (pks.length === 0) throw Error("EMPTY_AGGREGATE_ARRAY"); // PublicKey.aggregate, utils.ts:11
+    if (this.filling && this.src) this.source(SRC_EXPLICIT, this.nKeys, pks.length, 0);
+    for (const pk of pks) this.key(pk, numbers);
+  }
+
+  // a set's committee source ({committee: {list, offset, length}, bits})
+  committee(s) {
+    if (this.filling) {
+      const c = s.committee;
+      if (s.bits.length !== ((c.length + 7) >> 3)) throw bitfieldLengthError(s);
+      this.source(c.list, c.offset, c.length, this.nBits);
+      this.bits.set(s.bits, this.nBits);
     }
-    jobOffsets[k + 1] = i;
+    this.nBits += s.bits.length;
+  }
+
+  // the signing root of the set (jobs) or of the group
+  message(root) {
+    if (this.filling) this.msgs.set(root, 32 * this.nMsgs);
+    this.nMsgs++;
+  }
+
+  // the set's signature closes the set; one of another size than 96 or 192 leaves its slot zero (sigLen tells)
+  signature(sig) {
+    if (this.filling) {
+      this.sigLen[this.n] = sig.length;
+      if (sig.length === 96 || sig.length === 192) this.sigs.set(sig, 192 * this.n);
+      if (this.pkOffsets) this.pkOffsets[this.n + 1] = this.nKeys;
+    }
+    this.n++;
+  }
+
+  // closes the job or group
+  close() {
+    this.nOuter++;
+    if (this.filling) this.offsets[this.nOuter] = this.n;
+  }
+
+  // the batch, its keys in the order of the bgv_*_batch fields
+  batch() {
+    const {pkOffsets, src, bits, pkIndices, msgs, sigs, sigLen, rawPks} = this;
+    const head = {[this.outer]: this.offsets};
+    if (pkOffsets) return {...head, pkOffsets, pkIndices, msgs, sigs, sigLen, rawPks};
+    if (src) return {...head, src, bits, pkIndices, msgs, sigs, sigLen, rawPks};
+    return {...head, pkIndices, msgs, sigs, sigLen, rawPks};
+  }
+}
+
+function encodeBatch(outer, keys, walk) {
+  const w = new BatchWriter(outer, keys);
+  walk(w);
+  w.allocate();
+  walk(w);
+  return w.batch();
+}
+
+// jobs (arrays of sets) -> the SoA batch of include/bgv.h bgv_batch ("offsets") or, where a batch holds committee
+// sets ({type: "committee", committee: {list, offset, length}, bits, signingRoot, signature}), bgv_bits_batch ("sources")
+function encodeJobSets(jobs, keys) {
+  return encodeBatch("jobOffsets", keys, (w) => {
+    for (const job of jobs) {
+      for (const s of job) {
+        if (keys === "sources" && s.type === "committee") w.committee(s);
+        else w.run((s.type === "single" ? [s.pubkey] : s.pubkeys) || [], false);
+        w.message(s.signingRoot);
+        w.signature(s.signature);
+      }
+      w.close();
+    }
   });
-  return {jobOffsets, src, bits, pkIndices, msgs, sigs, sigLen, rawPks};
+}
+const encodeJobs = (jobs) => encodeJobSets(jobs, "offsets");
+const encodeJobsBits = (jobs) => encodeJobSets(jobs, "sources");
+
+// groups [{message, sets}] -> the arrays of a same-message batch; `set` names the keys of one set
+function encodeGroups(groups, keys, set) {
+  return encodeBatch("groupOffsets", keys, (w) => {
+    for (const g of groups) {
+      if (g.sets.length === 0) throw Error("Empty signature set");
+      w.message(g.message);
+      for (const s of g.sets) {
+        set(w, s);
+        w.signature(s.signature);
+      }
+      w.close();
+    }
+  });
 }
 
 // The routing rule of both classes: a device batch that holds a committee set
@@ -236,50 +339,6 @@ function encodeJobsBits(jobs) {
 function verifyJobs(ctx, jobSets, sync = false) {
   if (hasCommitteeSets(jobSets)) return (sync ? addon.verifyBitsSync : addon.verifyBits)(ctx, encodeJobsBits(jobSets));
   return (sync ? addon.verifySync : addon.verify)(ctx, encodeJobs(jobSets));
-}
-
-// jobs (arrays of sets) -> the SoA batch of include/bgv.h bgv_batch.  Two
-// passes (count, then fill typed arrays): a 2^17-set batch allocates its
-// arrays once instead of growing JS arrays of up to ~17M indices, which kept
-// the main thread in the garbage collector
-function encodeJobs(jobs) {
-  let n = 0, nIdx = 0, nRaw = 0;
-  for (const j of jobs) {
-    n += j.length;
-    for (const s of j) {
-      const pks = s.type === "single" ? [s.pubkey] : s.pubkeys;
-      if (!pks || pks.length === 0) throw Error("EMPTY_AGGREGATE_ARRAY"); // PublicKey.aggregate, utils.ts:11
-      nIdx += pks.length;
-      for (const pk of pks) if (pk.raw) nRaw++;
-    }
-  }
-  const jobOffsets = new Uint32Array(jobs.length + 1);
-  const pkOffsets = new Uint32Array(n + 1);
-  const pkIndices = new Uint32Array(Math.max(nIdx, 1));
-  const rawPks = new Uint8Array(Math.max(nRaw, 1) * 96);
-  const msgs = new Uint8Array(Math.max(n, 1) * 32);
-  const sigs = new Uint8Array(Math.max(n, 1) * 192);
-  const sigLen = new Uint32Array(Math.max(n, 1));
-  let i = 0, x = 0, r = 0;
-  jobs.forEach((job, k) => {
-    for (const s of job) {
-      if (s.type === "single") {
-        const pk = s.pubkey;
-        if (pk.raw) { pkIndices[x++] = (RAW_BIT | r) >>> 0; rawPks.set(pk.raw, 96 * r++); } else pkIndices[x++] = pk.index >>> 0;
-      } else {
-        for (const pk of s.pubkeys) {
-          if (pk.raw) { pkIndices[x++] = (RAW_BIT | r) >>> 0; rawPks.set(pk.raw, 96 * r++); } else pkIndices[x++] = pk.index >>> 0;
-        }
-      }
-      pkOffsets[i + 1] = x;
-      msgs.set(s.signingRoot, 32 * i);
-      sigLen[i] = s.signature.length;
-      if (s.signature.length === 96 || s.signature.length === 192) sigs.set(s.signature, 192 * i);
-      i++;
-    }
-    jobOffsets[k + 1] = i;
-  });
-  return {jobOffsets, pkOffsets, pkIndices, msgs, sigs, sigLen, rawPks};
 }
 
 // the caller-side checks of one verifySignatureSetsSameMessage call, as checkSets makes them
@@ -351,7 +410,7 @@ function encodeAggregateSide(calls, merged, n) {
 // call, {valid, aggregate, count} for an aggregate call, or the Error that
 // rejects it alone (its `previous` did not decode)
 function aggregateCallResult(addonRef, call, res, where, g) {
-  const valid = Array.from(res.valid.subarray(where[0], where[1]), (v) => v === 1);
+  const valid = toBooleans(res.valid, where[0], where[1]);
   if (!call.agg) return valid;
   if (res.aggCode[g] !== 0) return Error(`BLST_ERROR: ${addonRef.codeName(res.aggCode[g])}`);
   return {valid, aggregate: res.aggSigs.slice(96 * g, 96 * g + 96), count: res.aggCount[g]};
@@ -359,31 +418,7 @@ function aggregateCallResult(addonRef, call, res, where, g) {
 
 // groups [{message, sets: [{publicKey, signature}]}] -> the arrays of include/bgv.h bgv_sm_batch
 function encodeSameMessage(groups) {
-  let n = 0, nRaw = 0;
-  for (const g of groups) {
-    if (g.sets.length === 0) throw Error("Empty signature set");
-    n += g.sets.length;
-    for (const s of g.sets) if (s.publicKey.raw) nRaw++;
-  }
-  const groupOffsets = new Uint32Array(groups.length + 1);
-  const pkIndices = new Uint32Array(Math.max(n, 1));
-  const rawPks = new Uint8Array(Math.max(nRaw, 1) * 96);
-  const msgs = new Uint8Array(Math.max(groups.length, 1) * 32);
-  const sigs = new Uint8Array(Math.max(n, 1) * 192);
-  const sigLen = new Uint32Array(Math.max(n, 1));
-  let i = 0, r = 0;
-  groups.forEach((g, k) => {
-    msgs.set(g.message, 32 * k);
-    for (const s of g.sets) {
-      const pk = s.publicKey;
-      if (pk.raw) { pkIndices[i] = (RAW_BIT | r) >>> 0; rawPks.set(pk.raw, 96 * r++); } else pkIndices[i] = pk.index >>> 0;
-      sigLen[i] = s.signature.length;
-      if (s.signature.length === 96 || s.signature.length === 192) sigs.set(s.signature, 192 * i);
-      i++;
-    }
-    groupOffsets[k + 1] = i;
-  });
-  return {groupOffsets, pkIndices, msgs, sigs, sigLen, rawPks};
+  return encodeGroups(groups, "single", (w, s) => w.key(s.publicKey, false));
 }
 
 // the caller-side checks of one verifyAggregateSetsSameMessage call: every set is
@@ -393,12 +428,7 @@ function checkAggregateSameMessage(sets, message) {
   if (!message || message.length !== 32) throw Error("signingRoot must be 32 bytes");
   for (const s of sets) {
     if (s && s.committee) {
-      const c = s.committee;
-      if (!s.bits || !(c.list >= 0 && c.list < MAX_INDEX_LISTS)) throw Error("committee set without a committee, bits or a valid list id");
-      if (!(c.offset >= 0) || !(c.length >= 0) || c.offset + c.length > 0xffffffff || s.bits.length !== ((c.length + 7) >> 3)) {
-        throw Error(`committee set: ${s.bits.length} bitfield bytes for ${c.length} members`);
-      }
-      if (!s.bits.some((b) => b !== 0)) throw Error("EMPTY_AGGREGATE_ARRAY");
+      checkCommitteeSet(s);
       continue;
     }
     if (!s || !s.publicKeys || s.publicKeys.length === 0) throw Error("EMPTY_AGGREGATE_ARRAY");
@@ -411,38 +441,7 @@ function checkAggregateSameMessage(sets, message) {
 
 // groups [{message, sets: [{publicKeys, signature}]}] -> the arrays of include/bgv.h bgv_sma_batch
 function encodeSameMessageAgg(groups) {
-  let n = 0, nKeys = 0, nRaw = 0;
-  for (const g of groups) {
-    if (g.sets.length === 0) throw Error("Empty signature set");
-    n += g.sets.length;
-    for (const s of g.sets) {
-      if (s.publicKeys.length === 0) throw Error("EMPTY_AGGREGATE_ARRAY");
-      nKeys += s.publicKeys.length;
-      for (const pk of s.publicKeys) if (typeof pk !== "number" && pk.raw) nRaw++;
-    }
-  }
-  const groupOffsets = new Uint32Array(groups.length + 1);
-  const pkOffsets = new Uint32Array(n + 1);
-  const pkIndices = new Uint32Array(Math.max(nKeys, 1));
-  const rawPks = new Uint8Array(Math.max(nRaw, 1) * 96);
-  const msgs = new Uint8Array(Math.max(groups.length, 1) * 32);
-  const sigs = new Uint8Array(Math.max(n, 1) * 192);
-  const sigLen = new Uint32Array(Math.max(n, 1));
-  let i = 0, k = 0, r = 0;
-  groups.forEach((g, gi) => {
-    msgs.set(g.message, 32 * gi);
-    for (const s of g.sets) {
-      for (const pk of s.publicKeys) {
-        if (typeof pk === "number") pkIndices[k++] = pk >>> 0;
-        else if (pk.raw) { pkIndices[k++] = (RAW_BIT | r) >>> 0; rawPks.set(pk.raw, 96 * r++); } else pkIndices[k++] = pk.index >>> 0;
-      }
-      sigLen[i] = s.signature.length;
-      if (s.signature.length === 96 || s.signature.length === 192) sigs.set(s.signature, 192 * i);
-      pkOffsets[++i] = k;
-    }
-    groupOffsets[gi + 1] = i;
-  });
-  return {groupOffsets, pkOffsets, pkIndices, msgs, sigs, sigLen, rawPks};
+  return encodeGroups(groups, "offsets", (w, s) => w.run(s.publicKeys, true));
 }
 
 function hasCommitteeKeys(groups) {
@@ -453,49 +452,37 @@ function hasCommitteeKeys(groups) {
 // {committee: {list, offset, length}, bits, signature} becomes a list source over the
 // byte-packed bitfields, a set {publicKeys, signature} a BGV_SRC_EXPLICIT run of pkIndices
 function encodeSameMessageBits(groups) {
-  let n = 0, nKeys = 0, nRaw = 0, nBits = 0;
-  for (const g of groups) {
-    if (g.sets.length === 0) throw Error("Empty signature set");
-    n += g.sets.length;
-    for (const s of g.sets) {
-      if (s.committee) { nBits += s.bits.length; continue; }
-      if (s.publicKeys.length === 0) throw Error("EMPTY_AGGREGATE_ARRAY");
-      nKeys += s.publicKeys.length;
-      for (const pk of s.publicKeys) if (typeof pk !== "number" && pk.raw) nRaw++;
-    }
-  }
-  const groupOffsets = new Uint32Array(groups.length + 1);
-  const src = new Uint32Array(4 * n);
-  const bits = new Uint8Array(nBits);
-  const pkIndices = new Uint32Array(nKeys);
-  const rawPks = new Uint8Array(Math.max(nRaw, 1) * 96);
-  const msgs = new Uint8Array(Math.max(groups.length, 1) * 32);
-  const sigs = new Uint8Array(Math.max(n, 1) * 192);
-  const sigLen = new Uint32Array(Math.max(n, 1));
-  let i = 0, k = 0, r = 0, b = 0;
-  groups.forEach((g, gi) => {
-    msgs.set(g.message, 32 * gi);
-    for (const s of g.sets) {
-      if (s.committee) {
-        const c = s.committee;
-        if (s.bits.length !== ((c.length + 7) >> 3)) throw Error(`committee set: ${s.bits.length} bitfield bytes for ${c.length} members`);
-        src.set([c.list, c.offset, c.length, b], 4 * i);
-        bits.set(s.bits, b);
-        b += s.bits.length;
-      } else {
-        src.set([SRC_EXPLICIT, k, s.publicKeys.length, 0], 4 * i);
-        for (const pk of s.publicKeys) {
-          if (typeof pk === "number") pkIndices[k++] = pk >>> 0;
-          else if (pk.raw) { pkIndices[k++] = (RAW_BIT | r) >>> 0; rawPks.set(pk.raw, 96 * r++); } else pkIndices[k++] = pk.index >>> 0;
-        }
-      }
-      sigLen[i] = s.signature.length;
-      if (s.signature.length === 96 || s.signature.length === 192) sigs.set(s.signature, 192 * i);
-      i++;
-    }
-    groupOffsets[gi + 1] = i;
-  });
-  return {groupOffsets, src, bits, pkIndices, msgs, sigs, sigLen, rawPks};
+  return encodeGroups(groups, "sources", (w, s) => (s.committee ? w.committee(s) : w.run(s.publicKeys, true)));
+}
+
+// The routing rule of both classes for aggregate sets that sign one message: a call that holds a committee set goes
+// through bgv_verify_same_message_bits (the key count comes from the device, after the call); any other call takes
+// exactly the path it took before (the key count is the batch's, n sets, added before the call).  Returns the batch,
+// the addon call, and the two additions to lodestar_bls_aggregated_pubkeys_total.
+function routeAggregateSets(groups, n, sync = false) {
+  const bits = hasCommitteeKeys(groups);
+  const batch = bits ? encodeSameMessageBits(groups) : encodeSameMessageAgg(groups);
+  const entry = (bits ? "verifySameMessageBits" : "verifySameMessageAgg") + (sync ? "Sync" : "");
+  return {call: (ctx) => addon[entry](ctx, batch), keysBefore: bits ? 0 : batch.pkOffsets[n], keysAfter: (res) => (bits ? res.pubkeysAggregated : 0)};
+}
+
+// booleans of the verdicts valid[lo .. hi)
+function toBooleans(valid, lo = 0, hi = valid.length) {
+  return Array.from(valid.subarray(lo, hi), (v) => v === 1);
+}
+
+// verifyAndAggregateSameMessage's request, for both classes: the result of a call without sets, or the call to queue
+function aggregateRequest(sets, message, opts) {
+  checkAggregateOpts(sets, opts);
+  const previous = opts.previous != null ? opts.previous : null;
+  if (sets.length === 0) return {result: {valid: [], aggregate: Uint8Array.from(previous || G2_IDENTITY_96), count: 0}};
+  checkSameMessage(sets, message);
+  return {call: {sets, message, agg: {previous, take: opts.take != null ? opts.take : null}}};
+}
+
+// the batch of one verifySameMessageAggregate device call over merged calls with n sets
+function encodeAggregateCalls(calls, merged, n) {
+  return {...encodeSameMessage(merged.groups), ...encodeAggregateSide(calls, merged, n)};
 }
 
 // device work of a job in Montgomery Fp products (lodestar_amd/dist.py
@@ -585,6 +572,145 @@ function recordSmRetry(m, ctx) {
   m.sm_retry_pairs += p.pairs;
 }
 
+// The buffered queue of one family of same-message calls (the pool holds two: single-key sets and aggregate sets).
+// Batchable calls wait in a buffer of their own under the pool's rule (100 ms, or more than MAX_BUFFERED_SIGS
+// signatures waiting); whatever is queued goes out as ONE merged device call on one bulk context, one group per
+// call, calls with byte-equal messages sharing a group.  `kind` gives what differs between the two:
+//   started, retries: the names of the family's two counters in the pool's metrics
+//   encode(jobs, merged, n) -> send: encodes the merged call; send(ctx, metrics) issues it and resolves the addon's result
+//   countFirst: the device call is counted before it is encoded (else after)
+//   share(job, k, res, merged, metrics): call k's share of the result, or the Error that rejects it alone
+class SameMessageQueue {
+  constructor(pool, kind) {
+    this.pool = pool;
+    this.kind = kind;
+    this.jobs = [];
+    this.buffered = null;
+    this.running = false;
+    this.deviceCalls = 0; // merged device calls issued (test hook)
+    this.run = this.run.bind(this);
+    this.flush = this.flush.bind(this);
+  }
+
+  queue(call, batchable) {
+    return new Promise((resolve, reject) => {
+      const job = {...call, resolve, reject};
+      if (batchable) {
+        if (!this.buffered) this.buffered = {jobs: [], sigCount: 0, timeout: setTimeout(this.flush, MAX_BUFFER_WAIT_MS)};
+        this.buffered.jobs.push(job);
+        this.buffered.sigCount += call.sets.length;
+        if (this.buffered.sigCount > MAX_BUFFERED_SIGS) {
+          clearTimeout(this.buffered.timeout);
+          this.flush();
+        }
+      } else {
+        this.jobs.push(job);
+        setTimeout(this.run, 0);
+      }
+    });
+  }
+
+  flush() {
+    if (this.buffered) {
+      this.jobs.push(...this.buffered.jobs);
+      this.buffered = null;
+      setTimeout(this.run, 0);
+    }
+  }
+
+  async run() {
+    const pool = this.pool;
+    if (pool.closed || this.running || this.jobs.length === 0) return;
+    this.running = true;
+    const jobs = [];
+    let n = 0;
+    while (this.jobs.length > 0 && (jobs.length === 0 || n + this.jobs[0].sets.length <= pool.maxSetsPerDeviceBatch)) {
+      const j = this.jobs.shift();
+      jobs.push(j);
+      n += j.sets.length;
+    }
+    const m = pool.metrics;
+    try {
+      const merged = mergeSameMessage(jobs);
+      const {best} = pool.idleContexts();
+      let send = this.kind.countFirst ? null : this.kind.encode(jobs, merged, n);
+      this.deviceCalls++;
+      m[this.kind.started] += n;
+      if (!send) send = this.kind.encode(jobs, merged, n);
+      const ctx = pool.ctxs[best >= 0 ? best : 0];
+      const res = await send(ctx, m);
+      m[this.kind.retries] += res.groupsRetried;
+      recordSmRetry(m, ctx);
+      m.lodestar_bls_thread_pool_time_seconds_sum += (res.workerEndMs - res.workerStartMs) / 1000;
+      jobs.forEach((job, k) => {
+        const r = this.kind.share(job, k, res, merged, m);
+        if (r instanceof Error) job.reject(r);
+        else job.resolve(r);
+      });
+    } catch (e) {
+      for (const job of jobs) job.reject(e);
+    }
+    this.running = false;
+    if (this.jobs.length > 0) setTimeout(this.run, 0);
+  }
+
+  // calls and sets waiting, for canAcceptWork
+  waiting() {
+    let sets = this.buffered ? this.buffered.sigCount : 0;
+    for (const j of this.jobs) sets += j.sets.length;
+    return {jobs: this.jobs.length + (this.buffered ? this.buffered.jobs.length : 0), sets};
+  }
+
+  // rejects what is buffered and queued (the pool is closing)
+  abort() {
+    if (this.buffered) {
+      clearTimeout(this.buffered.timeout);
+      for (const job of this.buffered.jobs) job.reject(new QueueError());
+      this.buffered = null;
+    }
+    for (const job of this.jobs) job.reject(new QueueError());
+    this.jobs = [];
+  }
+}
+
+// verifySignatureSetsSameMessage and verifyAndAggregateSameMessage (bgv_verify_same_message, or
+// bgv_verify_same_message_aggregate once a queued call asks for its aggregate)
+const SINGLE_KEY_SETS = {
+  started: "lodestar_bls_thread_pool_same_message_sig_sets_started_total",
+  retries: "lodestar_bls_thread_pool_same_message_retries_total",
+  countFirst: true,
+  encode(jobs, merged, n) {
+    if (jobs.some((j) => j.agg)) {
+      const batch = encodeAggregateCalls(jobs, merged, n);
+      return (ctx) => addon.verifySameMessageAggregate(ctx, batch);
+    }
+    const batch = encodeSameMessage(merged.groups);
+    return (ctx) => addon.verifySameMessage(ctx, batch);
+  },
+  share(job, k, res, merged, m) {
+    const r = aggregateCallResult(addon, job, res, merged.where[k], merged.groupOf[k]);
+    if (job.agg && !(r instanceof Error)) m.lodestar_bls_thread_pool_same_message_aggregated_sigs_total += r.count;
+    return r;
+  },
+};
+
+// verifyAggregateSetsSameMessage (bgv_verify_same_message_agg, or bgv_verify_same_message_bits: routeAggregateSets)
+const AGGREGATE_SETS = {
+  started: "lodestar_bls_thread_pool_same_message_agg_sig_sets_started_total",
+  retries: "lodestar_bls_thread_pool_same_message_agg_retries_total",
+  countFirst: false,
+  encode(jobs, merged, n) {
+    const route = routeAggregateSets(merged.groups, n);
+    return async (ctx, m) => {
+      m.lodestar_bls_aggregated_pubkeys_total += route.keysBefore;
+      const res = await route.call(ctx);
+      m.lodestar_bls_aggregated_pubkeys_total += route.keysAfter(res);
+      return res;
+    };
+  },
+  share: (job, k, res, merged) => toBooleans(res.valid, merged.where[k][0], merged.where[k][1]),
+};
+
 class BlsGpuVerifier {
   // devices: HIP device ordinals, one context each, all owned by this process
   // (chain/chain.ts:199-202 constructs one verifier per node); every context
@@ -669,21 +795,18 @@ class BlsGpuVerifier {
     this.metrics = newMetrics();
     this.runJob = this.runJob.bind(this);
     this.runBufferedJobs = this.runBufferedJobs.bind(this);
-    // verifySignatureSetsSameMessage: a queue and a buffer of their own
-    this.smJobs = [];
-    this.smBuffered = null;
-    this.smRunning = false;
-    this.smDeviceCalls = 0; // merged device calls issued (test hook)
-    this.runSameMessage = this.runSameMessage.bind(this);
-    this.flushSameMessage = this.flushSameMessage.bind(this);
-    // verifyAggregateSetsSameMessage: again a queue and a buffer of their own
-    this.smaJobs = [];
-    this.smaBuffered = null;
-    this.smaRunning = false;
-    this.smaDeviceCalls = 0; // merged device calls issued (test hook)
-    this.runSameMessageAgg = this.runSameMessageAgg.bind(this);
-    this.flushSameMessageAgg = this.flushSameMessageAgg.bind(this);
+    // verifySignatureSetsSameMessage and verifyAggregateSetsSameMessage: a queue and a buffer of their own each
+    this.sm = new SameMessageQueue(this, SINGLE_KEY_SETS);
+    this.sma = new SameMessageQueue(this, AGGREGATE_SETS);
+    this.runSameMessage = this.sm.run;
+    this.flushSameMessage = this.sm.flush;
+    this.runSameMessageAgg = this.sma.run;
+    this.flushSameMessageAgg = this.sma.flush;
   }
+
+  // merged device calls issued per family (test hooks)
+  get smDeviceCalls() { return this.sm.deviceCalls; }
+  get smaDeviceCalls() { return this.sma.deviceCalls; }
 
   // syncPubkeys / addPubkey (pubkeyCache.ts:56-77): 48-byte compressed keys, every replica
   syncPubkeys(firstIndex, pubkeys48) {
@@ -729,12 +852,10 @@ class BlsGpuVerifier {
   // not (gating on idle devices would stop the network processor,
   // network/processor/index.ts:406, for every 5-40 ms device batch)
   canAcceptWork() {
-    const smJobs = this.smJobs.length + (this.smBuffered ? this.smBuffered.jobs.length : 0) +
-      this.smaJobs.length + (this.smaBuffered ? this.smaBuffered.jobs.length : 0);
-    let smSets = (this.smBuffered ? this.smBuffered.sigCount : 0) + (this.smaBuffered ? this.smaBuffered.sigCount : 0);
-    for (const j of this.smJobs) smSets += j.sets.length;
-    for (const j of this.smaJobs) smSets += j.sets.length;
-    return !this.closed && this.jobs.length + smJobs < MAX_JOBS_CAN_ACCEPT_WORK && this.queuedSets + smSets < this.maxSetsPerDeviceBatch;
+    const sm = this.sm.waiting();
+    const sma = this.sma.waiting();
+    return !this.closed && this.jobs.length + sm.jobs + sma.jobs < MAX_JOBS_CAN_ACCEPT_WORK &&
+      this.queuedSets + sm.sets + sma.sets < this.maxSetsPerDeviceBatch;
   }
 
   // IBlsVerifier.verifySignatureSetsSameMessage (upstream Lodestar; the call
@@ -749,7 +870,7 @@ class BlsGpuVerifier {
     if (this.closed) throw new QueueError();
     if (sets.length === 0) return [];
     checkSameMessage(sets, message);
-    return this.queueSameMessage({sets, message, addedTimeMs: Date.now()}, opts.batchable);
+    return this.sm.queue({sets, message, addedTimeMs: Date.now()}, opts.batchable);
   }
 
   // verifySignatureSetsSameMessage that also returns what the caller's
@@ -763,76 +884,8 @@ class BlsGpuVerifier {
   // decode rejects this call alone with BLST_ERROR: BLST_<NAME>.
   async verifyAndAggregateSameMessage(sets, message, opts = {}) {
     if (this.closed) throw new QueueError();
-    checkAggregateOpts(sets, opts);
-    if (sets.length === 0) return {valid: [], aggregate: Uint8Array.from(opts.previous != null ? opts.previous : G2_IDENTITY_96), count: 0};
-    checkSameMessage(sets, message);
-    const agg = {previous: opts.previous != null ? opts.previous : null, take: opts.take != null ? opts.take : null};
-    return this.queueSameMessage({sets, message, agg, addedTimeMs: Date.now()}, opts.batchable);
-  }
-
-  queueSameMessage(call, batchable) {
-    return new Promise((resolve, reject) => {
-      const job = {...call, resolve, reject};
-      const sets = call.sets;
-      if (batchable) {
-        if (!this.smBuffered) this.smBuffered = {jobs: [], sigCount: 0, timeout: setTimeout(this.flushSameMessage, MAX_BUFFER_WAIT_MS)};
-        this.smBuffered.jobs.push(job);
-        this.smBuffered.sigCount += sets.length;
-        if (this.smBuffered.sigCount > MAX_BUFFERED_SIGS) {
-          clearTimeout(this.smBuffered.timeout);
-          this.flushSameMessage();
-        }
-      } else {
-        this.smJobs.push(job);
-        setTimeout(this.runSameMessage, 0);
-      }
-    });
-  }
-
-  flushSameMessage() {
-    if (this.smBuffered) {
-      this.smJobs.push(...this.smBuffered.jobs);
-      this.smBuffered = null;
-      setTimeout(this.runSameMessage, 0);
-    }
-  }
-
-  async runSameMessage() {
-    if (this.closed || this.smRunning || this.smJobs.length === 0) return;
-    this.smRunning = true;
-    const jobs = [];
-    let n = 0;
-    while (this.smJobs.length > 0 && (jobs.length === 0 || n + this.smJobs[0].sets.length <= this.maxSetsPerDeviceBatch)) {
-      const j = this.smJobs.shift();
-      jobs.push(j);
-      n += j.sets.length;
-    }
-    const m = this.metrics;
-    try {
-      const merged = mergeSameMessage(jobs);
-      const {groups, where} = merged;
-      const {best} = this.idleContexts();
-      this.smDeviceCalls++;
-      m.lodestar_bls_thread_pool_same_message_sig_sets_started_total += n;
-      const ctx = this.ctxs[best >= 0 ? best : 0];
-      const withAgg = jobs.some((j) => j.agg);
-      const res = withAgg
-        ? await addon.verifySameMessageAggregate(ctx, {...encodeSameMessage(groups), ...encodeAggregateSide(jobs, merged, n)})
-        : await addon.verifySameMessage(ctx, encodeSameMessage(groups));
-      m.lodestar_bls_thread_pool_same_message_retries_total += res.groupsRetried;
-      recordSmRetry(m, ctx);
-      m.lodestar_bls_thread_pool_time_seconds_sum += (res.workerEndMs - res.workerStartMs) / 1000;
-      jobs.forEach((job, k) => {
-        const r = withAgg ? aggregateCallResult(addon, job, res, where[k], merged.groupOf[k]) : Array.from(res.valid.subarray(where[k][0], where[k][1]), (v) => v === 1);
-        if (r instanceof Error) return job.reject(r);
-        if (job.agg) m.lodestar_bls_thread_pool_same_message_aggregated_sigs_total += r.count;
-        job.resolve(r);
-      });
-    } catch (e) {
-      for (const job of jobs) job.reject(e);
-    }
-    this.smRunning = false;
-    if (this.smJobs.length > 0) setTimeout(this.runSameMessage, 0);
+    const r = aggregateRequest(sets, message, opts);
+    return r.result || this.sm.queue({...r.call, addedTimeMs: Date.now()}, opts.batchable);
   }
 
   // verifySignatureSetsSameMessage for aggregate sets (the aggregates of gossip
@@ -847,65 +900,7 @@ class BlsGpuVerifier {
     if (this.closed) throw new QueueError();
     if (sets.length === 0) return [];
     checkAggregateSameMessage(sets, message);
-    return new Promise((resolve, reject) => {
-      const job = {resolve, reject, sets, message, addedTimeMs: Date.now()};
-      if (opts.batchable) {
-        if (!this.smaBuffered) this.smaBuffered = {jobs: [], sigCount: 0, timeout: setTimeout(this.flushSameMessageAgg, MAX_BUFFER_WAIT_MS)};
-        this.smaBuffered.jobs.push(job);
-        this.smaBuffered.sigCount += sets.length;
-        if (this.smaBuffered.sigCount > MAX_BUFFERED_SIGS) {
-          clearTimeout(this.smaBuffered.timeout);
-          this.flushSameMessageAgg();
-        }
-      } else {
-        this.smaJobs.push(job);
-        setTimeout(this.runSameMessageAgg, 0);
-      }
-    });
-  }
-
-  flushSameMessageAgg() {
-    if (this.smaBuffered) {
-      this.smaJobs.push(...this.smaBuffered.jobs);
-      this.smaBuffered = null;
-      setTimeout(this.runSameMessageAgg, 0);
-    }
-  }
-
-  async runSameMessageAgg() {
-    if (this.closed || this.smaRunning || this.smaJobs.length === 0) return;
-    this.smaRunning = true;
-    const jobs = [];
-    let n = 0;
-    while (this.smaJobs.length > 0 && (jobs.length === 0 || n + this.smaJobs[0].sets.length <= this.maxSetsPerDeviceBatch)) {
-      const j = this.smaJobs.shift();
-      jobs.push(j);
-      n += j.sets.length;
-    }
-    const m = this.metrics;
-    try {
-      const {groups, where} = mergeSameMessage(jobs);
-      const {best} = this.idleContexts();
-      // the routing rule: a merged call that holds a committee set goes through
-      // bgv_verify_same_message_bits (the key count comes from the device); any
-      // other call takes exactly the path it took before
-      const bits = hasCommitteeKeys(groups);
-      const batch = bits ? encodeSameMessageBits(groups) : encodeSameMessageAgg(groups);
-      this.smaDeviceCalls++;
-      m.lodestar_bls_thread_pool_same_message_agg_sig_sets_started_total += n;
-      if (!bits) m.lodestar_bls_aggregated_pubkeys_total += batch.pkOffsets[n];
-      const ctx = this.ctxs[best >= 0 ? best : 0];
-      const res = await (bits ? addon.verifySameMessageBits(ctx, batch) : addon.verifySameMessageAgg(ctx, batch));
-      if (bits) m.lodestar_bls_aggregated_pubkeys_total += res.pubkeysAggregated;
-      m.lodestar_bls_thread_pool_same_message_agg_retries_total += res.groupsRetried;
-      recordSmRetry(m, ctx);
-      m.lodestar_bls_thread_pool_time_seconds_sum += (res.workerEndMs - res.workerStartMs) / 1000;
-      jobs.forEach((job, k) => job.resolve(Array.from(res.valid.subarray(where[k][0], where[k][1]), (v) => v === 1)));
-    } catch (e) {
-      for (const job of jobs) job.reject(e);
-    }
-    this.smaRunning = false;
-    if (this.smaJobs.length > 0) setTimeout(this.runSameMessageAgg, 0);
+    return this.sma.queue({sets, message, addedTimeMs: Date.now()}, opts.batchable);
   }
 
   async verifySignatureSets(sets, opts = {}) {
@@ -1176,20 +1171,8 @@ class BlsGpuVerifier {
     for (const job of this.jobs) job.reject(new QueueError());
     this.jobs = [];
     this.queuedSets = 0;
-    if (this.smBuffered) {
-      clearTimeout(this.smBuffered.timeout);
-      for (const job of this.smBuffered.jobs) job.reject(new QueueError());
-      this.smBuffered = null;
-    }
-    for (const job of this.smJobs) job.reject(new QueueError());
-    this.smJobs = [];
-    if (this.smaBuffered) {
-      clearTimeout(this.smaBuffered.timeout);
-      for (const job of this.smaBuffered.jobs) job.reject(new QueueError());
-      this.smaBuffered = null;
-    }
-    for (const job of this.smaJobs) job.reject(new QueueError());
-    this.smaJobs = [];
+    this.sm.abort();
+    this.sma.abort();
     for (const c of this.allContexts()) addon.close(c); // each waits for its batch in flight (the context mutex)
   }
 }
@@ -1238,20 +1221,16 @@ class BlsGpuSingleThreadVerifier {
     if (this.closed) throw new QueueError();
     if (sets.length === 0) return [];
     checkSameMessage(sets, message);
-    const res = addon.verifySameMessageSync(this.ctx, encodeSameMessage([{message, sets}]));
-    return Array.from(res.valid, (v) => v === 1);
+    return toBooleans(addon.verifySameMessageSync(this.ctx, encodeSameMessage([{message, sets}])).valid);
   }
 
   // verifyAndAggregateSameMessage on the calling thread: one device call, one group
   async verifyAndAggregateSameMessage(sets, message, opts = {}) {
     if (this.closed) throw new QueueError();
-    checkAggregateOpts(sets, opts);
-    if (sets.length === 0) return {valid: [], aggregate: Uint8Array.from(opts.previous != null ? opts.previous : G2_IDENTITY_96), count: 0};
-    checkSameMessage(sets, message);
-    const call = {sets, message, agg: {previous: opts.previous != null ? opts.previous : null, take: opts.take != null ? opts.take : null}};
+    const {result, call} = aggregateRequest(sets, message, opts);
+    if (result) return result;
     const merged = mergeSameMessage([call]);
-    const batch = {...encodeSameMessage(merged.groups), ...encodeAggregateSide([call], merged, sets.length)};
-    const res = addon.verifySameMessageAggregateSync(this.ctx, batch);
+    const res = addon.verifySameMessageAggregateSync(this.ctx, encodeAggregateCalls([call], merged, sets.length));
     const r = aggregateCallResult(addon, call, res, merged.where[0], 0);
     if (r instanceof Error) throw r;
     return r;
@@ -1262,16 +1241,11 @@ class BlsGpuSingleThreadVerifier {
     if (this.closed) throw new QueueError();
     if (sets.length === 0) return [];
     checkAggregateSameMessage(sets, message);
-    const groups = [{message, sets}];
-    if (hasCommitteeKeys(groups)) {  // the routing rule of runSameMessageAgg
-      const res = addon.verifySameMessageBitsSync(this.ctx, encodeSameMessageBits(groups));
-      this.metrics.lodestar_bls_aggregated_pubkeys_total += res.pubkeysAggregated;
-      return Array.from(res.valid, (v) => v === 1);
-    }
-    const batch = encodeSameMessageAgg(groups);
-    this.metrics.lodestar_bls_aggregated_pubkeys_total += batch.pkOffsets[sets.length];
-    const res = addon.verifySameMessageAggSync(this.ctx, batch);
-    return Array.from(res.valid, (v) => v === 1);
+    const route = routeAggregateSets([{message, sets}], sets.length, true);
+    this.metrics.lodestar_bls_aggregated_pubkeys_total += route.keysBefore;
+    const res = route.call(this.ctx);
+    this.metrics.lodestar_bls_aggregated_pubkeys_total += route.keysAfter(res);
+    return toBooleans(res.valid);
   }
 
   async close() {

@@ -71,21 +71,27 @@ ADDON = os.path.join(NAPI_DIR, "bgv.node")
 NODE_INCLUDE = [d for d in ("/usr/include/node", "/usr/include/nodejs/src") if os.path.exists(os.path.join(d, "node_api.h"))]
 
 
-def build_addon(force=False):
+def build_addon(force=False, lib_dir=None, out=None):
     """N-API addon lodestar_amd/napi/bgv.node over libbgv.so (INTEGRATION.md
     section 3).  gcc against the system node_api.h; rpath points at the
-    library one directory up.  Returns None when no Node headers exist."""
+    library one directory up.  Returns None when no Node headers exist.
+    lib_dir / out: link a copy at `out` against the libbgv.so in `lib_dir`
+    instead (tools/gen_napi_binding_golden.py: a stand-in library)."""
     if not NODE_INCLUDE:
         return None
-    build()
+    if lib_dir is None:
+        build()
+    lib_dir = lib_dir or os.path.dirname(LIB)
+    out = out or ADDON
     src = os.path.join(NAPI_DIR, "bgv_addon.c")
-    if (not force and os.path.exists(ADDON) and os.path.getmtime(ADDON) >= os.path.getmtime(src)
-            and os.path.getmtime(ADDON) >= os.path.getmtime(os.path.join(ROOT, "include", "bgv.h"))):
-        return ADDON
+    if (not force and os.path.exists(out) and os.path.getmtime(out) >= os.path.getmtime(src)
+            and os.path.getmtime(out) >= os.path.getmtime(os.path.join(ROOT, "include", "bgv.h"))):
+        return out
+    rpath = os.path.join("$ORIGIN", os.path.relpath(lib_dir, os.path.dirname(os.path.abspath(out))))
     subprocess.check_call(["gcc", "-O2", "-shared", "-fPIC", "-Wall", "-DNODE_GYP_MODULE_NAME=bgv",
-                           "-I" + NODE_INCLUDE[0], "-I" + os.path.join(ROOT, "include"), src, "-o", ADDON,
-                           "-L" + os.path.dirname(LIB), "-lbgv", "-lpthread", "-Wl,-rpath,$ORIGIN/.."])
-    return ADDON
+                           "-I" + NODE_INCLUDE[0], "-I" + os.path.join(ROOT, "include"), src, "-o", out,
+                           "-L" + lib_dir, "-lbgv", "-lpthread", "-Wl,-rpath," + rpath])
+    return out
 
 
 if __name__ == "__main__":
